@@ -11,10 +11,12 @@ Frames are resident in HBM before the timed region.  N>1: one process per GPU (t
 (weak scaling, no data-path collective); the per-frame records {n, keypoints, descriptors, pose} of every step are packed by one kernel and gathered to
 rank 0 with one RCCL gather per step on a side stream inside the timed region (BASELINE config 5).  value = all ranks' frames / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel class by summed HIP-event time inside the timed region), `cpu_baseline` (the oracle —
-CPU restatement of the reference path — timed on host cores) and `config2` (the ORB extract + match + pose-opt chain without detector / LK / RANSAC:
-BASELINE configs[1]), `host_input` (the same full chain fed from pinned host buffers: BGR + depth uploaded over PCIe and converted to gray inside the timed region)
-and `config4` (BASELINE configs[3]: bundle adjustment of 2 000 keyframes / 50 000 landmarks, seconds per call with a per-kernel-class roofline table).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and reports the headline figure (`value`, `ms_per_step`) with the chain's
+statistics of the last step; `--dump-outputs DIR` also writes what the timed path returned for its last step as .npy files.  With `--full` the line also carries
+`roofline` (dominant kernel class by summed HIP-event time inside the timed region), the ATE against ground truth, `cpu_baseline` (the oracle — CPU restatement of
+the reference path — timed on host cores) and `config2` (the ORB extract + match + pose-opt chain without detector / LK / RANSAC: BASELINE configs[1]),
+`host_input` (the same full chain fed from pinned host buffers: BGR + depth uploaded over PCIe and converted to gray inside the timed region) and `config4`
+(BASELINE configs[3]: bundle adjustment of 2 000 keyframes / 50 000 landmarks, seconds per call with a per-kernel-class roofline table); without it they are null.
 """
 import argparse
 import json
@@ -87,6 +89,46 @@ def latest_profile(name):
     raise FileNotFoundError(name)
 
 
+DUMP_SAMPLE = 64           # streams whose keypoints, descriptors and boxes --dump-outputs writes (a fixed, seeded sample; about 10 MB)
+
+
+def dump_outputs(out_dir, tr, res, with_detector, max_boxes, device, dsync):
+    """--dump-outputs: what a caller of the timed path receives for its last step, as out_dir/<name>.npy in float32 / float64.  Every stream: pose (Tcw) and the
+    per-frame counts of tr.read().  A fixed sample of streams: the frame record of sgx_tracker_pack_records_dev (cv::KeyPoint fields, descriptor bytes) and the
+    detector's person boxes; entries past a frame's count are zeroed, so that nothing left over from earlier frames is compared."""
+    import torch
+    from sg_slam_amd.capi import KP_DTYPE
+    os.makedirs(out_dir, exist_ok=True)
+    S, cap = tr.S, tr.cap
+    out = {'Tcw': res['Tcw'].reshape(S, 4, 4).astype(np.float32)}
+    for k in ('nkeys', 'nkeys_raw', 'nmatch', 'ninl', 'nmatch_local', 'ninl2', 'f_ok', 'f_stats'):
+        out[k] = res[k].astype(np.float64)
+    sample = np.sort(np.random.default_rng(0).choice(S, min(S, DUMP_SAMPLE), replace=False))
+    out['sample_streams'] = sample.astype(np.float64)
+    rec = torch.zeros((S, tr.rec_bytes), dtype=torch.uint8, device=device)
+    dsync()
+    tr.pack_records(rec)
+    tr.synchronize(); dsync()
+    a = rec.cpu().numpy()[sample]
+    n = a[:, 0:4].copy().view(np.int32)[:, 0]
+    valid = np.arange(cap)[None, :] < n[:, None]
+    kp = a[:, 16:16 + cap * 28].copy().view(KP_DTYPE).reshape(len(sample), cap)
+    out['keypoints'] = np.where(valid[..., None], np.stack([kp[f].astype(np.float32) for f in KP_DTYPE.names], -1), 0).astype(np.float32)
+    desc = a[:, 16 + cap * 28:16 + cap * 60].reshape(len(sample), cap, 32)
+    out['descriptors'] = np.where(valid[..., None], desc, 0).astype(np.float32)
+    if with_detector:
+        bx = torch.zeros((len(sample), max_boxes, 4), dtype=torch.float32, device=device); nb = torch.zeros((len(sample), 1), dtype=torch.int32, device=device)
+        dsync()
+        for j, s in enumerate(sample):
+            tr.snapshot_boxes(int(s), bx[j], nb[j])
+        tr.synchronize(); dsync()
+        nb = nb.cpu().numpy()[:, 0]; bx = bx.cpu().numpy()
+        out['person_boxes'] = np.where((np.arange(max_boxes)[None, :] < nb[:, None])[..., None], bx, 0).astype(np.float32)
+        out['person_box_count'] = nb.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + '.npy'), v)
+
+
 def needs_spawn(gpus, environ):
     """`python bench.py --gpus N` outside torchrun (no WORLD_SIZE): this process becomes the launcher of N ranks.  Under the driver's own
     `python -m torch.distributed.run ... bench.py --gpus N` WORLD_SIZE is set and the process is a rank."""
@@ -140,7 +182,13 @@ def main():
     ap.add_argument('--tum', default='', help='TUM RGB-D sequence directory (rgb/ depth/ associations.txt [groundtruth.txt]): the streams are consecutive chunks of the sequence')
     ap.add_argument('--save-trajectory', default='', help='write stream 0 of rank 0 as a TUM trajectory file (System::SaveTrajectoryTUM format)')
     ap.add_argument('--cpu-sample', type=int, default=120, help='frames timed on the CPU oracle')
+    ap.add_argument('--full', action='store_true', help='also measure and check everything beyond the headline figure: the per-kernel roofline table (HIP-event timing inside the '
+                    'timed region), the ATE against ground truth, the CPU baseline, config2, host input and config4 (each still switched off by its --no-* option)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='after the timed steps, write what the timed path returned for its last step (rank 0\'s streams) as '
+                    'DIR/<name>.npy in float32 / float64: pose and counts of every stream, keypoints, descriptors and person boxes of a fixed sample of streams')
     args = ap.parse_args()
+    if args.config2_only and args.dump_outputs:
+        ap.error('--dump-outputs writes the outputs of the full per-frame path; --config2-only does not run it')
 
     # SGX_BENCH_EMU_TEST=1 (tests/test_bench_gloo.py ONLY): the harness itself — rank set-up, stream sharding, the per-step record gather, max-over-ranks timing, the JSON line —
     # on the tests' kernel-logic emulator with the gloo backend, so that the N > 1 code of THIS file runs in a container without GPUs.  Never a measurement: the line says so.
@@ -307,15 +355,17 @@ def main():
 
     gather = sdist.FrameRecordGather(dist, S, tr.cap, DEV) if dist else None
     NSTEP = args.warmup + args.steps
-    traj = torch.zeros((NSTEP, S, 16), dtype=torch.float32, device=DEV)                     # pose snapshots per step (device copies on the tracking stream)
-    NBOX = min(64, NSTEP)
+    TRAJ = args.full or bool(args.save_trajectory)                                          # the trajectory feeds the ATE (--full) and --save-trajectory only
+    traj = torch.zeros((NSTEP, S, 16), dtype=torch.float32, device=DEV) if TRAJ else None  # pose snapshots per step (device copies on the tracking stream)
+    NBOX = min(64, NSTEP) if args.full else 0
     box_log = torch.zeros((NBOX, MB, 4), dtype=torch.float32, device=DEV); nbox_log = torch.zeros((NBOX, 1), dtype=torch.int32, device=DEV)      # stream 0, for the oracle-chain comparison
     dsync()          # the snapshot copies run on the tracker's own (non-blocking) streams: the zero-fills above must have landed first
 
     def step(i):
         fi = order[i % len(order)]
         tr.step(d_frames[fi], depth_of(fi), d_bgr=d_bgr[fi] if det is not None else None, stream=stream)
-        tr.snapshot_pose(traj[i])
+        if TRAJ:
+            tr.snapshot_pose(traj[i])
         if det is not None and i < NBOX:
             tr.snapshot_boxes(0, box_log[i], nbox_log[i])
         if gather is not None:
@@ -329,8 +379,9 @@ def main():
     dsync()
     if dist: dist.barrier()
     dsync()
-    lib.profile_read(reset=True)
-    lib.profile_enable(True)
+    if args.full:                                   # per-kernel-class HIP events around every launch: the roofline table's input
+        lib.profile_read(reset=True)
+        lib.profile_enable(True)
     gather_bytes0 = gather.bytes_moved if gather else 0
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -341,10 +392,14 @@ def main():
     if dist: dist.barrier()
     dsync()
     dt = time.perf_counter() - t0
-    lib.profile_enable(False)
-    prof = lib.profile_read()
+    prof = {}
+    if args.full:
+        lib.profile_enable(False)
+        prof = lib.profile_read()
     tr.last_status(stream=stream)
     res = tr.read()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, res, det is not None, MB, DEV, dsync)
     nkp, nmatch, ninl, nmatch_local, ninl2, n_raw, f_ok, f_stats = (res[k] for k in ('nkeys', 'nmatch', 'ninl', 'nmatch_local', 'ninl2', 'nkeys_raw', 'f_ok', 'f_stats'))
     if not args.no_local_map:
         ninl = ninl2
@@ -361,12 +416,12 @@ def main():
 
     # ---- accuracy over the WHOLE run (warm-up + timed steps): per-stream Horn-aligned ATE against the synthetic ground truth (or groundtruth.txt)
     N = NSTEP
-    est = traj.cpu().numpy().reshape(N, S, 4, 4).astype('f8')
+    est = traj.cpu().numpy().reshape(N, S, 4, 4).astype('f8') if TRAJ else None
     ate_gt = None; ate_sq = 0.0; ate_cnt = 0; ate_excl = 0
-    if not args.tum:
+    if args.full and not args.tum:
         gt = np.stack([np.stack([gen.Tcw(t0 + order[i % len(order)]) for t0 in t0s]) for i in range(N)])
         ate_gt, ate_sq, ate_cnt, ate_excl = ate_pooled(est, gt)
-    elif gt_tum is not None:
+    elif args.full and gt_tum is not None:
         gst, gxyz, _ = gt_tum
         for s in range(S):
             st_s = np.array([stamps[s, order[i % len(order)]] for i in range(N)])
@@ -389,13 +444,13 @@ def main():
         tum.save_trajectory_tum(args.save_trajectory, st0, [est[i, 0] for i in range(N)])
 
     c2 = None
-    if not args.no_config2 and not args.tum:
+    if args.full and not args.no_config2 and not args.tum:
         del traj
         c2 = run_config2(args.config2_steps, 4)
 
     # ------------------------------------------------------------------------------------------------ host-input mode: the same chain fed from host memory
     host_in = None
-    if not args.no_host_input and not args.tum and world == 1:
+    if args.full and not args.no_host_input and not args.tum and world == 1:
         # what a caller that holds cv::imread's images does (rgbd_tum.cc:114-115): BGR + 16-bit depth of every stream are uploaded from pinned host buffers on the tracker's
         # upload stream and converted to gray on the device (Tracking.cc:214-227) INSIDE the timed region.  The two staging slots are filled once (decode / disk are the
         # caller's); every step moves S x (921 600 + 614 400) bytes over PCIe.
@@ -422,7 +477,7 @@ def main():
 
     # ------------------------------------------------------------------------------------------------ BASELINE configs[3]: bundle adjustment, 2 000 keyframes / 50 000 landmarks
     c4 = None
-    if not args.no_config4 and not args.tum and world == 1:
+    if args.full and not args.no_config4 and not args.tum and world == 1:
         sys.path.insert(0, os.path.join(ROOT, 'tests'))
         from scenes import make_big_ba_problem, CAM as BA_CAM          # the seeded generator the parity tests use (SURVEY.md §8(d) input 4)
         from sg_slam_amd.optimizer import Optimizer
@@ -578,7 +633,7 @@ def main():
                 roofline['orb_stage']['frac_of_valu_issue_standalone'] = round(roofline['orb_stage']['valu_issue_ms_per_step'] / orb_sa, 4)
 
     cpu = None; ate_oracle = None
-    if not args.no_cpu_baseline and world == 1 and not args.tum:
+    if args.full and not args.no_cpu_baseline and world == 1 and not args.tum:
         # the oracle chained exactly like the tracker (checker/baseline leg only — never the measured product path): 1 core in-process, then
         # frames-parallel on all host cores (one worker process per core, each its own stream), as SURVEY.md §8(d) asks
         from oracle import cpu_chain
@@ -652,7 +707,7 @@ def main():
                    'mean_keypoints': float(nkp.mean()), 'mean_keypoints_before_mask': float(n_raw.mean()), 'mean_matches': float(nmatch.mean()), 'mean_inliers': float(ninl.mean()),
                    'fundamental_ok_frac': float(f_ok.mean()), 'mean_ransac_iterations': float(f_stats[:, 0].mean()),
                    'tracked_streams_last_frame': tracked, 'trajectory_frames_per_stream': N,
-                   'ate_rmse_m_vs_ground_truth': ate_gt, 'ate_streams_excluded': ate_excl, 'ate_vs_oracle_chain': ate_oracle,
+                   'ate_rmse_m_vs_ground_truth': ate_gt, 'ate_streams_excluded': ate_excl if args.full else None, 'ate_vs_oracle_chain': ate_oracle,
                    'frame_record_gather': None if gather is None else {'collective': 'gather to rank 0 (torch.distributed over RCCL), one per step, records packed by one kernel (sgx_tracker_pack_records_dev)',
                                                                        'bytes_per_step': gather._step_bytes(), 'record_bytes': gather.rec_bytes, 'records_per_step': gather.world * S,
                                                                        'GBs_into_rank0_over_xgmi': (gather.bytes_moved - gather_bytes0) / dt / 1e9, 'inside_timed_region': True},

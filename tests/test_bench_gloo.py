@@ -27,7 +27,7 @@ def _run(nproc, extra, gpus_flag=True):
     return json.loads(lines[0])
 
 
-ARGS = ['--steps', '2', '--warmup', '1', '--streams', '2', '--frames', '3', '--no-detector', '--no-config2', '--no-config4', '--no-host-input', '--no-cpu-baseline']
+ARGS = ['--steps', '2', '--warmup', '1', '--streams', '2', '--frames', '3', '--no-detector', '--no-config2', '--no-config4', '--no-host-input', '--no-cpu-baseline', '--full']
 
 
 def test_bench_two_ranks_gloo():

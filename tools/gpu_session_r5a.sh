@@ -5,8 +5,8 @@ set -u
 O=gpurun_out/r5a; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 ( time timeout 1200 python -m pytest tests -m gpu -q -p no:cacheprovider -s 2>&1 | tail -150 ) > $O/gpu_tests.log 2>&1
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err
-Q="--no-cpu-baseline --no-config2 --no-config4 --no-host-input --steps 60 --warmup 8"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err
+Q="--full --no-cpu-baseline --no-config2 --no-config4 --no-host-input --steps 60 --warmup 8"
 for rep in 1 2; do
   timeout 300 python bench.py $Q > $O/ab_base_$rep.json 2>> $O/ab.err
   timeout 300 python bench.py $Q --groups 2 > $O/ab_groups2_$rep.json 2>> $O/ab.err

@@ -6,7 +6,7 @@ O=gpurun_out/r5b; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 ( time timeout 1200 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -60 ) > $O/gpu_tests.log 2>&1
 tail -4 $O/gpu_tests.log
-Q="--no-cpu-baseline --no-config2 --no-config4 --no-host-input --steps 60 --warmup 8"
+Q="--full --no-cpu-baseline --no-config2 --no-config4 --no-host-input --steps 60 --warmup 8"
 ab() { name=$1; shift; env SGX_BENCH_TAPS_LIB=1 "$@" timeout 300 python bench.py $Q > $O/ab_$name.json 2>> $O/ab.err; }
 ab base_taps_1
 ab irb_split300 SGX_IRB_SPLIT=300

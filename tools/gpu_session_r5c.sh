@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/r5c; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-Q="--no-cpu-baseline --no-config2 --no-config4 --steps 40 --warmup 8 --host-steps 60"
+Q="--full --no-cpu-baseline --no-config2 --no-config4 --steps 40 --warmup 8 --host-steps 60"
 ab() { name=$1; shift; env "$@" timeout 300 python bench.py $Q > $O/hi_$name.json 2>> $O/ab.err; }
 ab product_1 X=1
 ab fork1 SGX_BENCH_TAPS_LIB=1 SGX_DET_FORK=1

@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/r5d; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-Q="--no-cpu-baseline --no-config2 --no-config4 --no-host-input --steps 60 --warmup 8"
+Q="--full --no-cpu-baseline --no-config2 --no-config4 --no-host-input --steps 60 --warmup 8"
 timeout 300 python bench.py $Q > $O/sc_layered.json 2>> $O/ab.err
 timeout 300 python bench.py $Q --scene dynamic > $O/sc_dynamic.json 2>> $O/ab.err
 timeout 300 python bench.py $Q --scene dynamic --person-logit 0 > $O/sc_dynamic_person0.json 2>> $O/ab.err

@@ -9,7 +9,7 @@ SGX_DET_HRB=0 timeout 300 python tools/prof_det_ops.py 512 5 > $O/det_ops_fb2.tx
 head -8 $O/det_ops_hrb.txt; head -8 $O/det_ops_fb2.txt | tail -6
 ( time timeout 900 python -m pytest tests/test_detector_gpu.py -x -q -p no:cacheprovider 2>&1 | tail -25 ) > $O/gpu_tests_detector.log 2>&1
 tail -12 $O/gpu_tests_detector.log
-Q="--no-cpu-baseline --no-config2 --no-config4 --no-host-input --steps 60 --warmup 8"
+Q="--full --no-cpu-baseline --no-config2 --no-config4 --no-host-input --steps 60 --warmup 8"
 timeout 300 python bench.py $Q > $O/bench_hrb.json 2> $O/bench.err
 SGX_BENCH_TAPS_LIB=1 SGX_DET_HRB=0 timeout 300 python bench.py $Q > $O/bench_fb2.json 2>> $O/bench.err
 for f in $O/bench_hrb.json $O/bench_fb2.json; do python - "$f" <<'PY'

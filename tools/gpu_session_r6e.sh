@@ -5,7 +5,7 @@ O=gpurun_out/r6e; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 ( time timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider -x 2>&1 | tail -30 ) > $O/gpu_tests.log 2>&1
 tail -6 $O/gpu_tests.log
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench.err
 python - <<'PY'
 import json
 j = json.load(open('gpurun_out/r6e/bench_driver_form.json'))
