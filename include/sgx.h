@@ -309,6 +309,20 @@ int sgx_frame_gray_from_color_batch_dev(int batch, int width, int height, const 
 int sgx_frame_stereo_from_rgbd_batch_dev(int batch, int cap, const sgx_keypoint *d_keys, const int32_t *d_n,
                                          const uint16_t *d_depth, int width, int height, float depth_map_factor,
                                          float bf, float *d_uright, float *d_zdepth, void *stream);
+/* ---- lens distortion (Frame::UndistortKeyPoints, Frame.cc:654-684; Frame::ComputeImageBounds, :686-714; mDistCoef, Tracking.cc:66-77) -----------------
+ * dist = k1, k2, p1, p2 [, k3 [, k4, k5, k6]] (ndist 4, 5 or 8, else SGX_ERR_INVALID); K4 = fx, fy, cx, cy.  The undistortion restates OpenCV 3.4's
+ * cv::undistortPoints(src, dst, K, D, noArray(), K): five fixed-point iterations in fp64, the icdist < 0 guard, float outputs.
+ * sgx_undistort_points: n host points (x, y pairs), computed on the device, synchronous; no k1 == 0 shortcut (cv::undistortPoints always iterates). */
+int sgx_undistort_points(int n, const float *pts, const float *K4, const float *dist, int ndist, float *out);
+/* Frame::UndistortKeyPoints fused with Frame::ComputeStereoFromRGBD: d_keys_un = d_keys with pt undistorted (the other 20 bytes of each record, and rows
+ * n..cap-1, are copies), depth read at the distorted pixel, uright = x_un - bf/d; uright / zdepth as sgx_frame_stereo_from_rgbd_batch_dev otherwise.
+ * K and bf come from *cam.  dist[0] == 0 is the reference's early-out (Frame.cc:656-660): d_keys_un is a byte copy of d_keys whatever p1, p2, k3 are. */
+int sgx_frame_undistort_stereo_rgbd_batch_dev(int batch, int cap, const sgx_keypoint *d_keys, const int32_t *d_n, const float *dist, int ndist,
+                                              const sgx_camera *cam, const uint16_t *d_depth, int width, int height, float depth_map_factor,
+                                              sgx_keypoint *d_keys_un, float *d_uright, float *d_zdepth, void *stream);
+/* Frame::ComputeImageBounds: cam->min_x..max_y from the undistorted image corners (0, cols, 0, rows when dist[0] == 0); the other fields are left alone */
+int sgx_frame_image_bounds(int width, int height, const float *K4, const float *dist, int ndist, sgx_camera *cam);
+
 /* Frame::UnprojectStereo (Frame.cc:916-930) for every keypoint: xw = Rwc*x3Dc + Ow, has = depth>0 */
 int sgx_frame_unproject_batch_dev(int batch, int cap, const sgx_keypoint *d_keys, const int32_t *d_n, const float *d_zdepth,
                                   const float *d_Tcw, const sgx_camera *cam, float *d_xw, uint8_t *d_has, void *stream);
@@ -532,6 +546,12 @@ void sgx_tracker_destroy(sgx_tracker *t);
 int sgx_tracker_keypoint_capacity(const sgx_tracker *t);
 int sgx_tracker_record_bytes(const sgx_tracker *t);                   /* 16 + cap * 28 + cap * 32 + 64: the per-frame record of BASELINE config 5 */
 int sgx_tracker_set_initial_pose(sgx_tracker *t, const float *Tcw /* streams x 16, host */);
+/* the camera's distortion coefficients (mDistCoef, Tracking.cc:66-77; ndist 4, 5 or 8), before the first step only (else SGX_ERR_INVALID).  dist[0] == 0: no
+ * change (Frame.cc:656-660 / :707-713 skip everything).  Otherwise the grid / frustum bounds become those of sgx_frame_image_bounds (copied to *out_cam when it
+ * is not NULL; with dist[0] == 0 *out_cam receives the unchanged camera), every frame's keypoints are undistorted beside ComputeStereoFromRGBD, and the
+ * undistorted keypoints (mvKeysUn) feed the matchers, both PoseOptimization calls, the unprojection and the map points; ORB, LK, RANSAC, the dynamic mask
+ * and the erase step keep the raw ones. */
+int sgx_tracker_set_distortion(sgx_tracker *t, const float *dist, int ndist, sgx_camera *out_cam);
 /* one frame of every stream from device memory: d_gray streams x height x gray_pitch u8, d_depth streams x height x width raw u16, d_bgr (optional, detector
  * input) streams x height x bgr_pitch interleaved 3-channel u8.  Asynchronous — a step only ENQUEUES work.  The inputs of a step may be rewritten
  * (a) by work enqueued on `caller_stream` after the THIRD following sgx_tracker_step_dev call (that call orders caller_stream behind the step's readers), or
@@ -568,6 +588,8 @@ void sgx_dist_destroy(sgx_dist *d);
 int sgx_dist_world(const sgx_dist *d, int32_t *world, int32_t *rank);
 int sgx_dist_gather_records(sgx_dist *d, const void *d_send, size_t bytes_per_rank, void *d_recv, int root, void *stream);
 int sgx_tracker_frame_dev(sgx_tracker *t, const int32_t **d_n, const sgx_keypoint **d_keys, const uint8_t **d_desc, const float **d_Tcw, const float **d_xw, const uint8_t **d_has);
+/* the undistorted keypoints (mvKeysUn) of the frame tracked last: the d_keys of sgx_tracker_frame_dev when the tracker has no distortion */
+int sgx_tracker_frame_keys_un_dev(sgx_tracker *t, const sgx_keypoint **d_keys_un);
 sgx_orb *sgx_tracker_extractor(sgx_tracker *t);
 
 /* ---- per-kernel HIP-event timing (process-wide) ---------------------------------------------------

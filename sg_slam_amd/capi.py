@@ -80,7 +80,8 @@ SYMBOLS = [
     'sgx_sim3_solver_set_ransac_parameters', 'sgx_sim3_solver_iterate', 'sgx_sim3_solver_get_estimate', 'sgx_sim3_solver_destroy',
     'sgx_match_search_for_initialization', 'sgx_voc_load', 'sgx_voc_create', 'sgx_voc_info', 'sgx_voc_destroy', 'sgx_voc_transform',
     'sgx_voc_transform_batch_dev', 'sgx_voc_score', 'sgx_match_project_sim3', 'sgx_match_search_by_sim3', 'sgx_optimize_sim3',
-    'sgx_optimize_essential_graph', 'sgx_correct_map_points',
+    'sgx_optimize_essential_graph', 'sgx_correct_map_points', 'sgx_undistort_points', 'sgx_frame_undistort_stereo_rgbd_batch_dev', 'sgx_frame_image_bounds',
+    'sgx_tracker_set_distortion', 'sgx_tracker_frame_keys_un_dev',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -170,6 +171,11 @@ class SgxLib:
         d.sgx_frame_compact_keys_batch_dev.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
         d.sgx_match_project_local.argtypes = [C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 7 + [C.POINTER(Camera), vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp]
         d.sgx_match_project_local_batch_dev.argtypes = [C.c_int, C.c_int] + [vp] * 6 + [C.c_int] + [vp] * 8 + [C.POINTER(Camera), vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]
+        d.sgx_undistort_points.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp]
+        d.sgx_frame_undistort_stereo_rgbd_batch_dev.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.POINTER(Camera), vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp]
+        d.sgx_frame_image_bounds.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, C.POINTER(Camera)]
+        d.sgx_tracker_set_distortion.argtypes = [vp, vp, C.c_int, C.POINTER(Camera)]
+        d.sgx_tracker_frame_keys_un_dev.argtypes = [vp, C.POINTER(vp)]
         d.sgx_frame_make_map_points_batch_dev.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 7 + [C.c_int] + [vp] * 7
         d.sgx_frame_merge_matches_batch_dev.argtypes = [C.c_int, C.c_int] + [vp] * 10
         d.sgx_flow_create.argtypes = [C.POINTER(FlowConfig), C.POINTER(vp)]

@@ -8,7 +8,7 @@
 // in "visual odometry" form (the map points a frame is tracked against are the previous frame's keypoints unprojected with their measured depth,
 // Tracking::UpdateLastFrame :840-904; the local map is the points of frames t-2 and t-3), with the stages spread over three HIP streams:
 //     D  Detector2D::detect of frame t            (the reference runs it on its own thread, Detector2D::Run; Frame.cc:478 waits for it)
-//     E  ORB extract -> LK flow -> RANSAC F -> [event: detector done] -> dynamic mask + erase -> stereo-from-RGBD              of frame t + 1
+//     E  ORB extract -> LK flow -> RANSAC F -> [event: detector done] -> dynamic mask + erase -> [UndistortKeyPoints +] stereo-from-RGBD   of frame t + 1
 //     T  motion model -> SearchByProjection(cur,last) -> PoseOptimization -> SearchLocalPoints -> PoseOptimization -> unproject -> map points   of frame t
 // Frame state is triple-buffered (frame t lives in slot t % 3); events order the streams; nothing synchronises with the host inside a step.
 // An optional upload stream U takes host frames (pinned staging buffers the caller fills, as cv::imread would) to the device and converts
@@ -84,6 +84,8 @@ struct sgx_tracker {
     // triple-buffered frame state
     sgx_keypoint *keys[3]; uint8_t *desc[3]; int32_t *n[3]; float *uright[3], *zdepth[3], *xw[3]; uint8_t *has[3];
     float *Tcw[3];                          // cur, last, last-last (rotating)
+    // lens distortion (sgx_tracker_set_distortion): mvKeysUn per slot; NULL and unused while the camera has none
+    sgx_keypoint *keys_un[3] = { nullptr, nullptr, nullptr }; float dist[8] = {}; int ndist = 0; bool undistort = false;
     int32_t *match, *nmatch, *ninl, *zero_i4; uint8_t *outlier, *zero_u8, *vel_valid;
     float *lm_xw, *lm_normal, *lm_min, *lm_max; uint8_t *lm_desc, *lm_skip; int32_t *lm_obs, *lm_n;
     int32_t *match_local, *nmatch_local, *merged, *cur_mp_obs, *ninl2; uint8_t *in_view, *outlier2; float *xw_all;
@@ -211,6 +213,26 @@ extern "C" int sgx_tracker_set_initial_pose(sgx_tracker *t, const float *Tcw)
     return SGX_OK;
 }
 
+// mDistCoef (Tracking.cc:66-77) before the first frame.  dist[0] == 0 leaves the tracker exactly as it was (the reference skips UndistortKeyPoints and
+// ComputeImageBounds then, Frame.cc:656-660 / :707-713); otherwise Frame::ComputeImageBounds replaces the grid / frustum bounds and mvKeysUn is allocated.
+extern "C" int sgx_tracker_set_distortion(sgx_tracker *t, const float *dist, int ndist, sgx_camera *out_cam)
+{
+    if (!t || !dist || (ndist != 4 && ndist != 5 && ndist != 8) || t->frame_idx > 0) return SGX_ERR_INVALID;
+    if (dist[0] != 0.0f) {
+        const float K4[4] = { t->cfg.cam.fx, t->cfg.cam.fy, t->cfg.cam.cx, t->cfg.cam.cy };
+        sgx_camera cam = t->cfg.cam;
+        TRK_CHECK(sgx_frame_image_bounds(t->cfg.width, t->cfg.height, K4, dist, ndist, &cam));
+        if (!t->keys_un[0]) {
+            for (int i = 0; i < 3; i++) TRK_CHECK(t->alloc(&t->keys_un[i], (size_t)t->S * t->cap));
+            TRK_HIP(hipDeviceSynchronize());       // zero-fills on the null stream, which the tracker's non-blocking streams do not wait for
+        }
+        t->cfg.cam = cam;
+        memcpy(t->dist, dist, (size_t)ndist * sizeof(float)); t->ndist = ndist; t->undistort = true;
+    }
+    if (out_cam) *out_cam = t->cfg.cam;
+    return SGX_OK;
+}
+
 // One frame of every stream.  d_gray: S x H x gray_pitch u8; d_depth: S x H x W u16 (raw, Tracking.cc:229-230 divides by DepthMapFactor);
 // d_bgr (optional, with a detector): S x H x bgr_pitch interleaved 3-channel u8 — what Detector2D::detect sees.  Asynchronous: the inputs are read on the
 // tracker's streams after everything already enqueued on `caller_stream`.  Issuing a step only ENQUEUES work, so "three more steps were issued" says nothing about
@@ -260,7 +282,13 @@ extern "C" int sgx_tracker_step_dev(sgx_tracker *t, const uint8_t *d_gray, int g
         }
     } else
         TRK_CHECK(sgx_orb_extract_batch_dev(t->ex, d_gray, gray_pitch, S, t->keys[c], t->desc[c], t->n[c], cap, sE));
-    TRK_CHECK(sgx_frame_stereo_from_rgbd_batch_dev(S, cap, t->keys[c], t->n[c], d_depth, cf.width, cf.height, cf.depth_map_factor, cf.cam.bf, t->uright[c], t->zdepth[c], sE));
+    // Frame.cc:172-173: UndistortKeyPoints (fused with ComputeStereoFromRGBD in one kernel when the camera has distortion); the tracking stages read mvKeysUn
+    if (t->undistort)
+        TRK_CHECK(sgx_frame_undistort_stereo_rgbd_batch_dev(S, cap, t->keys[c], t->n[c], t->dist, t->ndist, &cf.cam, d_depth, cf.width, cf.height, cf.depth_map_factor,
+                                                            t->keys_un[c], t->uright[c], t->zdepth[c], sE));
+    else
+        TRK_CHECK(sgx_frame_stereo_from_rgbd_batch_dev(S, cap, t->keys[c], t->n[c], d_depth, cf.width, cf.height, cf.depth_map_factor, cf.cam.bf, t->uright[c], t->zdepth[c], sE));
+    const sgx_keypoint *ku_c = t->undistort ? t->keys_un[c] : t->keys[c], *ku_l = t->undistort ? t->keys_un[l] : t->keys[l];
     if (t->pipelined) {
         ev_record(t->ev_extract[c], sE); st_wait(sT, t->ev_extract[c]);
         // "inputs consumed" by the extraction stream's readers; the detector's forward read d_bgr on its own stream and has its own event (ev_det_read[c]): whoever wants to
@@ -270,22 +298,22 @@ extern "C" int sgx_tracker_step_dev(sgx_tracker *t, const uint8_t *d_gray, int g
     // ---- T: Tracking::TrackWithMotionModel (Tracking.cc:906-967)
     if (i > 0) {
         TRK_CHECK(sgx_frame_motion_model_batch_dev(S, Tl, Tll, t->vel_valid, Tc, sT));            // frame 1 has no velocity yet: it starts from the last pose
-        TRK_CHECK(sgx_match_project_frame_batch_dev(S, cap, t->keys[c], t->desc[c], t->uright[c], t->n[c], Tc, t->keys[l], t->n[l], t->has[l], t->zero_u8, t->xw[l], t->zero_i4,
+        TRK_CHECK(sgx_match_project_frame_batch_dev(S, cap, ku_c, t->desc[c], t->uright[c], t->n[c], Tc, ku_l, t->n[l], t->has[l], t->zero_u8, t->xw[l], t->zero_i4,
                                                     t->desc[l], Tl, &cf.cam, t->scale, t->nlevels, cf.th_projection, 0, 1, t->match, t->nmatch, sT));
-        TRK_CHECK(sgx_pose_optimization_batch_dev(S, cap, t->keys[c], t->uright[c], t->n[c], t->match, nullptr, t->xw[l], cap, t->inv_sigma2, t->nlevels, &cf.cam, Tc, t->outlier, t->ninl, sT));
+        TRK_CHECK(sgx_pose_optimization_batch_dev(S, cap, ku_c, t->uright[c], t->n[c], t->match, nullptr, t->xw[l], cap, t->inv_sigma2, t->nlevels, &cf.cam, Tc, t->outlier, t->ninl, sT));
         if (i == 1) TRK_HIP(hipMemsetAsync(t->vel_valid, 1, (size_t)S, sT));
     }
     if (i > 0 && cf.local_map) {
         // ---- Tracking::TrackLocalMap (:969-1013): SearchLocalPoints (isInFrustum + SearchByProjection th = 3) and the second PoseOptimization
         TRK_CHECK(sgx_frame_merge_matches_batch_dev(S, cap, t->n[c], t->match, t->outlier, nullptr, nullptr, nullptr, nullptr, t->cur_mp_obs, nullptr, sT));
-        TRK_CHECK(sgx_match_project_local_batch_dev(S, cap, t->keys[c], t->desc[c], t->uright[c], t->n[c], Tc, t->cur_mp_obs, 2 * cap, t->lm_n, t->lm_xw, t->lm_normal, t->lm_min, t->lm_max,
+        TRK_CHECK(sgx_match_project_local_batch_dev(S, cap, ku_c, t->desc[c], t->uright[c], t->n[c], Tc, t->cur_mp_obs, 2 * cap, t->lm_n, t->lm_xw, t->lm_normal, t->lm_min, t->lm_max,
                                                     t->lm_desc, t->lm_obs, t->lm_skip, &cf.cam, t->scale, t->nlevels, t->log_scale, 3.0f, 0.8f, 0.5f, t->match_local, t->nmatch_local, t->in_view, sT));
         TRK_CHECK(sgx_frame_merge_matches_batch_dev(S, cap, t->n[c], t->match, t->outlier, t->match_local, t->xw[l], t->lm_xw, t->merged, nullptr, t->xw_all, sT));
-        TRK_CHECK(sgx_pose_optimization_batch_dev(S, cap, t->keys[c], t->uright[c], t->n[c], t->merged, nullptr, t->xw_all, 3 * cap, t->inv_sigma2, t->nlevels, &cf.cam, Tc, t->outlier2, t->ninl2, sT));
+        TRK_CHECK(sgx_pose_optimization_batch_dev(S, cap, ku_c, t->uright[c], t->n[c], t->merged, nullptr, t->xw_all, 3 * cap, t->inv_sigma2, t->nlevels, &cf.cam, Tc, t->outlier2, t->ninl2, sT));
     }
-    TRK_CHECK(sgx_frame_unproject_batch_dev(S, cap, t->keys[c], t->n[c], t->zdepth[c], Tc, &cf.cam, t->xw[c], t->has[c], sT));
+    TRK_CHECK(sgx_frame_unproject_batch_dev(S, cap, ku_c, t->n[c], t->zdepth[c], Tc, &cf.cam, t->xw[c], t->has[c], sT));
     if (i > 0 && cf.local_map)      // the last frame's points join the local map for the NEXT frames (ring slice (i - 1) % 2 <- frame i - 1)
-        TRK_CHECK(sgx_frame_make_map_points_batch_dev(S, cap, (i - 1) % 2, t->keys[l], t->n[l], t->xw[l], t->has[l], t->desc[l], Tl, t->scale, t->nlevels, t->lm_xw, t->lm_normal, t->lm_min,
+        TRK_CHECK(sgx_frame_make_map_points_batch_dev(S, cap, (i - 1) % 2, ku_l, t->n[l], t->xw[l], t->has[l], t->desc[l], Tl, t->scale, t->nlevels, t->lm_xw, t->lm_normal, t->lm_min,
                                                       t->lm_max, t->lm_desc, t->lm_skip, sT));
     if (t->pipelined) ev_record(t->ev_track[c], sT);
     else { t->last_stream = (sgx_st)caller_stream; ev_record(t->ev_step, t->last_stream); }
@@ -415,6 +443,13 @@ extern "C" int sgx_tracker_frame_dev(sgx_tracker *t, const int32_t **d_n, const 
     if (!t || t->frame_idx < 1) return SGX_ERR_INVALID;
     const int c = t->cur;
     if (d_n) *d_n = t->n[c]; if (d_keys) *d_keys = t->keys[c]; if (d_desc) *d_desc = t->desc[c]; if (d_Tcw) *d_Tcw = t->Tcw[1]; if (d_xw) *d_xw = t->xw[c]; if (d_has) *d_has = t->has[c];
+    return SGX_OK;
+}
+
+extern "C" int sgx_tracker_frame_keys_un_dev(sgx_tracker *t, const sgx_keypoint **d_keys_un)
+{
+    if (!t || !d_keys_un || t->frame_idx < 1) return SGX_ERR_INVALID;
+    *d_keys_un = t->undistort ? t->keys_un[t->cur] : t->keys[t->cur];
     return SGX_OK;
 }
 

@@ -47,3 +47,36 @@ def gray_from_color_batch(lib, batch, width, height, d_src, src_pitch, channels,
     """cvtColor(..., CV_{RGB,BGR,RGBA,BGRA}2GRAY) of Tracking::GrabImageRGBD (Tracking.cc:214-227) on device images."""
     lib.check(lib.dll.sgx_frame_gray_from_color_batch_dev(batch, width, height, _vp(d_src), src_pitch, channels, 1 if blue_first else 0, _vp(d_gray), gray_pitch, _vp(stream)),
               'sgx_frame_gray_from_color_batch_dev')
+
+
+def _dist_array(dist):
+    import numpy as np
+    return np.ascontiguousarray(dist, 'f4').reshape(-1)
+
+
+def undistort_points(lib, pts, cam, dist):
+    """cv::undistortPoints(pts, out, K, D, noArray(), K) as Frame::UndistortKeyPoints calls it (Frame.cc:654-684): (n, 2) float32 points in, the same out.
+    dist: 4, 5 or 8 coefficients (k1, k2, p1, p2 [, k3 [, k4, k5, k6]]).  Computed on the device, synchronous."""
+    import numpy as np
+    p = np.ascontiguousarray(pts, 'f4').reshape(-1, 2)
+    out = np.zeros_like(p)
+    K4 = np.array([cam['fx'], cam['fy'], cam['cx'], cam['cy']], 'f4'); d = _dist_array(dist)
+    lib.check(lib.dll.sgx_undistort_points(len(p), _vp(p), _vp(K4), _vp(d), len(d), _vp(out)), 'sgx_undistort_points')
+    return out
+
+
+def undistort_stereo_rgbd_batch_dev(lib, batch, cap, d_keys, d_n, dist, cam, d_depth_u16, width, height, d_keys_un, d_uright, d_zdepth, stream=None):
+    """Frame::UndistortKeyPoints fused with Frame::ComputeStereoFromRGBD (Frame.cc:654-684, :893-914) on device frames; cam carries fx..cy, bf, depth_factor."""
+    cs = camera_struct(cam, width, height); d = _dist_array(dist)
+    lib.check(lib.dll.sgx_frame_undistort_stereo_rgbd_batch_dev(batch, cap, _vp(d_keys), _vp(d_n), _vp(d), len(d), C.byref(cs), _vp(d_depth_u16), width, height,
+                                                                float(cam['depth_factor']), _vp(d_keys_un), _vp(d_uright), _vp(d_zdepth), _vp(stream)),
+              'sgx_frame_undistort_stereo_rgbd_batch_dev')
+
+
+def image_bounds(lib, width, height, cam, dist):
+    """Frame::ComputeImageBounds (Frame.cc:686-714): dict(min_x, max_x, min_y, max_y) as float32 values"""
+    import numpy as np
+    K4 = np.array([cam['fx'], cam['fy'], cam['cx'], cam['cy']], 'f4'); d = _dist_array(dist)
+    cs = camera_struct(cam, width, height)
+    lib.check(lib.dll.sgx_frame_image_bounds(int(width), int(height), _vp(K4), _vp(d), len(d), C.byref(cs)), 'sgx_frame_image_bounds')
+    return dict(min_x=cs.min_x, max_x=cs.max_x, min_y=cs.min_y, max_y=cs.max_y)

@@ -484,6 +484,19 @@ public:
     sgx_det *handle() { return h_; }
 };
 
+// cv::undistortPoints(points, out, K, D, noArray(), K) as Frame::UndistortKeyPoints calls it (Frame.cc:654-684), and Frame::ComputeImageBounds (:686-714);
+// K4 = fx, fy, cx, cy, distCoef = 4, 5 or 8 coefficients.  Points are (x, y) pairs.
+inline std::vector<float> UndistortPoints(const std::vector<float> &points, const float K4[4], const std::vector<float> &distCoef)
+{
+    std::vector<float> out(points.size());
+    check(sgx_undistort_points((int)(points.size() / 2), points.data(), K4, distCoef.data(), (int)distCoef.size(), out.data()), "sgx_undistort_points");
+    return out;
+}
+inline void ComputeImageBounds(int cols, int rows, const float K4[4], const std::vector<float> &distCoef, sgx_camera &cam)
+{
+    check(sgx_frame_image_bounds(cols, rows, K4, distCoef.data(), (int)distCoef.size(), &cam), "sgx_frame_image_bounds");
+}
+
 // The pipelined per-frame host (sgx_tracker_*): S RGB-D streams tracked in lock-step with Tracking::GrabImageRGBD's call order (src/sg-slam/src/Tracking.cc:206-251,
 // :906-1013) on three event-chained HIP streams inside the library.  GrabImagesRGBD(slot) = one frame of every stream from the pinned staging buffers of `slot`
 // (imRGB as cv::imread delivers it — interleaved 8-bit BGR — and the raw 16-bit depth map, rgbd_tum.cc:114-115), asynchronous; Pose() synchronises.
@@ -502,6 +515,14 @@ public:
     TrackingPipeline(const TrackingPipeline &) = delete;
     TrackingPipeline &operator=(const TrackingPipeline &) = delete;
     void SetInitialPose(const std::vector<float> &Tcw) { if ((int)Tcw.size() != 16 * S_) throw std::invalid_argument("SetInitialPose: streams x 16 floats"); check(sgx_tracker_set_initial_pose(h_, Tcw.data()), "sgx_tracker_set_initial_pose"); }
+    // mDistCoef (Tracking.cc:66-77: k1, k2, p1, p2 [, k3]), before the first frame: Frame::UndistortKeyPoints / ComputeImageBounds from then on (k1 == 0: nothing changes).
+    // Returns the camera with the grid / frustum bounds the pipeline uses (mnMinX, mnMaxX, mnMinY, mnMaxY).
+    sgx_camera SetDistortion(const std::vector<float> &distCoef)
+    {
+        sgx_camera cam; std::memset(&cam, 0, sizeof cam);
+        check(sgx_tracker_set_distortion(h_, distCoef.data(), (int)distCoef.size(), &cam), "sgx_tracker_set_distortion");
+        return cam;
+    }
     // staging buffers of slot 0 / 1: bgr = streams x height rows of `pitch` bytes (3 * width used), depth = streams x height x width uint16
     void HostBuffers(int slot, uint8_t **bgr, int *pitch, uint16_t **depth) { check(sgx_tracker_host_buffers(h_, slot, bgr, pitch, depth), "sgx_tracker_host_buffers"); }
     void GrabImagesRGBD(int slot, bool rgbOrder = true) { check(sgx_tracker_step_host(h_, slot, rgbOrder ? 1 : 0), "sgx_tracker_step_host"); }

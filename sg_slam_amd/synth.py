@@ -163,6 +163,69 @@ class DynamicStream(LayeredStream):
         return gray, depth, T
 
 
+def distort_normalized(x, y, dist):
+    """OpenCV's forward lens model on normalised coordinates (float64): k1, k2, p1, p2 [, k3 [, k4, k5, k6]]"""
+    k = np.zeros(8); d = np.asarray(dist, 'f8').reshape(-1); k[:len(d)] = d
+    r2 = x * x + y * y
+    radial = (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2) / (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2)
+    return (x * radial + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x), y * radial + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y)
+
+
+class _DistortedRender:
+    """Renders a stream through a lens: the distorted pixel (u, v) shows what the pinhole camera sees at its undistorted position.  The inverse of the
+    lens model is computed once per pixel in float64 by fixed-point iteration run to convergence (not OpenCV's five steps); poses and scene are the
+    base stream's."""
+
+    def _init_lens(self, dist):
+        self.dist = np.asarray(dist, 'f4').reshape(-1)
+        cam = self.cam
+        fx, fy, cx, cy = (float(np.float32(cam[c])) for c in ('fx', 'fy', 'cx', 'cy'))
+        u = np.arange(self.w, dtype='f8')[None, :].repeat(self.h, 0); v = np.arange(self.h, dtype='f8')[:, None].repeat(self.w, 1)
+        xd = (u - cx) / fx; yd = (v - cy) / fy
+        x, y = xd.copy(), yd.copy()
+        for _ in range(500):
+            px, py = distort_normalized(x, y, self.dist)
+            ex, ey = px - xd, py - yd
+            x, y = x - ex, y - ey
+            if max(np.abs(ex).max(), np.abs(ey).max()) < 1e-14:
+                break
+        px, py = distort_normalized(x, y, self.dist)
+        self.lens_residual_px = float(max(np.abs(px - xd).max() * fx, np.abs(py - yd).max() * fy))
+        assert self.lens_residual_px < 1e-6, 'lens inverse did not converge'
+        self._uu = x * fx + cx; self._vu = y * fy + cy                 # undistorted pixel of every distorted pixel
+
+    def _warp_coords(self, t, z):
+        """Q16 texel coordinates of the base stream's warp (PlaneStream._warp_coords) evaluated at the undistorted position of every pixel"""
+        cam, z0, ts = self.cam, self.z0, self.ts
+        fx, fy, cx, cy = cam['fx'], cam['fy'], cam['cx'], cam['cy']
+        cxm, cym, th = self.pose(t)
+        c, s = math.cos(th), math.sin(th)
+        Q = 1 << 16
+        k = z / z0
+        a00 = int(round(k * c * Q)); a01 = int(round(k * s * (fx / fy) * Q))
+        a10 = int(round(-k * s * (fy / fx) * Q)); a11 = int(round(k * c * Q))
+        b0 = int(round((ts / 2 + fx / z0 * cxm - k * (c * cx + s * (fx / fy) * cy)) * Q))
+        b1 = int(round((ts / 2 + fy / z0 * cym + k * (s * (fy / fx) * cx - c * cy)) * Q))
+        u, v = self._uu, self._vu
+        return np.floor(a00 * u + a01 * v + b0 + 0.5).astype(np.int64), np.floor(a10 * u + a11 * v + b1 + 0.5).astype(np.int64)
+
+
+class DistortedPlaneStream(_DistortedRender, PlaneStream):
+    """PlaneStream seen through a lens with distortion coefficients `dist` (e.g. TUM1.yaml's); same ground-truth poses."""
+
+    def __init__(self, dist, seed=1234, **kw):
+        PlaneStream.__init__(self, seed=seed, **kw)
+        self._init_lens(dist)
+
+
+class DistortedLayeredStream(_DistortedRender, LayeredStream):
+    """LayeredStream seen through a lens with distortion coefficients `dist`; the depth image is registered to the distorted colour image."""
+
+    def __init__(self, dist, seed=1234, **kw):
+        LayeredStream.__init__(self, seed=seed, **kw)
+        self._init_lens(dist)
+
+
 def _texel_map(stream, t):
     """3x3 homogeneous map pixel (u, v) of frame t -> texel of the world texture (the float form of PlaneStream.frame's Q16 warp)."""
     cam, z0, ts = stream.cam, stream.z0, stream.ts

@@ -6,6 +6,8 @@ step, every stage device-resident and asynchronous on one HIP stream:
                                        findFundamentalMat, :454-472) + wait for the detector (:478-500) + sgx_dynamic_mask_batch_dev +
                                        sgx_frame_compact_keys_batch_dev (:556-604)          [lk=True; with lk=False the LK / F inputs are given by the caller]
   Frame::ComputeStereoFromRGBD      -> sgx_frame_stereo_from_rgbd_batch_dev (Frame.cc:893-914)
+                                       [dist with k1 != 0: Frame::UndistortKeyPoints + ComputeStereoFromRGBD -> sgx_frame_undistort_stereo_rgbd_batch_dev
+                                       (Frame.cc:654-684), the bounds of Frame::ComputeImageBounds (:686-714), and mvKeysUn in every stage below]
   constant-velocity prediction      -> sgx_frame_motion_model_batch_dev     (Tracking.cc:463-470, :914)
   ORBmatcher::SearchByProjection    -> sgx_match_project_frame_batch_dev    (ORBmatcher.cc:1332-1472, th=15)
   Optimizer::PoseOptimization       -> sgx_pose_optimization_batch_dev      (Optimizer.cc:239-451)
@@ -26,15 +28,20 @@ from .capi import _vp
 from .matcher import camera_struct
 from .orb import ORBextractor
 from .flow import OpticalFlowLK, fundamental_ransac_batch_dev
+from .frame import image_bounds
 
 
 class TrackerBatch:
     stream_priorities = (0, 0)      # (extraction, tracking) HIP stream priorities; see __init__
-    def __init__(self, lib, streams, cam, width=640, height=480, nfeatures=1000, xp='torch', th=15.0, pipelined=True, local_map=True, debug_taps=False, lk=False, max_boxes=8):
+    def __init__(self, lib, streams, cam, width=640, height=480, nfeatures=1000, xp='torch', th=15.0, pipelined=True, local_map=True, debug_taps=False, lk=False, max_boxes=8, dist=None):
         self.lib, self.S, self.cam, self.W, self.H, self.th = lib, streams, dict(cam), width, height, th
+        # mDistCoef (Tracking.cc:66-77): with k1 == 0 the reference skips UndistortKeyPoints and ComputeImageBounds (Frame.cc:656-660, :707-713), and so does this
+        self.dist = None if dist is None or np.float32(np.asarray(dist, 'f4').reshape(-1)[0]) == 0 else np.ascontiguousarray(dist, 'f4').reshape(-1)
+        if self.dist is not None:
+            self.cam.update(image_bounds(lib, width, height, self.cam, self.dist))
         self.ex = ORBextractor(nfeatures=nfeatures, width=width, height=height, max_batch=streams, lib=lib)
         self.cap = self.ex.capacity
-        self.cs = camera_struct(cam, width, height)
+        self.cs = camera_struct(self.cam, width, height)
         self.scale = np.ascontiguousarray(self.ex.mvScaleFactor, 'f4')
         self.inv_sigma2 = np.ascontiguousarray(self.ex.mvInvLevelSigma2, 'f4')
         self.xp = xp
@@ -43,6 +50,7 @@ class TrackerBatch:
         # triple-buffered per-frame state: frame t lives in slot t % 3 (current / last / being overwritten by the next extract)
         NB = 3
         self.keys = [z((S, cap, 28), 'u1') for _ in range(NB)]
+        self.keys_un = self.keys if self.dist is None else [z((S, cap, 28), 'u1') for _ in range(NB)]       # mvKeysUn (the same buffers without distortion)
         self.desc = [z((S, cap, 32), 'u1') for _ in range(NB)]
         self.n = [z((S,), 'i4') for _ in range(NB)]
         self.uright = [z((S, cap), 'f4') for _ in range(NB)]
@@ -188,8 +196,14 @@ class TrackerBatch:
                                                      self.max_boxes, _vp(self.keep), _vp(stE)), 'dynamic mask')
             L.check(L.dll.sgx_frame_compact_keys_batch_dev(S, cap, _vp(self.rkeys), _vp(self.rdesc), _vp(self.rn), _vp(self.keep), _vp(mask.get('have_dynamic')),
                                                            self.nfeatures, _vp(self.keys[c]), _vp(self.desc[c]), _vp(self.n[c]), _vp(stE)), 'compact keys')
-        L.check(L.dll.sgx_frame_stereo_from_rgbd_batch_dev(S, cap, _vp(self.keys[c]), _vp(self.n[c]), _vp(d_depth), self.W, self.H,
-                                                           float(cam['depth_factor']), float(cam['bf']), _vp(self.uright[c]), _vp(self.zdepth[c]), _vp(stE)), 'stereo')
+        if self.dist is None:
+            L.check(L.dll.sgx_frame_stereo_from_rgbd_batch_dev(S, cap, _vp(self.keys[c]), _vp(self.n[c]), _vp(d_depth), self.W, self.H,
+                                                               float(cam['depth_factor']), float(cam['bf']), _vp(self.uright[c]), _vp(self.zdepth[c]), _vp(stE)), 'stereo')
+        else:
+            L.check(L.dll.sgx_frame_undistort_stereo_rgbd_batch_dev(S, cap, _vp(self.keys[c]), _vp(self.n[c]), _vp(self.dist), len(self.dist), C.byref(self.cs), _vp(d_depth),
+                                                                     self.W, self.H, float(cam['depth_factor']), _vp(self.keys_un[c]), _vp(self.uright[c]),
+                                                                     _vp(self.zdepth[c]), _vp(stE)), 'undistort + stereo')
+        ku = self.keys_un
         if self.pipelined:
             self.ev_extract[c].record(self.sE)
             self.sT.wait_event(self.ev_extract[c])
@@ -198,11 +212,11 @@ class TrackerBatch:
             # Tc <- predicted pose from (Tl, Tll); frame 1 has no velocity yet -> uses the last pose
             L.check(L.dll.sgx_frame_motion_model_batch_dev(S, _vp(Tl), _vp(Tll), _vp(self.vel_valid), _vp(Tc), st), 'motion model')
             L.check(L.dll.sgx_match_project_frame_batch_dev(
-                S, cap, _vp(self.keys[c]), _vp(self.desc[c]), _vp(self.uright[c]), _vp(self.n[c]), _vp(Tc),
-                _vp(self.keys[l]), _vp(self.n[l]), _vp(self.has[l]), _vp(self.zero_u8), _vp(self.xw[l]), _vp(self.zero_i4), _vp(self.desc[l]), _vp(Tl),
+                S, cap, _vp(ku[c]), _vp(self.desc[c]), _vp(self.uright[c]), _vp(self.n[c]), _vp(Tc),
+                _vp(ku[l]), _vp(self.n[l]), _vp(self.has[l]), _vp(self.zero_u8), _vp(self.xw[l]), _vp(self.zero_i4), _vp(self.desc[l]), _vp(Tl),
                 C.byref(self.cs), _vp(self.scale), len(self.scale), float(self.th), 0, 1, _vp(self.match), _vp(self.nmatch), st), 'match')
             L.check(L.dll.sgx_pose_optimization_batch_dev(
-                S, cap, _vp(self.keys[c]), _vp(self.uright[c]), _vp(self.n[c]), _vp(self.match), None, _vp(self.xw[l]), cap,
+                S, cap, _vp(ku[c]), _vp(self.uright[c]), _vp(self.n[c]), _vp(self.match), None, _vp(self.xw[l]), cap,
                 _vp(self.inv_sigma2), len(self.inv_sigma2), C.byref(self.cs), _vp(Tc), _vp(self.outlier), _vp(self.ninl), st), 'pose opt')
             if t == 1:
                 if self.pipelined:
@@ -223,19 +237,19 @@ class TrackerBatch:
             L.check(L.dll.sgx_frame_merge_matches_batch_dev(S, cap, _vp(self.n[c]), _vp(self.match), _vp(self.outlier), None, None, None,
                                                             None, _vp(self.cur_mp_obs), None, st), 'mp_obs')
             L.check(L.dll.sgx_match_project_local_batch_dev(
-                S, cap, _vp(self.keys[c]), _vp(self.desc[c]), _vp(self.uright[c]), _vp(self.n[c]), _vp(Tc), _vp(self.cur_mp_obs),
+                S, cap, _vp(ku[c]), _vp(self.desc[c]), _vp(self.uright[c]), _vp(self.n[c]), _vp(Tc), _vp(self.cur_mp_obs),
                 2 * cap, _vp(self.lm_n), _vp(self.lm_xw), _vp(self.lm_normal), _vp(self.lm_min), _vp(self.lm_max), _vp(self.lm_desc), _vp(self.lm_obs), _vp(self.lm_skip),
                 C.byref(self.cs), _vp(self.scale), len(self.scale), self.log_scale, 3.0, 0.8, 0.5, _vp(self.match_local), _vp(self.nmatch_local), _vp(self.in_view), st), 'match local')
             L.check(L.dll.sgx_frame_merge_matches_batch_dev(S, cap, _vp(self.n[c]), _vp(self.match), _vp(self.outlier), _vp(self.match_local),
                                                             _vp(self.xw[l]), _vp(self.lm_xw), _vp(self.merged), None, _vp(self.xw_all), st), 'merge')
             L.check(L.dll.sgx_pose_optimization_batch_dev(
-                S, cap, _vp(self.keys[c]), _vp(self.uright[c]), _vp(self.n[c]), _vp(self.merged), None, _vp(self.xw_all), 3 * cap,
+                S, cap, _vp(ku[c]), _vp(self.uright[c]), _vp(self.n[c]), _vp(self.merged), None, _vp(self.xw_all), 3 * cap,
                 _vp(self.inv_sigma2), len(self.inv_sigma2), C.byref(self.cs), _vp(Tc), _vp(self.outlier2), _vp(self.ninl2), st), 'pose opt 2')
-        L.check(L.dll.sgx_frame_unproject_batch_dev(S, cap, _vp(self.keys[c]), _vp(self.n[c]), _vp(self.zdepth[c]), _vp(Tc), C.byref(self.cs),
+        L.check(L.dll.sgx_frame_unproject_batch_dev(S, cap, _vp(ku[c]), _vp(self.n[c]), _vp(self.zdepth[c]), _vp(Tc), C.byref(self.cs),
                                                     _vp(self.xw[c]), _vp(self.has[c]), st), 'unproject')
         if t > 0 and self.local_map:
             # the last frame's points join the local map for the NEXT frames (ring slice (t-1) % 2 <- frame t-1, i.e. at step t+1 the ring holds t-1 and t-2)
-            L.check(L.dll.sgx_frame_make_map_points_batch_dev(S, cap, (t - 1) % 2, _vp(self.keys[l]), _vp(self.n[l]), _vp(self.xw[l]), _vp(self.has[l]), _vp(self.desc[l]),
+            L.check(L.dll.sgx_frame_make_map_points_batch_dev(S, cap, (t - 1) % 2, _vp(ku[l]), _vp(self.n[l]), _vp(self.xw[l]), _vp(self.has[l]), _vp(self.desc[l]),
                                                               _vp(Tl), _vp(self.scale), len(self.scale), _vp(self.lm_xw), _vp(self.lm_normal), _vp(self.lm_min),
                                                               _vp(self.lm_max), _vp(self.lm_desc), _vp(self.lm_skip), st), 'make map points')
         if self.pipelined:

@@ -8,7 +8,7 @@ from .matcher import camera_struct
 
 
 class TrackerNative:
-    def __init__(self, lib, streams, cam, width=640, height=480, nfeatures=1000, th=15.0, pipelined=True, local_map=True, dynamic_mask=True, max_boxes=8, detector=None):
+    def __init__(self, lib, streams, cam, width=640, height=480, nfeatures=1000, th=15.0, pipelined=True, local_map=True, dynamic_mask=True, max_boxes=8, detector=None, dist=None):
         self.lib, self.S, self.W, self.H = lib, int(streams), int(width), int(height)
         cfg = TrackerConfig()
         cfg.streams, cfg.width, cfg.height = self.S, width, height
@@ -23,6 +23,12 @@ class TrackerNative:
         self.rec_bytes = lib.dll.sgx_tracker_record_bytes(h)
         self.max_boxes = int(max_boxes)
         self.frame_idx = 0
+        # mDistCoef (Tracking.cc:66-77; 4, 5 or 8 coefficients): the grid / frustum bounds the library derived from it (Frame::ComputeImageBounds) are kept in `bounds`
+        out = camera_struct(cam, width, height)
+        if dist is not None:
+            d = np.ascontiguousarray(dist, 'f4').reshape(-1)
+            lib.check(lib.dll.sgx_tracker_set_distortion(h, _vp(d), len(d), C.byref(out)), 'sgx_tracker_set_distortion')
+        self.bounds = dict(min_x=out.min_x, max_x=out.max_x, min_y=out.min_y, max_y=out.max_y)
 
     def close(self):
         if getattr(self, 'h', None):
@@ -84,6 +90,12 @@ class TrackerNative:
         p = [C.c_void_p() for _ in range(6)]
         self.lib.check(self.lib.dll.sgx_tracker_frame_dev(self.h, *[C.byref(x) for x in p]))
         return dict(zip(('n', 'keys', 'desc', 'Tcw', 'xw', 'has'), [x.value for x in p]))
+
+    def frame_keys_un_dev(self):
+        """device pointer (int) of the undistorted keypoints (mvKeysUn) of the frame tracked last; the `keys` of frame_dev() without distortion"""
+        p = C.c_void_p()
+        self.lib.check(self.lib.dll.sgx_tracker_frame_keys_un_dev(self.h, C.byref(p)))
+        return p.value
 
     def last_status(self, stream=None):
         self.lib.check(self.lib.dll.sgx_orb_last_status(self.lib.dll.sgx_tracker_extractor(self.h), None if stream is None else C.c_void_p(stream)))
