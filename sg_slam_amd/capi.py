@@ -81,7 +81,8 @@ SYMBOLS = [
     'sgx_match_search_for_initialization', 'sgx_voc_load', 'sgx_voc_create', 'sgx_voc_info', 'sgx_voc_destroy', 'sgx_voc_transform',
     'sgx_voc_transform_batch_dev', 'sgx_voc_score', 'sgx_match_project_sim3', 'sgx_match_search_by_sim3', 'sgx_optimize_sim3',
     'sgx_optimize_essential_graph', 'sgx_correct_map_points', 'sgx_undistort_points', 'sgx_frame_undistort_stereo_rgbd_batch_dev', 'sgx_frame_image_bounds',
-    'sgx_tracker_set_distortion', 'sgx_tracker_frame_keys_un_dev',
+    'sgx_tracker_set_distortion', 'sgx_tracker_frame_keys_un_dev', 'sgx_pnp_solver_create', 'sgx_pnp_solver_set_ransac_parameters', 'sgx_pnp_solver_iterate',
+    'sgx_pnp_solver_get_estimate', 'sgx_pnp_solver_destroy', 'sgx_pnp_batch_create', 'sgx_pnp_batch_set_dev', 'sgx_pnp_batch_iterate_dev', 'sgx_pnp_batch_destroy',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -89,7 +90,7 @@ TAP_SYMBOLS = [
     'sgx_orb_debug_run_octree', 'sgx_pose_opt_debug_set_threads', 'sgx_ba_debug_set_solver', 'sgx_ba_debug_set_jobs', 'sgx_ba_debug_set_init', 'sgx_ba_debug_last_plan', 'sgx_det_debug_read_blob',
     'sgx_det_debug_detection_output', 'sgx_debug_flow_affine_batch_dev', 'sgx_det_debug_set_fusion', 'sgx_det_debug_set_legacy_kernels',
     'sgx_det_debug_set_block_fusion', 'sgx_det_debug_set_irb', 'sgx_det_debug_set_gemm', 'sgx_det_debug_time_ops', 'sgx_det_debug_run_step', 'sgx_flow_debug_read_level',
-    'sgx_flow_debug_level_size', 'sgx_debug_corun_bf16',
+    'sgx_flow_debug_level_size', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas',
 ]
 
 
@@ -201,6 +202,15 @@ class SgxLib:
         d.sgx_sim3_solver_iterate.argtypes = [vp, C.c_int] + [vp] * 7
         d.sgx_sim3_solver_get_estimate.argtypes = [vp] * 5
         d.sgx_sim3_solver_destroy.argtypes = [vp]; d.sgx_sim3_solver_destroy.restype = None
+        d.sgx_pnp_solver_create.argtypes = [C.c_int] + [vp] * 4 + [C.c_uint, vp]
+        d.sgx_pnp_solver_set_ransac_parameters.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
+        d.sgx_pnp_solver_iterate.argtypes = [vp, C.c_int] + [vp] * 7
+        d.sgx_pnp_solver_get_estimate.argtypes = [vp] * 6
+        d.sgx_pnp_solver_destroy.argtypes = [vp]; d.sgx_pnp_solver_destroy.restype = None
+        d.sgx_pnp_batch_create.argtypes = [C.c_int, C.c_int, vp]
+        d.sgx_pnp_batch_set_dev.argtypes = [vp, C.c_int] + [vp] * 8
+        d.sgx_pnp_batch_iterate_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+        d.sgx_pnp_batch_destroy.argtypes = [vp]; d.sgx_pnp_batch_destroy.restype = None
         d.sgx_mappoint_update_normal_and_depth.argtypes = [C.c_int] + [vp] * 6 + [C.c_int, vp, vp, vp]
         d.sgx_mappoint_distinctive_descriptors.argtypes = [C.c_int, vp, vp, vp, vp]
         d.sgx_triangulate_new_map_points.argtypes = [C.c_int, vp] + [C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 5 + [vp, vp, vp, C.c_int, vp, vp, vp]
@@ -238,6 +248,7 @@ class SgxLib:
             d.sgx_debug_flow_affine_batch_dev.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp]
             d.sgx_flow_debug_read_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
             d.sgx_debug_corun_bf16.argtypes = [C.c_int, C.c_int, C.c_int, vp]
+            d.sgx_pnp_debug_betas.argtypes = [C.c_int, vp, vp, vp]
             d.sgx_flow_debug_level_size.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
 
     def tap(self, name):

@@ -319,6 +319,38 @@ private:
     sgx_sim3_solver *h_ = nullptr; std::vector<int32_t> idx1_; int N1_, n_;
 };
 
+// PnPsolver (src/sg-slam/src/PnPsolver.cc), the EPnP RANSAC of Tracking::Relocalization (Tracking.cc:1504-1530), on the device
+class PnPsolver {
+public:
+    // the constructor's flattening (:78-101): p2d = mvKeysUn[i].pt (n x 2), sigma2 = mvLevelSigma2[octave], p3dw = GetWorldPos() (n x 3), keyPointIndices[k] = i
+    // (mvKeyPointIndices), N = vpMapPointMatches.size(); cam = fx, fy, cx, cy.  Ends with SetRansacParameters() and its defaults, as the reference does.
+    PnPsolver(const std::vector<float> &p2d, const std::vector<float> &sigma2, const std::vector<float> &p3dw, const float cam[4], const std::vector<int32_t> &keyPointIndices,
+              int N, unsigned randSeed = 0) : idx_(keyPointIndices), N_(N), n_((int)sigma2.size())
+    { check(sgx_pnp_solver_create(n_, p2d.data(), sigma2.data(), p3dw.data(), cam, randSeed, &h_), "sgx_pnp_solver_create"); }
+    ~PnPsolver() { if (h_) sgx_pnp_solver_destroy(h_); }
+    PnPsolver(const PnPsolver &) = delete; PnPsolver &operator=(const PnPsolver &) = delete;
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4f, float th2 = 5.991f)
+    { check(sgx_pnp_solver_set_ransac_parameters(h_, probability, minInliers, maxIterations, minSet, epsilon, th2), "sgx_pnp_solver_set_ransac_parameters"); }
+    // cv::Mat iterate(int nIterations, bool &bNoMore, vector<bool> &vbInliers, int &nInliers): returns true and fills Tcw (4x4 row-major) when a model is returned.
+    // randDraws (optional): 4 raw rand() values per hypothesis of the call; otherwise the solver's glibc-compatible replica is used.
+    bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, float Tcw[16], const std::vector<int32_t> *randDraws = nullptr)
+    {
+        std::vector<uint8_t> inl((size_t)(n_ > 0 ? n_ : 1), 0); int32_t nm = 0, ni = 0, fnd = 0;
+        check(sgx_pnp_solver_iterate(h_, nIterations, randDraws ? randDraws->data() : nullptr, Tcw, &nm, inl.data(), &ni, &fnd, nullptr), "sgx_pnp_solver_iterate");
+        bNoMore = nm != 0; nInliers = ni; vbInliers.assign((size_t)N_, false);
+        if (fnd) for (int i = 0; i < n_; i++) if (inl[(size_t)i]) vbInliers[(size_t)idx_[(size_t)i]] = true;            // vbInliers[mvKeyPointIndices[i]] = true (:229-234)
+        return fnd != 0;
+    }
+    // cv::Mat find(vector<bool> &vbInliers, int &nInliers) (:159-163)
+    bool find(std::vector<bool> &vbInliers, int &nInliers, float Tcw[16])
+    {
+        int32_t maxIts = 0; check(sgx_pnp_solver_get_estimate(h_, nullptr, &maxIts, nullptr, nullptr, nullptr), "sgx_pnp_solver_get_estimate");
+        bool bFlag = false; return iterate(maxIts, bFlag, vbInliers, nInliers, Tcw);
+    }
+private:
+    sgx_pnp_solver *h_ = nullptr; std::vector<int32_t> idx_; int N_, n_;
+};
+
 // ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (src/sg-slam/include/ORBVocabulary.h:31-32): the members the reference calls
 class ORBVocabulary {
 public:
