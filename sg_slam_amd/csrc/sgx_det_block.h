@@ -673,10 +673,11 @@ SGX_KERNEL(256) k_se_gate(int HW, int total, const float *__restrict__ y, size_t
     SGX_THREADS_END
 }
 static inline bool sgx_se_gate_supported(int cout, int cq) { return cout == 40 && cq == 10; }
-static inline int sgx_se_gate_launch(const SgxSeGate &p, int batch, sgx_stream_t st)
+// prepare = true only reports whether the shape has an instantiation (sgx_det_create), prepare = false launches it
+static inline int sgx_se_gate_dispatch(const SgxSeGate &p, int batch, sgx_stream_t st, bool prepare)
 {
     const int total = batch * p.HW;
-    if (p.Cout == 40 && p.Cq == 10) { auto kfn = k_se_gate<40, 10>; SGX_LAUNCH(kfn, dim3((unsigned)((total + 255) / 256)), dim3(256), st, p.HW, total, p.y, p.y_pitch, p.out, p.out_pitch, p.res, p.res_pitch, p.se); return SGX_OK; }
+    if (p.Cout == 40 && p.Cq == 10) { if (prepare) return SGX_OK; auto kfn = k_se_gate<40, 10>; SGX_LAUNCH(kfn, dim3((unsigned)((total + 255) / 256)), dim3(256), st, p.HW, total, p.y, p.y_pitch, p.out, p.out_pitch, p.res, p.res_pitch, p.se); return SGX_OK; }
     return SGX_ERR_INVALID;
 }
 
@@ -785,8 +786,7 @@ static inline bool sgx_dw3_plan(int C, int H, int W, int Ho, int Wo, int k, int 
     *px = (stride == 1 && Wo >= 16) ? 2 : 1;
     p->C = C; p->H = H; p->W = W; p->Ho = Ho; p->Wo = Wo; p->pad = pad; p->NP = NP; p->HP = HP; p->WP = WP; p->nchunks = (C / 2 + NP - 1) / NP;
     p->WU = (Wo + *px - 1) / *px; p->NU = Ho * p->WU;
-    { auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); };
-      p->m_wu = magic(p->WU); p->m_wp = magic(WP); p->m_cells = (HP * WP < 4096 && NP * HP * WP < (1 << 20)) ? magic(HP * WP) : 0u; }
+    p->m_wu = sgx_magic(p->WU); p->m_wp = sgx_magic(WP); p->m_cells = (HP * WP < 4096 && NP * HP * WP < (1 << 20)) ? sgx_magic(HP * WP) : 0u;
     *lds = (size_t)NP * per_pair;
     return true;
 }
@@ -803,9 +803,9 @@ static inline void sgx_dw3_launch(const SgxDw3 &p, int k, int stride, int px, si
 
 #endif
 
-// ---- k_fused_block2 dispatch: (Cin, Cout, K, stride) -> instantiation; the tile variant comes from SGX_FB2_TILE (tuning tap) --------------------------------------
+// ---- k_fused_block2 dispatch: (Cin, Cout, K, stride) -> instantiation; tile_sel >= 0 (SGX_FB2_TILE, tuning tap) forces the tile variant --------------------------------------
 static inline int sgx_fb2_cm(int v2) { return (v2 >> 4) == 1 ? 16 : 8; }       /* expanded channels per chunk of the instantiation (Cmid must be a multiple) */
-static inline int sgx_fb2_variant(int cin, int cout, int k, int stride, int cq = 0)
+static inline int sgx_fb2_variant(int cin, int cout, int k, int stride, int cq, int tile_sel)
 {
     if (cq) {                                                                   // block with a squeeze-excite tail: 24 -> 72 -> 40 (5 x 5, stride 2, 75 -> 38): 0.86 -> 0.75 ms per 512 frames.
         // The two 40 -> 120 -> 40 blocks at 38 x 38 were measured too (8 x 16 tiles): 0.67 ms against 0.61 for the five per-layer kernels — 40 input channels leave one pixel
@@ -813,13 +813,12 @@ static inline int sgx_fb2_variant(int cin, int cout, int k, int stride, int cq =
         if (cin == 24 && cout == 40 && k == 5 && stride == 2 && cq == 10) return 4 * 16;
         return 0;
     }
-    static const int tile_env = sgx_getenv("SGX_FB2_TILE") ? atoi(sgx_getenv("SGX_FB2_TILE")) : -1;          // tuning tap: force 8 x 16 (0) or 16 x 16 (1) output tiles on the stride-1 blocks
     int shape = 0;
     if (cin == 16 && cout == 16 && k == 3 && stride == 1) shape = 1;
     else if (cin == 16 && cout == 24 && k == 3 && stride == 2) shape = 2;
     else if (cin == 24 && cout == 24 && k == 3 && stride == 1) shape = 3;
     if (!shape) return 0;
-    const int tile = tile_env >= 0 ? tile_env : (shape == 1 ? 1 : 0);           // measured at 512 frames: 16 -> 16 -> 16 at 150 x 150 is best with 16 x 16 tiles (0.76 ms against 0.79), 24 -> 72 -> 24 with 8 x 16 (0.61 against 0.68)
+    const int tile = tile_sel >= 0 ? tile_sel : (shape == 1 ? 1 : 0);      // tile_sel: force 8 x 16 (0) or 16 x 16 (1) output tiles on the stride-1 blocks;           // measured at 512 frames: 16 -> 16 -> 16 at 150 x 150 is best with 16 x 16 tiles (0.76 ms against 0.79), 24 -> 72 -> 24 with 8 x 16 (0.61 against 0.68)
     return shape * 16 + ((shape == 2) ? 0 : (tile & 1));                       // stride 1: tile 0 = 8 x 16, tile 1 = 16 x 16; stride 2: 8 x 16 only (input pixels live in registers)
 }
 static inline void sgx_fb2_tile(int v2, int *toh, int *tow)
@@ -828,11 +827,12 @@ static inline void sgx_fb2_tile(int v2, int *toh, int *tow)
     if ((v2 >> 4) == 4) { *toh = 4; *tow = 19; return; }        // 38 = 2 x 19 columns: 20 tiles per image; measured 0.67 ms against 0.75 (5 x 16) and 0.72 (6 x 13)
     *toh = (v2 >> 4) == 2 ? 7 : (v2 & 1) ? 16 : 8;
 }       // stride 2: 7 x 16 outputs = 15 x 33 inputs = 4 full slots
-static inline int sgx_fb2_launch(const SgxFusedBlk &fb, int batch, sgx_stream_t st)
+// the dispatch table: prepare = true only reports whether fb.v2 names an instantiation (sgx_det_create), prepare = false launches it
+static inline int sgx_fb2_dispatch(const SgxFusedBlk &fb, int batch, sgx_stream_t st, bool prepare)
 {
     const unsigned grid = (unsigned)(fb.tiles_x * fb.tiles_y * batch);
     SgxFb2Se se; se.wq1p = fb.wq1p; se.bq1 = fb.bq1; se.wq2p = fb.wq2p; se.bq2 = fb.bq2; se.qlo = fb.qlo; se.qhi = fb.qhi; se.gc1 = fb.gc1; se.glo = fb.glo; se.ghi = fb.ghi; se.gc2 = fb.gc2;
-#define SGX_FB2Q(CIN_, COUT_, K_, S_, TOH_, TOW_, CM_, RES_, UA_, NQ_, PIPE_) do { auto kfn = fb.res ? k_fused_block2<CIN_, COUT_, K_, S_, TOH_, TOW_, CM_, RES_, UA_, NQ_, PIPE_> : k_fused_block2<CIN_, COUT_, K_, S_, TOH_, TOW_, CM_, 0, UA_, NQ_, PIPE_>;                                        \
+#define SGX_FB2Q(CIN_, COUT_, K_, S_, TOH_, TOW_, CM_, RES_, UA_, NQ_, PIPE_) do { if (prepare) break; auto kfn = fb.res ? k_fused_block2<CIN_, COUT_, K_, S_, TOH_, TOW_, CM_, RES_, UA_, NQ_, PIPE_> : k_fused_block2<CIN_, COUT_, K_, S_, TOH_, TOW_, CM_, 0, UA_, NQ_, PIPE_>;                                        \
         SGX_LAUNCH(kfn, dim3(grid), dim3(SGX_FB2_THREADS), st, fb.Cmid, fb.H, fb.W, fb.Ho, fb.Wo, fb.pad, fb.tiles_x, fb.tiles_y, fb.lo1, fb.hi1, fb.lo2, fb.hi2,     \
                    fb.in, fb.in_pitch, fb.w1, fb.b1, fb.wd2, fb.bd, fb.w2t, fb.ldw2, fb.b2, fb.out, fb.out_pitch, fb.res, fb.res_pitch, se); } while (0)
 #define SGX_FB2(CIN_, COUT_, K_, S_, TOH_, TOW_, CM_, RES_, UA_) SGX_FB2Q(CIN_, COUT_, K_, S_, TOH_, TOW_, CM_, RES_, UA_, 0, 0)
@@ -849,3 +849,4 @@ static inline int sgx_fb2_launch(const SgxFusedBlk &fb, int batch, sgx_stream_t 
 #undef SGX_FB2Q
     return SGX_OK;
 }
+

@@ -451,32 +451,27 @@ SGX_KERNEL_OCC(256, OCC) k_hrb(SgxHrb p)
 #else
 #define SGX_HRB_ALTERNATIVES(X)
 #endif
-static inline bool sgx_hrb_variant(int cin, int cmid, int cout, int k, int s, int cq, bool res, float lo1, float lo2, int *toh, int *tow, int *occ)
+// pick (tap build, SGX_HRB_PICK): take the pick-th instantiation that fits the block instead of the first
+static inline bool sgx_hrb_variant(int cin, int cmid, int cout, int k, int s, int cq, bool res, float lo1, float lo2, int pick, int *toh, int *tow, int *occ)
 {
     if (lo1 != 0.f || lo2 != 0.f) return false;
-    static const int pick_env = sgx_getenv("SGX_HRB_PICK") ? atoi(sgx_getenv("SGX_HRB_PICK")) : 0;
     int seen = 0; bool found = false;
 #define SGX_HRB_X(CIN_, CMID_, COUT_, K_, S_, TOH_, TOW_, NQS_, RES_, OCC_) \
-    if (cin == CIN_ && cmid == CMID_ && cout == COUT_ && k == K_ && s == S_ && ((cq + 15) / 16) == NQS_ && res == RES_) { if (!found || seen <= pick_env) { *toh = TOH_; *tow = TOW_; *occ = OCC_; found = true; } seen++; }
+    if (cin == CIN_ && cmid == CMID_ && cout == COUT_ && k == K_ && s == S_ && ((cq + 15) / 16) == NQS_ && res == RES_) { if (!found || seen <= pick) { *toh = TOH_; *tow = TOW_; *occ = OCC_; found = true; } seen++; }
     SGX_HRB_INSTANCES(SGX_HRB_X)
 #undef SGX_HRB_X
     return found;
 }
-static inline int sgx_hrb_launch(const SgxHrb &p0, int batch, sgx_stream_t st)
+// the dispatch table: prepare = true reports whether p has an instantiation and allows it its dynamic LDS (sgx_det_create, once per planned step); prepare = false launches it
+static inline int sgx_hrb_dispatch(const SgxHrb &p0, int batch, sgx_stream_t st, bool prepare)
 {
     SgxHrb p = p0; p.batch = batch;
     const unsigned grid = (unsigned)(p.tiles_x * p.tiles_y * batch);
-#ifndef SGX_EMU
 #define SGX_HRB_X(CIN_, CMID_, COUT_, K_, S_, TOH_, TOW_, NQS_, RES_, OCC_) \
     if (p.Cin == CIN_ && p.Cmid == CMID_ && p.Cout == COUT_ && p.K == K_ && p.S == S_ && ((p.Cq + 15) / 16) == NQS_ && (p.res != nullptr) == RES_ && p.TOH == TOH_ && p.TOW == TOW_ && p.occ == OCC_) { \
-        auto kfn = k_hrb<CIN_, CMID_, COUT_, K_, S_, TOH_, TOW_, NQS_, RES_, OCC_>; constexpr int lds = SgxHrbGeom<CIN_, CMID_, COUT_, K_, S_, TOH_, TOW_>::LDS_BYTES; static bool attr = false; \
-        if (!attr) { (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; } \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, p); return SGX_OK; }
-#else
-#define SGX_HRB_X(CIN_, CMID_, COUT_, K_, S_, TOH_, TOW_, NQS_, RES_, OCC_) \
-    if (p.Cin == CIN_ && p.Cmid == CMID_ && p.Cout == COUT_ && p.K == K_ && p.S == S_ && ((p.Cq + 15) / 16) == NQS_ && (p.res != nullptr) == RES_ && p.TOH == TOH_ && p.TOW == TOW_ && p.occ == OCC_) { \
-        auto kfn = k_hrb<CIN_, CMID_, COUT_, K_, S_, TOH_, TOW_, NQS_, RES_, OCC_>; SGX_LAUNCH(kfn, dim3(grid), dim3(256), st, p); return SGX_OK; }
-#endif
+        auto kfn = k_hrb<CIN_, CMID_, COUT_, K_, S_, TOH_, TOW_, NQS_, RES_, OCC_>; constexpr int lds = SgxHrbGeom<CIN_, CMID_, COUT_, K_, S_, TOH_, TOW_>::LDS_BYTES; \
+        if (prepare) return sgx_allow_lds(kfn, lds); \
+        SGX_LAUNCH_DYN(kfn, dim3(grid), dim3(256), lds, st, p); return SGX_OK; }
     SGX_HRB_INSTANCES(SGX_HRB_X)
 #undef SGX_HRB_X
     return SGX_ERR_INVALID;

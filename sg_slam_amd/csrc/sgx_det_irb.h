@@ -989,13 +989,16 @@ __global__ void __launch_bounds__(256) k_presplit(int C, int HW, int ldS, int nk
 #endif
 
 #ifndef SGX_IRB_NO_LAUNCH
-static inline int sgx_irb_launch(const SgxIrb &p, int batch, sgx_stream_t st)
+// One dispatch table for the three kernel families (k_irb, k_irb with a bf16x3 expand GEMM, k_irb3): prepare = true reports whether an instantiation exists for p and allows
+// it its dynamic LDS (sgx_det_create, once per planned step); prepare = false launches it.
+static inline int sgx_irb_dispatch(const SgxIrb &p, int batch, sgx_stream_t st, bool prepare)
 {
+    const int NT = (p.Cout + 31) / 32, NQ = (p.Cq + 31) / 32, NT2 = (p.Cout2 + 31) / 32;
 #ifdef SGX_EMU
+    if (prepare) return sgx_irb_supported(p.K, p.S, NT, NQ, p.has_expand != 0, p.act2 == SGX_EMODE_HSWISH, NT2) ? SGX_OK : SGX_ERR_UNSUPPORTED;
     for (int b = 0; b < batch; b++) sgx_irb_emu(p, b);
     return SGX_OK;
 #else
-    const int NT = (p.Cout + 31) / 32, NQ = (p.Cq + 31) / 32, NT2 = (p.Cout2 + 31) / 32;
     const int maxPO = p.nbands > 1 ? p.OH * p.Wo : p.G * p.Ho * p.Wo, ngo = (maxPO + 31) / 32;
     const int maxPI = p.nbands > 1 ? std::min(p.H, (p.OH - 1) * p.S + p.K) * p.W : p.G * p.H * p.W;
     const int nw = std::max(ngo, std::min(12, (maxPI + 31) / 32));               // one wave per output-pixel group; up to 12 waves share the stage-A tiles
@@ -1003,37 +1006,32 @@ static inline int sgx_irb_launch(const SgxIrb &p, int batch, sgx_stream_t st)
     const size_t lds = sgx_irb_lds_bytes(p);
     if (nw > 12 || lds > 160 * 1024) return SGX_ERR_UNSUPPORTED;
     SgxIrb q = p; q.batch = batch;
-    { static const int dbg_env = sgx_getenv("SGX_IRB3_DBG") ? atoi(sgx_getenv("SGX_IRB3_DBG")) : 0; q.dbg = dbg_env; }
-#ifdef SGX_DEBUG_TAPS
+#define SGX_IRB_X(K_, S_, NT_, NQ_, E_, H_, N2_) if (p.K == K_ && p.S == S_ && NT == NT_ && NQ == NQ_ && (p.has_expand != 0) == E_ && (p.act2 == SGX_EMODE_HSWISH) == H_ && NT2 == N2_) { \
+        auto kfn = SGX_IRB_KERNEL(K_, S_, NT_, NQ_, E_, H_, N2_); \
+        if (prepare) return sgx_allow_lds(kfn, 160 * 1024); \
+        hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * nw), lds, st, q); return SGX_OK; }
+#ifdef SGX_DEBUG_TAPS      /* k_irb3 and the bf16x3-expand variant of k_irb */
     if (p.gemm == 1) {
         const int nqs = NQ == 0 ? 1 : (NQ == 2 ? 3 : (NT == 2 ? 1 : 2));
         if (NQ > 0 && (p.Cq + 15) / 16 != nqs) return SGX_ERR_UNSUPPORTED;
-#define SGX_IRB_X(K_, S_, NT_, NQ_, E_, H_, N2_) if (p.K == K_ && p.S == S_ && NT == NT_ && NQ == NQ_ && (p.has_expand != 0) == E_ && (p.act2 == SGX_EMODE_HSWISH) == H_ && NT2 == N2_) { \
-        auto kfn = k_irb3<K_, S_, NT_, NQ_, E_, H_, N2_>; static bool attr = false; \
-        if (!attr) { (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * nw), lds, st, q); return SGX_OK; }
+#define SGX_IRB_KERNEL(...) k_irb3<__VA_ARGS__>
         SGX_IRB_INSTANCES(SGX_IRB_X)
-#undef SGX_IRB_X
+#undef SGX_IRB_KERNEL
         return SGX_ERR_UNSUPPORTED;
     }
-    if (p.gemm == 2 && p.has_expand && p.inS) {
-        const int nks = (p.Cin + 15) / 16, total = batch * nks * 2 * p.H * p.W;
-        hipLaunchKernelGGL(k_presplit, dim3((total + 255) / 256), dim3(256), 0, st, p.Cin, p.H * p.W, p.ldS, nks, total, p.in, p.in_pitch, (sgx_u32x4 *)p.inS);
-    }
     if (p.gemm == 2 && p.has_expand) {
-#define SGX_IRB_X(K_, S_, NT_, NQ_, E_, H_, N2_) if (E_ && p.K == K_ && p.S == S_ && NT == NT_ && NQ == NQ_ && (p.act2 == SGX_EMODE_HSWISH) == H_ && NT2 == N2_) { \
-        auto kfn = k_irb<K_, S_, NT_, NQ_, E_, H_, N2_, true>; static bool attr = false; \
-        if (!attr) { (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * nw), lds, st, q); return SGX_OK; }
+        if (p.inS && !prepare) {
+            const int nks = (p.Cin + 15) / 16, total = batch * nks * 2 * p.H * p.W;
+            hipLaunchKernelGGL(k_presplit, dim3((total + 255) / 256), dim3(256), 0, st, p.Cin, p.H * p.W, p.ldS, nks, total, p.in, p.in_pitch, (sgx_u32x4 *)p.inS);
+        }
+#define SGX_IRB_KERNEL(...) k_irb<__VA_ARGS__, true>
         SGX_IRB_INSTANCES(SGX_IRB_X)
-#undef SGX_IRB_X
+#undef SGX_IRB_KERNEL
     }
-#endif      /* SGX_DEBUG_TAPS: k_irb3 and the bf16x3-expand variant of k_irb */
-#define SGX_IRB_X(K_, S_, NT_, NQ_, E_, H_, N2_) if (p.K == K_ && p.S == S_ && NT == NT_ && NQ == NQ_ && (p.has_expand != 0) == E_ && (p.act2 == SGX_EMODE_HSWISH) == H_ && NT2 == N2_) { \
-        auto kfn = k_irb<K_, S_, NT_, NQ_, E_, H_, N2_>; static bool attr = false; \
-        if (!attr) { (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * nw), lds, st, q); return SGX_OK; }
+#endif
+#define SGX_IRB_KERNEL(...) k_irb<__VA_ARGS__>
     SGX_IRB_INSTANCES(SGX_IRB_X)
+#undef SGX_IRB_KERNEL
 #undef SGX_IRB_X
     return SGX_ERR_UNSUPPORTED;
 #endif

@@ -281,6 +281,16 @@ SGX_DEV unsigned sgx_fastdiv(unsigned n, unsigned m)
     return m ? (unsigned)(((unsigned long long)n * m) >> 32) : n;
 #endif
 }
+// host: the m of sgx_fastdiv for the divisor d
+static inline unsigned sgx_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
+// host: the `prepare` half of a dispatch table — a kernel whose dynamic LDS exceeds 64 KB must be allowed that much once, before its first launch (and outside any stream capture)
+template <class Kfn> static inline int sgx_allow_lds(Kfn kfn, size_t bytes)
+{
+#ifndef SGX_EMU
+    if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return SGX_ERR_DEVICE;
+#endif
+    return SGX_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // k_conv_pw2: 1x1 convolution as a weights-stationary streaming GEMM on the fp32 matrix cores.
