@@ -10,6 +10,7 @@
 
 #define SGX_BA_THREADS 256
 #define SGX_BA_MAX_DENSE 24576       /* largest reduced camera system (6 * free poses) factorised densely (4.8 GB of fp64) */
+static_assert(sizeof(int) * (SGX_BA_MAX_DENSE / 6) <= 64 * 1024, "k_ba_jobs_row keeps one LDS counter per free pose: they must fit the default 64 KB dynamic LDS limit");
 
 // edge record: pose index, point index, flags (bit0 stereo, bit1 level==1, bit2 Huber on)
 struct SgxBaEdge { int pose, point, flags; float obs[3]; float info; };
@@ -219,14 +220,14 @@ SGX_KERNEL(SGX_BA_THREADS) k_ba_schur_init(int nf, const double *Hpp, double lam
 // The reference factorises it with Eigen SimplicialLDLT (G/solvers/linear_solver_eigen.h:94-124); the solution is unique,
 // so a Cholesky L L^T is used here.  *ok is cleared when a pivot is not positive (or NaN): the LM step is then rejected
 // exactly like solve()==false (levenberg.cpp:126-127).
-//   n <= 128 : k_chol_small_reg — one 256-thread workgroup, the working matrix in registers, finished columns in LDS (k_chol_small, the LDS-resident
-//              first version, stays as a comparison tap).
+//   n <= 128 : k_chol_small_reg — one 256-thread workgroup, the working matrix in registers, finished columns in LDS.
 //   n  > 128 : blocked right-looking factorisation on 32x32 tiles staged in LDS, per panel k:
-//                k_chol_diag_wave (ONE wave, tile in registers: factor L_kk and its explicit inverse Linv_kk; k_chol_diag = workgroup / LDS version, emulator + tap)
+//                k_chol_diag_wave (ONE wave, tile in registers: factor L_kk and its explicit inverse Linv_kk; k_chol_diag = workgroup / LDS version, the emulator's)
 //                k_chol_panel  (one workgroup per row tile below:  L_ik = A_ik Linv_kk^T   — a tile GEMM)
 //                k_chol_update (one workgroup per lower-triangular tile pair inside the current 256-column outer panel: A_ij -= L_ik L_jk^T)
 //              per outer panel: k_chol_update_wide (fp64 MFMA rank-256 update of everything right of the panel, 64 x 64 tiles)
-//              then the backward pass: k_chol_back_step per diagonal block (all CUs), or k_chol_solve (one workgroup) via the tuning tap.
+//              then the backward pass: k_chol_back_step per diagonal block (all CUs).
+// Switches (BaSwitches, sgx_ba_plan.h; tap build and emulator only): SGX_TUNE_CHOL_WIDE_MIN = unknowns above which the outer panels are used (default 1024).
 // ---------------------------------------------------------------------------------------------
 #define SGX_NB 32            /* tile edge of the blocked factorisation.  Measured: 64 halves the launches and runs the 2000-keyframe BA 8 % faster, but its
                                 diagonal-tile kernel (64 serial steps + a 64-long register inverse) makes LocalBA-sized systems 20 % slower */
@@ -234,58 +235,14 @@ SGX_KERNEL(SGX_BA_THREADS) k_ba_schur_init(int nf, const double *Hpp, double lam
 #define SGX_TB (SGX_NB / 16)  /* register block edge of the tile GEMMs (16 x 16 thread map) */
 #define SGX_CHOL_SMALL 128
 
-SGX_KERNEL(256) k_chol_small(int n, const double *S, const double *bp, const double *coef, double *x, int *ok)
-{
-    // L D L^T in "unscaled column" form: column j keeps u_ij = L_ij * d_j, so no square roots and no separate column-scaling phase; the right-hand side
-    // rides along as an extra column (forward substitution folded into the factorisation).  One barrier per column for the factorisation, one per
-    // column for the back substitution  x_j = (v_j - sum_{i>j} u_ij x_i) / d_j.  Rows are padded to an odd stride (bank-conflict-free column walks);
-    // the trailing update maps the 256 threads as 16 x 16 over (row, column) residues — no integer divisions in the loops.
-    constexpr int LD = SGX_CHOL_SMALL + 1;
-    SGX_LDS double A[SGX_CHOL_SMALL * LD];
-    SGX_LDS double v[SGX_CHOL_SMALL];
-    const int NT = (int)blockDim.x;
-    SGX_THREADS_BEGIN(tid)
-    for (int r = tid >> 4; r < n; r += NT >> 4)
-        for (int c = tid & 15; c < n; c += 16) A[r * LD + c] = S[(size_t)r * n + c];
-    for (int i = tid; i < n; i += NT) v[i] = bp[i] - coef[i];
-    SGX_THREADS_END
-    SGX_SYNC();
-    int jfail = n;
-    for (int j = 0; j < n; j++) {
-        const double d = A[j * LD + j];                  // final pivot: every update from the columns before j has been applied
-        if (!(d > 0)) { jfail = j; break; }
-        const double rd = 1.0 / d, vj = v[j];
-        SGX_THREADS_BEGIN(tid)
-        const int ty = tid >> 4, tx = tid & 15;
-        for (int i = j + 1 + ty; i < n; i += NT >> 4) {
-            const double f = A[i * LD + j] * rd;         // L_ij
-            for (int c = j + 1 + tx; c <= i; c += 16) A[i * LD + c] -= f * A[c * LD + j];
-            if (tx == 0) v[i] -= f * vj;
-        }
-        SGX_THREADS_END
-        SGX_SYNC();
-    }
-    if (jfail < n) {
-        SGX_THREADS_BEGIN(tid) if (tid == 0) *ok = 0; SGX_THREADS_END
-        return;
-    }
-    for (int j = n - 1; j >= 0; j--) {
-        const double xj = v[j] / A[j * LD + j];
-        SGX_THREADS_BEGIN(tid)
-        for (int i = tid; i < j; i += NT) v[i] -= A[j * LD + i] * xj;
-        if (tid == 0) x[j] = xj;
-        SGX_THREADS_END
-        SGX_SYNC();
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
-// k_chol_small_reg: the same factorisation and solve (n <= 128, unscaled L D L^T, right-hand side riding along) with the working matrix in REGISTERS.
+// k_chol_small_reg: factorisation and solve for n <= 128 with the working matrix in REGISTERS.  L D L^T in "unscaled column" form: column j keeps u_ij = L_ij * d_j, so
+// no square roots and no separate column-scaling phase; the right-hand side rides along as an extra column (forward substitution folded into the factorisation).
 // Thread (ty, tx) of the 16 x 16 map owns A[ty + 16 a][tx + 16 c], a, c = 0..7 (64 doubles) and a copy of the right-hand side entries v[tx + 16 c].
 // Column j: its owners (tx == j mod 16) publish the finished column, unscaled, as row j of LmT in LDS (+ v_j in slot 128) — one barrier — and every thread
 // applies the rank-1 update to its own registers from 2 x 8 broadcast reads of that row.  The 8 x 16 column steps are unrolled over the column group jb so
 // that every register index is static and the row / column groups already eliminated (a, c < jb; c > a) are pruned at compile time: 120 multiply-add
-// statements in total instead of 64 per column.  The LDS-resident version (k_chol_small) spends ~1.8 us per column on dependent LDS read-modify-writes;
+// statements in total instead of 64 per column.  An LDS-resident first version spent ~1.8 us per column on dependent LDS read-modify-writes;
 // LmT doubles as the factor for the back substitution, done 16 unknowns at a time: every thread solves the 16 x 16 triangle redundantly in registers
 // (no barriers inside), then threads 0..j0-1 push the block into their pending right-hand sides — 8 barriers instead of 128.
 // (Measured and dropped: two columns per barrier, every thread correcting the second published column itself — 3.30 vs 3.05 ms per LocalBA of 20 + 40
@@ -392,7 +349,7 @@ SGX_KERNEL(256) k_chol_small_reg(int n, const double *S, const double *bp, const
 // factor the diagonal tile (lower part of S overwritten with L_kk) and store Linv_kk (32x32, row-major, zero-padded) in Linv[k0/NB]
 SGX_KERNEL(256) k_chol_diag(int n, int k0, double *S, double *Linv, int *ok, const double *bp, const double *coef, double *x)
 {
-    // Factorised in the same unscaled L D L^T form as k_chol_small (one barrier per column, 16 x 16 thread map, no integer divisions in the loops);
+    // Factorised in the same unscaled L D L^T form as k_chol_small_reg (one barrier per column, 16 x 16 thread map, no integer divisions in the loops);
     // the Cholesky factor the panel / update kernels expect is recovered at the end: L_ij = u_ij / sqrt(d_j), L_jj = sqrt(d_j).
     SGX_LDS double A[SGX_NB][SGX_NB + 1];
     SGX_LDS double X[SGX_NB][SGX_NB + 1];
@@ -1155,30 +1112,8 @@ SGX_KERNEL(1024) k_chol_env_back(int n, int nt, const int *rstart, const int *ro
     }
 }
 
-// x = (bp - coef); L y = x; L^T x = y — blocked with the stored diagonal inverses, one 256-thread workgroup
-SGX_KERNEL(256) k_chol_solve(int n, const double *S, const double *Linv, const double *bp, const double *coef, double *x, const int *ok)
-{
-    SGX_LDS double ys[SGX_NB];
-    if (!*ok) return;
-    const int NT = (int)blockDim.x;
-    // x already holds y = L^-1 (bp - coef): the forward substitution ran inside k_chol_diag / k_chol_panel.  Backward pass:
-    for (int k0 = ((n - 1) / SGX_NB) * SGX_NB; k0 >= 0; k0 -= SGX_NB) {
-        const int nb = min(SGX_NB, n - k0);
-        const double *Lk = Linv + (size_t)(k0 / SGX_NB) * SGX_NB * SGX_NB;
-        SGX_THREADS_BEGIN(tid)
-        if (tid < nb) { double sacc = 0; for (int q = tid; q < nb; q++) sacc += Lk[q * SGX_NB + tid] * x[k0 + q]; ys[tid] = sacc; }    // x_k = Linv_kk^T y_k
-        SGX_THREADS_END
-        SGX_SYNC();
-        SGX_THREADS_BEGIN(tid)
-        if (tid < nb) x[k0 + tid] = ys[tid];
-        for (int i = tid; i < k0; i += NT) { double vv = x[i]; for (int q = 0; q < nb; q++) vv -= S[(size_t)(k0 + q) * n + i] * ys[q]; x[i] = vv; }
-        SGX_THREADS_END
-        SGX_SYNC();
-    }
-}
-
-// One step of the same backward pass spread over the chip (large systems: the single workgroup above would stream the whole factor, n^2/2 doubles,
-// through one CU).  Launched once per diagonal block, last block first: every workgroup recomputes x_k = Linv_kk^T y_k (a 32 x 32 mat-vec) from the
+// One step of the backward pass  L^T x = y  of the blocked factorisation (y = L^-1 (bp - coef) is already in place: the forward substitution ran inside the diagonal
+// and panel kernels), spread over the chip: a single workgroup would stream the whole factor, n^2/2 doubles, through one CU.  Launched once per diagonal block, last block first: every workgroup recomputes x_k = Linv_kk^T y_k (a 32 x 32 mat-vec) from the
 // working vector y, workgroup 0 stores it to `xsol`, and workgroup w applies the update y_i -= sum_q L[k0+q][i] x_k[q] to its 256 columns i < k0
 // (32 coalesced row segments).  y[k0..] is only read during the launch and `xsol` only written, so the workgroups need no ordering among themselves.
 SGX_KERNEL(256) k_chol_back_step(int n, int k0, const double *S, const double *Linv, double *y, double *xsol, const int *ok)

@@ -18,8 +18,6 @@
 thread_local sgx_dim3 blockIdx, blockDim, gridDim;
 #endif
 
-#define SGX_CHECK_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
-    fprintf(stderr, "sgx: HIP error %d (%s) at %s:%d\n", (int)_e, hipGetErrorString(_e), __FILE__, __LINE__); return SGX_ERR_DEVICE; } } while (0)
 
 struct sgx_orb {
     sgx_orb_config cfg;

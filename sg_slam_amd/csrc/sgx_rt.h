@@ -106,5 +106,11 @@ static inline hipError_t hipMemcpyToSymbolEmu(void *d, const void *s, size_t n) 
 enum { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
 #endif
 
+// host side: a failed runtime call ends the C entry with SGX_ERR_DEVICE (the user needs <stdio.h> and include/sgx.h)
+#ifndef SGX_CHECK_HIP
+#define SGX_CHECK_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
+    fprintf(stderr, "sgx: HIP error %d (%s) at %s:%d\n", (int)_e, hipGetErrorString(_e), __FILE__, __LINE__); return SGX_ERR_DEVICE; } } while (0)
+#endif
+
 // round-half-to-even to int (OpenCV cvRound semantics)
 SGX_DEV int sgx_cvround(float v) { return (int)rintf(v); }

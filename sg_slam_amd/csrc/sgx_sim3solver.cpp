@@ -10,8 +10,6 @@
 #include <string.h>
 #include <vector>
 
-#define SGX_CHECK_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
-    fprintf(stderr, "sgx: HIP error %d (%s) at %s:%d\n", (int)_e, hipGetErrorString(_e), __FILE__, __LINE__); return SGX_ERR_DEVICE; } } while (0)
 
 struct sgx_sim3_solver {
     int N = 0, fix_scale = 0;

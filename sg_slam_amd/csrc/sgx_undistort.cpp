@@ -7,8 +7,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#define SGX_CHECK_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
-    fprintf(stderr, "sgx: HIP error %d (%s) at %s:%d\n", (int)_e, hipGetErrorString(_e), __FILE__, __LINE__); return SGX_ERR_DEVICE; } } while (0)
 
 static int make_undist(const float *K4, const float *dist, int ndist, int on, SgxUndist *ud)
 {

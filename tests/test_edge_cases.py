@@ -59,3 +59,26 @@ def run_edge_cases(lib, oracle, S):
 
 def test_edge_cases_emu(emu, oracle, stream_frames):
     run_edge_cases(emu, oracle, stream_frames)
+
+
+def test_ba_oversized_job_list_is_unsupported_emu(emu):
+    """4 096 free poses, 129 landmarks each observed by every pose: 528 384 edges whose Schur job list could hold 129 * 4096^2 = 129 * 2^24 > 2^31 entries, more than
+    the int offsets of the list (host builder, k_ba_jobs_scan) can count.  The index pass refuses it (SGX_ERR_UNSUPPORTED = -2) before anything is allocated or launched:
+    within a second."""
+    import ctypes as C
+    import time
+    from sg_slam_amd.capi import BaProblem, BaStats
+    from sg_slam_amd.matcher import camera_struct
+    npose, nl = 4096, 129
+    poses = np.tile(np.eye(4, dtype='f4').reshape(16), (npose, 1)); fixed = np.zeros(npose, np.uint8)
+    pts = np.zeros((nl, 3), 'f4'); pts[:, 2] = 5.0
+    el, ep = [a.ravel().astype('i4') for a in np.meshgrid(np.arange(nl), np.arange(npose), indexing='ij')]
+    ne = len(ep); assert ne == 528384
+    eo = np.tile(np.array([320.0, 240.0, 300.0], 'f4'), (ne, 1)); ei = np.ones(ne, 'f4')
+    P = BaProblem(npose, nl, ne, poses.ctypes.data, fixed.ctypes.data, pts.ctypes.data, ep.ctypes.data, el.ctypes.data, eo.ctypes.data, ei.ctypes.data)
+    erase = np.zeros(ne, np.uint8); st = BaStats(); cs = camera_struct(CAM)
+    t = time.perf_counter()
+    rc = emu.dll.sgx_local_bundle_adjustment(C.byref(P), C.byref(cs), None, erase.ctypes.data_as(C.c_void_p), C.byref(st))
+    dt = time.perf_counter() - t
+    assert rc == -2, rc
+    assert dt < 1.0, dt
