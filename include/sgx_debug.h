@@ -37,6 +37,8 @@ int sgx_pnp_debug_betas(int which, const double *L, const double *rho, double *b
 int sgx_debug_corun_bf16(int blocks, int iters, int launches, void *stream);      /* test tap: `launches` launches of a kernel that only issues bf16 matrix products, asynchronous on `stream` (co-runner of the packed-fp32 regression test) */
 /* test tap: DetectionOutput + detect() filtering alone on caller-supplied head outputs (host arrays: loc batch x num_priors x 4, conf batch x num_priors x num_class) */
 int sgx_det_debug_detection_output(sgx_det *h, const float *loc, const float *conf, int batch, sgx_det_result *results);
+/* test tap: number of (frame, class) pairs of this handle's last DetectionOutput that the per-frame cut sent through the continuation (0 with SGX_DET_OUT_SINGLE) */
+int sgx_det_debug_continued(sgx_det *h, int *count);
 /* test / tuning taps.  Every sgx_*_debug_set_* setting is PER CALLING THREAD (thread_local): it affects the next create / call made by the same thread only, so the taps
  * cannot leak into the Tracking, Detector2D or LocalMapping thread of a host program; the SGX_* environment switches are read once and never written.
  * set_fusion(0) makes the NEXT sgx_det_create build the unfused plan (one kernel per ncnn layer, every blob

@@ -78,6 +78,7 @@ struct DetSwitches {
     int prefuse = 1, xcd = 1;                           // SGX_DET_PREFUSE (pre-processing inside the stem), SGX_DET_XCD (XCD-aware work order, sgx_xcd_order)
     int stem_words = 13824, dw2 = 1, dw3 = 0, dw_budget = 8192, pw3_mink = 64, pw3_force = 0, pw2_direct = 1;      // launch geometry: SGX_DET_STEM_WORDS, SGX_DW2, SGX_DW3, SGX_DW_BUDGET, SGX_PW3_MINK, SGX_PW3_FORCE (OCB * 10 + PXB), SGX_PW2_DIRECT
     int no_graph = 0, fork_lanes = SGX_DET_FORK_LANES, graph_execs = SGX_DET_GRAPH_EXECS, skip_output = 0;      // SGX_DET_NO_GRAPH, SGX_DET_FORK, SGX_DET_EXECS, SGX_DET_SKIP_OUTPUT (timing tap: what the per-class NMS chains cost the detector stream)
+    int out_single = 0;                                 // SGX_DET_OUT_SINGLE: DetectionOutput as one full NMS per (frame, class) instead of first chunk + cut + continuation (A/B arm; same rows)
 };
 
 struct sgx_det {
@@ -95,6 +96,8 @@ struct sgx_det {
     int loc_blob = -1, conf_blob = -1;
     SgxDetTab *d_xt = nullptr, *d_yt = nullptr; uint8_t *d_img = nullptr;
     float *d_priors = nullptr, *d_cls_rows = nullptr; int *d_cls_count = nullptr; sgx_det_result *d_results = nullptr;      // DetectionOutput on the device
+    int *d_cls_ncut = nullptr, *d_cls_cont = nullptr; uint32_t *d_cls_next = nullptr, *d_sstar = nullptr;                  // its first chunk's record per (frame, class), the cut's decision (k_det_cut)
+    int last_out_batch = 0;                                                                                                // batch of the last two-stage DetectionOutput (0: none, or single-stage) for sgx_det_debug_continued
     double gmac = 0;
 #ifndef SGX_EMU
     std::map<int, std::vector<hipGraphExec_t>> graphs;     // captured plan per batch size (launch-bound tail of ~100 small kernels -> one graph launch); SGX_DET_EXECS instances used in turn
@@ -152,6 +155,7 @@ static DetSwitches det_switches()
     env("SGX_PW3_MINK", s.pw3_mink); env("SGX_PW3_FORCE", s.pw3_force); env("SGX_PW2_DIRECT", s.pw2_direct);
     s.no_graph = sgx_getenv("SGX_DET_NO_GRAPH") != nullptr; env("SGX_DET_FORK", s.fork_lanes); env("SGX_DET_EXECS", s.graph_execs);
     s.skip_output = sgx_getenv("SGX_DET_SKIP_OUTPUT") != nullptr;
+    s.out_single = sgx_getenv("SGX_DET_OUT_SINGLE") != nullptr;
     return s;
 }
 
@@ -894,6 +898,7 @@ static int finalise(sgx_det *h)
         h->keep_top_k > SGX_DET_MAX) return SGX_ERR_UNSUPPORTED;
     int rc = h->upload(&h->d_priors, h->priors.data(), (size_t)h->num_priors * 4); if (rc) return rc;
     if (h->alloc(&h->d_cls_rows, (size_t)B * (h->num_class - 1) * SGX_DO_TOPK * 6) || h->alloc(&h->d_cls_count, (size_t)B * (h->num_class - 1)) || h->alloc(&h->d_results, (size_t)B)) return SGX_ERR_NOMEM;
+    if (h->alloc(&h->d_cls_ncut, (size_t)B * (h->num_class - 1)) || h->alloc(&h->d_cls_next, (size_t)B * (h->num_class - 1)) || h->alloc(&h->d_cls_cont, (size_t)B * (h->num_class - 1)) || h->alloc(&h->d_sstar, (size_t)B)) return SGX_ERR_NOMEM;
 #ifndef SGX_EMU      // A/B switch of the XCD-aware work order (sgx_xcd_order); on by default
     SGX_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(sgx_det_xcd_order), &h->sw.xcd, sizeof(int)));
 #else
@@ -1331,7 +1336,7 @@ SGX_TAP int sgx_det_debug_read_blob(sgx_det *h, const char *name, int image, flo
 static int run_detection_output(sgx_det *h, int batch, sgx_det_result *d_results, float *d_boxes, int32_t *d_nboxes, int max_boxes, int32_t *d_have_dynamic, sgx_stream_t st);
 
 // Detector2D::detect, device-resident: forward, then ncnn DetectionOutput (decode + per-class NMS + keep_top_k) and the detect() filtering as two kernels
-// (k_det_class_nms, k_det_merge).  d_results[batch] receives the same struct the host entry returns; d_boxes / d_nboxes / d_have_dynamic (optional) are
+// (k_det_class_nms as first chunk and continuation with k_det_cut between them, k_det_merge).  d_results[batch] receives the same struct the host entry returns; d_boxes / d_nboxes / d_have_dynamic (optional) are
 // the person rectangles, their count and the have-dynamic flag in the layout sgx_dynamic_mask_batch_dev and sgx_frame_compact_keys_batch_dev take.
 extern "C" int sgx_det_detect_batch_dev(sgx_det *h, const uint8_t *d_img, int pitch, int batch, sgx_det_result *d_results,
                                         float *d_boxes, int32_t *d_nboxes, int max_boxes, int32_t *d_have_dynamic, void *stream_)
@@ -1349,7 +1354,19 @@ static int run_detection_output(sgx_det *h, int batch, sgx_det_result *d_results
     P.var0 = h->dvar[0]; P.var1 = h->dvar[1]; P.var2 = h->dvar[2]; P.var3 = h->dvar[3];
     if (h->sw.skip_output) return SGX_OK;      // timing tap (round 6): what the per-class NMS chains cost the detector stream's critical path
     sgx_prof_begin(SGX_K_DET_OUT, st);
-    SGX_LAUNCH_DYN(k_det_class_nms, dim3(h->num_class - 1, batch), dim3(256), (size_t)std::max(h->num_priors, 7 * SGX_DO_TOPK) * 4 + 16, st, P, h->blobs[h->loc_blob].d, h->blobs[h->conf_blob].d, h->d_priors, h->d_cls_rows, h->d_cls_count);
+    const dim3 grid(h->num_class - 1, batch);
+    const size_t lds_full = (size_t)std::max(h->num_priors, 7 * SGX_DO_TOPK) * 4 + 16, lds_first = (size_t)std::max(h->num_priors, 7 * (SGX_DO_FIRST + 1)) * 4 + 16;
+    const float *loc = h->blobs[h->loc_blob].d, *conf = h->blobs[h->conf_blob].d;
+    const int *no_cont = nullptr; const uint32_t *no_sstar = nullptr; int *no_ncut = nullptr; uint32_t *no_next = nullptr;
+    if (h->sw.out_single) {
+        SGX_LAUNCH_DYN(k_det_class_nms<0>, grid, dim3(256), lds_full, st, P, loc, conf, h->d_priors, h->d_cls_rows, h->d_cls_count, no_ncut, no_next, no_cont, no_sstar);
+    } else {
+        // first chunk of every class, the per-frame cut, then the classes it lets continue (none on dense frames): the decision never leaves the device
+        SGX_LAUNCH_DYN(k_det_class_nms<SGX_DO_FIRST>, grid, dim3(256), lds_first, st, P, loc, conf, h->d_priors, h->d_cls_rows, h->d_cls_count, h->d_cls_ncut, h->d_cls_next, no_cont, no_sstar);
+        SGX_LAUNCH(k_det_cut, dim3(batch), dim3(256), st, P, h->d_cls_rows, h->d_cls_count, h->d_cls_ncut, h->d_cls_next, h->d_sstar, h->d_cls_cont);
+        SGX_LAUNCH_DYN(k_det_class_nms<0>, grid, dim3(256), lds_full, st, P, loc, conf, h->d_priors, h->d_cls_rows, h->d_cls_count, no_ncut, no_next, h->d_cls_cont, h->d_sstar);
+    }
+    h->last_out_batch = h->sw.out_single ? 0 : batch;
     SGX_LAUNCH(k_det_merge, dim3(batch), dim3(256), st, P, h->d_cls_rows, h->d_cls_count, h->det_th, h->dyn_th, h->W, h->H, h->T, d_results, d_boxes, d_nboxes, max_boxes, d_have_dynamic);
     sgx_prof_end(SGX_K_DET_OUT, st);
     SGX_CHECK_HIP(hipGetLastError());
@@ -1365,6 +1382,16 @@ SGX_TAP int sgx_det_debug_detection_output(sgx_det *h, const float *loc, const f
     int rc = run_detection_output(h, batch, h->d_results, nullptr, nullptr, 0, nullptr, (sgx_stream_t)0);
     if (rc != SGX_OK) return rc;
     SGX_CHECK_HIP(hipMemcpy(results, h->d_results, sizeof(sgx_det_result) * batch, hipMemcpyDeviceToHost));
+    return SGX_OK;
+}
+
+// test tap: how many (frame, class) pairs of the last DetectionOutput of this handle went through the continuation (0 on the single-stage path)
+SGX_TAP int sgx_det_debug_continued(sgx_det *h, int *count)
+{
+    if (!h || !count) return SGX_ERR_INVALID;
+    std::vector<int> cont((size_t)h->last_out_batch * (h->num_class - 1));
+    if (!cont.empty()) SGX_CHECK_HIP(hipMemcpy(cont.data(), h->d_cls_cont, cont.size() * sizeof(int), hipMemcpyDeviceToHost));
+    *count = 0; for (int v : cont) *count += v;
     return SGX_OK;
 }
 

@@ -1097,6 +1097,13 @@ SGX_KERNEL(256) k_compact_keys(int cap, const uint8_t *keys, const uint8_t *desc
 //     greedy NMS "keep i unless a kept, higher-ranked box overlaps it by more than nms_th" is resolved exactly: the overlap relation with all higher-ranked
 //     candidates is one bit matrix (computed in parallel), the greedy scan then runs 64 candidates at a time (suppression by earlier chunks is a parallel
 //     AND with the final kept words; inside a chunk one thread walks 64 rows).  The kept rows are written in rank order.
+//     Only rows that can reach the output are computed.  Greedy NMS is prefix-closed in rank order (a candidate's fate depends on higher-ranked candidates of
+//     its class only), so the kept rows of a class's first C candidates are final.  k_det_class_nms<SGX_DO_FIRST> does just that first chunk per (frame,
+//     class) and records the class's candidate count after the nms_top_k cut and the score of its (C+1)-th candidate; k_det_cut takes s* = the keep_top_k-th
+//     largest score among a frame's first-chunk rows: keep_top_k final rows score >= s*, so nothing below s* appears in the output.  A class continues iff it
+//     was truncated and (s* is undefined: fewer than keep_top_k rows, or its (C+1)-th candidate scores >= s* — ties at s* are decided by the merge's
+//     class-major sequence, so they stay in); k_det_class_nms<0> with the continue flags then redoes those classes alone with the full path over the candidates
+//     scoring >= s* and replaces their rows (their first rows are the ones the first chunk wrote).  Without flags (cont == nullptr) it is the single-stage path.
 //   k_det_merge      (grid: frames, 256 threads): the rows of all classes in class-major order, stable-sorted by score, cut to keep_top_k, then the
 //     detect() filter (score > det_th, or class 15 "person" above dyn_th; clamp to the 300 x 300 net input, scale to the image) fills the same
 //     sgx_det_result the host entry returns and, optionally, the (boxes, count, have-dynamic) arrays sgx_dynamic_mask_batch_dev / compact_keys take.
@@ -1106,6 +1113,7 @@ SGX_KERNEL(256) k_compact_keys(int cap, const uint8_t *keys, const uint8_t *desc
 #define SGX_DO_TOPK 320                    /* nms_top_k <= this (5 words of 64 candidates) */
 #define SGX_DO_WORDS (SGX_DO_TOPK / 64)
 #define SGX_DO_MERGE 8192                  /* (classes - 1) * nms_top_k <= this */
+#define SGX_DO_FIRST 64                    /* first chunk C of the two-stage DetectionOutput: a multiple of 64, < SGX_DO_TOPK */
 struct SgxDetOut { int n, nc, nms_top_k, keep_top_k; float nms_th, conf_th, var0, var1, var2, var3; };
 
 // descending bitonic sort of `size` (power of two) 64-bit keys in LDS by `NT` threads
@@ -1233,23 +1241,32 @@ SGX_DEV bool sgx_iou_gt(float a0, float a1, float a2, float a3, float area_a, fl
     return inter / uni > th;
 }
 
-SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf, const float *priors, float *cls_rows, int *cls_count)
+// C = 0: the full path (nms_top_k candidates; with `cont` only the classes flagged there, over the candidates scoring >= sstar[frame]).  C > 0: the first C ranked
+// candidates only; cls_ncut / cls_next receive the class's candidate count after the nms_top_k cut and the score pattern of its (C+1)-th candidate (0 = none).
+template <int C>
+SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf, const float *priors, float *cls_rows, int *cls_count, int *cls_ncut, uint32_t *cls_next,
+                                const int *cont, const uint32_t *sstar)
 {
-    SGX_DYN_LDS(sc_pool);                                        // score pattern per prior (u32 view `sc`), 0 = below the confidence threshold: sized by the host to max(num_priors, 7 * SGX_DO_TOPK) words
+    constexpr int ROWS = C ? C + 1 : SGX_DO_TOPK;                // candidates selected and ordered (the first chunk also needs its successor's score)
+    constexpr int WORDS = C ? C / 64 : SGX_DO_WORDS;             // 64-candidate words of the candidates that go through the NMS
+    SGX_DYN_LDS(sc_pool);                                        // score pattern per prior (u32 view `sc`), 0 = below the confidence threshold: sized by the host to max(num_priors, 7 * ROWS) words
     unsigned long long *sc64 = (unsigned long long *)sc_pool;     // (a static SGX_DO_SORT-entry array cost 7 KB more than this graph's 2 268 priors need: six workgroups per CU instead of five)
     uint32_t *sc = (uint32_t *)sc_pool;
     // the sorted keys, the decoded boxes and their areas are written only after the last read of `sc` (the selection loop): they live in its storage — 31 KB instead of 40 KB
     // of LDS, five workgroups per CU instead of four (round 4)
-    unsigned long long *keys = sc64;                              // [SGX_DO_TOPK]
-    float (*box)[4] = (float (*)[4])(sc + 2 * SGX_DO_TOPK);       // [SGX_DO_TOPK][4]
-    float *area = (float *)(sc + 6 * SGX_DO_TOPK);                // [SGX_DO_TOPK]
-    SGX_LDS unsigned long long over[SGX_DO_TOPK][SGX_DO_WORDS];
-    SGX_LDS unsigned long long kept[SGX_DO_WORDS];
+    unsigned long long *keys = sc64;                              // [ROWS]
+    float (*box)[4] = (float (*)[4])(sc + 2 * ROWS);              // [ROWS][4]
+    float *area = (float *)(sc + 6 * ROWS);                       // [ROWS]
+    SGX_LDS unsigned long long over[ROWS][WORDS];
+    SGX_LDS unsigned long long kept[WORDS];
     SGX_LDS int hist[256], eqc[256], sel[4];
     SGX_LDS int s_m, s_pos, s_tot;
     unsigned long long *ck = &over[0][0];                        // the unsorted selection lives in the not-yet-used suppression matrix
     const int c = 1 + (int)blockIdx.x, f = (int)blockIdx.y, n = P.n, nc = P.nc;
-    const float *L = loc + (size_t)f * n * 4, *C = conf + (size_t)f * n * nc;
+    const int cls = f * (nc - 1) + (c - 1);
+    if (cont && !cont[cls]) return;                              // continuation launch: this class's first chunk already holds every row that can reach the output
+    const uint32_t lo = cont ? sstar[f] : 0u;                    // candidates below s* cannot reach the output (0: s* undefined, all candidates)
+    const float *L = loc + (size_t)f * n * 4, *CF = conf + (size_t)f * n * nc;
     SGX_THREADS_BEGIN(tid)
     if (tid == 0) { s_m = 0; s_pos = 0; }
     hist[tid] = 0;
@@ -1258,8 +1275,8 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
     SGX_THREADS_BEGIN(tid)
     int cnt = 0;
     for (int i = tid; i < n; i += 256) {
-        const float s = C[(size_t)i * nc + c]; uint32_t b = 0;
-        if (s > P.conf_th) { memcpy(&b, &s, 4); cnt++; }
+        const float s = CF[(size_t)i * nc + c]; uint32_t b = 0;
+        if (s > P.conf_th) { memcpy(&b, &s, 4); if (b >= lo) cnt++; else b = 0; }
         sc[i] = b;
     }
     if (cnt) sgx_atomic_add(&s_m, cnt);
@@ -1267,15 +1284,17 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
     SGX_SYNC();
     const int ncand = s_m;
     if (ncand == 0) {                                            // a class nobody scored above the threshold (the common case with trained weights): nothing to do
-        SGX_THREADS_BEGIN(tid) if (tid == 0) cls_count[f * (nc - 1) + (c - 1)] = 0; SGX_THREADS_END
+        SGX_THREADS_BEGIN(tid) if (tid == 0) { cls_count[cls] = 0; if (C) { cls_ncut[cls] = 0; cls_next[cls] = 0; } } SGX_THREADS_END
         return;
     }
     // The NMS only ever looks at the nms_top_k best candidates (ordered by score, ties by prior index — the stable sort of the list built in index order).
     // Select them first (score of rank nms_top_k by radix select; a tie across the cut takes the lowest prior indices), then order just those.
-    const int m = min(ncand, P.nms_top_k);
+    // The first chunk selects its C candidates and their successor the same way: they are the head of that order whatever the cut.
+    const int K = C ? min(P.nms_top_k, C + 1) : P.nms_top_k;
+    const int m = min(ncand, K), mp = C ? min(m, C) : m;         // selected and ordered; through decode and NMS
     const int CH = (n + 255) / 256;
-    if (ncand > P.nms_top_k) {
-        SGX_TOPK_SELECT32(sc, n, P.nms_top_k, hist, sel)
+    if (ncand > K) {
+        SGX_TOPK_SELECT32(sc, n, K, hist, sel)
         SGX_THREADS_BEGIN(tid)
         const uint32_t S = (uint32_t)sel[0]; int e = 0;
         for (int i = tid * CH; i < min(n, (tid + 1) * CH); i++) e += sc[i] == S ? 1 : 0;
@@ -1286,7 +1305,7 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
         SGX_SYNC();
     }
     SGX_THREADS_BEGIN(tid)
-    const bool cut = ncand > P.nms_top_k;
+    const bool cut = ncand > K;
     const uint32_t S = cut ? (uint32_t)sel[0] : 1u; const int need = cut ? sel[1] : n;
     int run = cut ? eqc[tid] : 0;
     for (int i = tid * CH; i < min(n, (tid + 1) * CH); i++) {
@@ -1299,7 +1318,7 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
     SGX_SYNC();
     SGX_RANK_SORT_DESC(ck, m, keys)
     SGX_THREADS_BEGIN(tid)
-    for (int r = tid; r < m; r += 256) {                        // decode (ncnn detectionoutput.cpp; the host code this replaces used the same expressions)
+    for (int r = tid; r < mp; r += 256) {                       // decode (ncnn detectionoutput.cpp; the host code this replaces used the same expressions)
         const int i = (int)(0xFFFFFFFFu - (uint32_t)keys[r]);
         const float *p = priors + 4 * i, *l = L + 4 * i;
         const float pw = p[2] - p[0], ph = p[3] - p[1], pcx = (p[0] + p[2]) * 0.5f, pcy = (p[1] + p[3]) * 0.5f;
@@ -1308,7 +1327,7 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
         const float x0 = cx - w * 0.5f, y0 = cy - hh * 0.5f, x1 = cx + w * 0.5f, y1 = cy + hh * 0.5f;
         box[r][0] = x0; box[r][1] = y0; box[r][2] = x1; box[r][3] = y1; area[r] = (x1 - x0) * (y1 - y0);
     }
-    for (int w = tid; w < SGX_DO_WORDS; w += 256) kept[w] = 0;
+    for (int w = tid; w < WORDS; w += 256) kept[w] = 0;
     SGX_THREADS_END
     SGX_SYNC();
     // over[r] bit q: candidate r overlaps the higher-ranked candidate q by more than nms_th (only words up to r / 64 are ever read)
@@ -1317,16 +1336,16 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
         const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
         // lanes along the higher-ranked candidates q = 64 w + lane: their boxes do not depend on the row, so every wave keeps them in registers; a row then
         // costs one broadcast read of its own box and one independent compare chain + ballot per word
-        float qb[SGX_DO_WORDS][4], qa[SGX_DO_WORDS];
+        float qb[WORDS][4], qa[WORDS];
 #pragma unroll
-        for (int w = 0; w < SGX_DO_WORDS; w++) {
-            const int qq = min(64 * w + lane, m - 1);
+        for (int w = 0; w < WORDS; w++) {
+            const int qq = min(64 * w + lane, mp - 1);
             qb[w][0] = box[qq][0]; qb[w][1] = box[qq][1]; qb[w][2] = box[qq][2]; qb[w][3] = box[qq][3]; qa[w] = area[qq];
         }
-        for (int r = wave; r < m; r += 4) {
+        for (int r = wave; r < mp; r += 4) {
             const float a0 = box[r][0], a1 = box[r][1], a2 = box[r][2], a3 = box[r][3], aa = area[r];
 #pragma unroll
-            for (int w = 0; w < SGX_DO_WORDS; w++) {
+            for (int w = 0; w < WORDS; w++) {
                 if (64 * w < r) {                                // uniform
                     const bool o = 64 * w + lane < r && sgx_iou_gt(a0, a1, a2, a3, aa, qb[w][0], qb[w][1], qb[w][2], qb[w][3], qa[w], P.nms_th);
                     const unsigned long long bits = __ballot(o);
@@ -1338,8 +1357,8 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
     }
 #else
     SGX_THREADS_BEGIN(tid)
-    for (int t = tid; t < m * SGX_DO_WORDS; t += 256) {
-        const int r = t / SGX_DO_WORDS, w = t - r * SGX_DO_WORDS;
+    for (int t = tid; t < mp * WORDS; t += 256) {
+        const int r = t / WORDS, w = t - r * WORDS;
         unsigned long long bits = 0;
         for (int b = 0; b < 64; b++) {
             const int q = 64 * w + b;
@@ -1356,11 +1375,11 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
 #ifndef SGX_EMU
     if ((int)threadIdx.x < 64) {                                 // wave 0: row bits and the "suppressed by an earlier word" flag sit in lanes, the chain runs on the scalar unit
         const int lane = (int)threadIdx.x;
-        for (int ch = 0; ch * 64 < m; ch++) {
+        for (int ch = 0; ch * 64 < mp; ch++) {
             const int r = 64 * ch + lane;
-            bool s = r >= m;
-            if (r < m) for (int w = 0; w < ch; w++) s = s || (over[r][w] & kept[w]) != 0;
-            const unsigned long long row = r < m ? over[r][ch] : 0ull;
+            bool s = r >= mp;
+            if (r < mp) for (int w = 0; w < ch; w++) s = s || (over[r][w] & kept[w]) != 0;
+            const unsigned long long row = r < mp ? over[r][ch] : 0ull;
             const unsigned long long blocked = __ballot(s);
             const uint32_t rlo = (uint32_t)row, rhi = (uint32_t)(row >> 32);
             unsigned long long word = 0;
@@ -1376,11 +1395,11 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
     }
     SGX_SYNC();
 #else
-    for (int ch = 0; ch * 64 < m; ch++) {
+    for (int ch = 0; ch * 64 < mp; ch++) {
         SGX_THREADS_BEGIN(tid)
         if (tid == 0) {
             unsigned long long word = 0;
-            for (int t = 0; t < 64 && 64 * ch + t < m; t++) {
+            for (int t = 0; t < 64 && 64 * ch + t < mp; t++) {
                 const int r = 64 * ch + t; bool s = false;
                 for (int w = 0; w < ch; w++) s = s || (over[r][w] & kept[w]) != 0;
                 if (!s && (over[r][ch] & word) == 0) word |= 1ull << t;
@@ -1391,8 +1410,8 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
     }
 #endif
     SGX_THREADS_BEGIN(tid)
-    float *out = cls_rows + ((size_t)f * (nc - 1) + (c - 1)) * SGX_DO_TOPK * 6;
-    for (int r = tid; r < m; r += 256) {
+    float *out = cls_rows + (size_t)cls * SGX_DO_TOPK * 6;
+    for (int r = tid; r < mp; r += 256) {
         const int w = r >> 6, b = r & 63;
         if (!((kept[w] >> b) & 1)) continue;
         int pos = SGX_POPCLL(kept[w] & ((1ull << b) - 1));
@@ -1401,7 +1420,44 @@ SGX_KERNEL(256) k_det_class_nms(SgxDetOut P, const float *loc, const float *conf
         float *o = out + 6 * pos;
         o[0] = (float)c; o[1] = s; o[2] = box[r][0]; o[3] = box[r][1]; o[4] = box[r][2]; o[5] = box[r][3];
     }
-    if (tid == 0) { int tot = 0; for (int q = 0; q < SGX_DO_WORDS; q++) tot += SGX_POPCLL(kept[q]); cls_count[f * (nc - 1) + (c - 1)] = tot; }
+    if (tid == 0) {
+        int tot = 0; for (int q = 0; q < WORDS; q++) tot += SGX_POPCLL(kept[q]); cls_count[cls] = tot;
+        if (C) { cls_ncut[cls] = min(ncand, P.nms_top_k); cls_next[cls] = m > C ? (uint32_t)(keys[C] >> 32) : 0u; }
+    }
+    SGX_THREADS_END
+}
+
+// The cut of the two-stage DetectionOutput (grid: frames, 256 threads): s* = the keep_top_k-th largest score among the frame's first-chunk rows (0 = undefined: fewer
+// rows than that) and, per class, whether it continues (see above).  The decision stays in device memory: the continuation launch reads sstar / cont.
+SGX_KERNEL(256) k_det_cut(SgxDetOut P, const float *cls_rows, const int *cls_count, const int *cls_ncut, const uint32_t *cls_next, uint32_t *sstar, int *cont)
+{
+    SGX_LDS uint32_t sc[SGX_DO_MERGE];
+    SGX_LDS int off[64];
+    SGX_LDS int hist[256], sel[4];
+    SGX_LDS int s_total;
+    const int f = (int)blockIdx.x, ncl = P.nc - 1;
+    SGX_THREADS_BEGIN(tid)
+    if (tid == 0) { int run = 0; for (int q = 0; q < ncl; q++) { off[q] = run; run += cls_count[f * ncl + q]; } off[ncl] = run; s_total = run; }
+    hist[tid] = 0;
+    SGX_THREADS_END
+    SGX_SYNC();
+    const int total = s_total;
+    const bool defined = P.keep_top_k >= 1 && total >= P.keep_top_k;
+    if (defined) {
+        SGX_THREADS_BEGIN(tid)
+        for (int q = 0; q < ncl; q++) {
+            const int cnt = off[q + 1] - off[q];
+            const float *rows = cls_rows + ((size_t)f * ncl + q) * SGX_DO_TOPK * 6;
+            for (int p = tid; p < cnt; p += 256) { const float s = rows[6 * p + 1]; uint32_t b; memcpy(&b, &s, 4); sc[off[q] + p] = b; }
+        }
+        SGX_THREADS_END
+        SGX_SYNC();
+        SGX_TOPK_SELECT32(sc, total, P.keep_top_k, hist, sel)
+    }
+    SGX_THREADS_BEGIN(tid)
+    const uint32_t S = defined ? (uint32_t)sel[0] : 0u;
+    if (tid == 0) sstar[f] = S;
+    if (tid < ncl) cont[f * ncl + tid] = (cls_ncut[f * ncl + tid] > SGX_DO_FIRST && (S == 0 || cls_next[f * ncl + tid] >= S)) ? 1 : 0;
     SGX_THREADS_END
 }
 

@@ -11,7 +11,7 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 PARAM = os.path.join(ROOT, 'tests', 'golden', 'mobilenetv3_ssdlite_voc.param')
 lib = sg_slam_amd.load()
-layers = synth.parse_ncnn_param(PARAM); _, blob = synth.synth_ncnn_weights(layers, seed=7, person_logit=-4.0)
+layers = synth.parse_ncnn_param(PARAM); _, blob = synth.synth_ncnn_weights(layers, seed=7, person_logit=-0.5)
 det = Detector2D(0.9, 0.01, param_text=open(PARAM).read(), bin_bytes=blob, max_batch=B, lib=lib)
 gen = synth.LayeredStream(seed=1234)
 frames = np.stack([gen.frame(7 * s)[0] for s in range(min(B, 16))])
