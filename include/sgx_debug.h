@@ -30,6 +30,7 @@ int sgx_ba_debug_set_jobs(int host);               /* test tap: 1 = the bundle a
 int sgx_ba_debug_set_solver(int mode);             /* test / tuning tap: reduced-camera-system solver of the bundle adjustments: -1 default (SGX_BA_SOLVER or auto), 0 auto, 1 dense blocked Cholesky, 2 envelope solver */
 int sgx_det_debug_read_blob(sgx_det *h, const char *blob_name, int image, float *dst, int cap, int *n);
 int sgx_flow_debug_read_level(sgx_flow *h, int slot, int frame, int level, uint8_t *img);     /* test tap: pyramid level, w*h tight */
+int sgx_flow_debug_read_slot(sgx_flow *h, int slot, int frame, int level, uint8_t *img, int32_t *pitch);   /* test tap: the level as stored (pitch*h, padding columns included); img == NULL: pitch only */
 int sgx_flow_debug_level_size(const sgx_flow *h, int level, int32_t *w, int32_t *hgt);
 /* test tap: one step of the device EPnP (sg_slam_amd/csrc/sgx_pnp_kernels.h) on caller values, on one lane: which = 0 runs gauss_newton (five steps, no update on a singular
  * qr_solve) on betas in place; which = 1..3 writes find_betas_approx_<which> (IEEE division by betas[0]).  L = 6 x 10, rho = 6, betas = 4 doubles (host arrays). */

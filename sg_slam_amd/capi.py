@@ -90,7 +90,7 @@ TAP_SYMBOLS = [
     'sgx_orb_debug_run_octree', 'sgx_pose_opt_debug_set_threads', 'sgx_ba_debug_set_solver', 'sgx_ba_debug_set_jobs', 'sgx_ba_debug_set_init', 'sgx_ba_debug_last_plan', 'sgx_det_debug_read_blob',
     'sgx_det_debug_detection_output', 'sgx_det_debug_continued', 'sgx_debug_flow_affine_batch_dev', 'sgx_det_debug_set_fusion', 'sgx_det_debug_set_legacy_kernels',
     'sgx_det_debug_set_block_fusion', 'sgx_det_debug_set_irb', 'sgx_det_debug_set_gemm', 'sgx_det_debug_time_ops', 'sgx_det_debug_run_step', 'sgx_flow_debug_read_level',
-    'sgx_flow_debug_level_size', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas',
+    'sgx_flow_debug_level_size', 'sgx_flow_debug_read_slot', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas',
 ]
 
 
@@ -251,6 +251,7 @@ class SgxLib:
             d.sgx_debug_corun_bf16.argtypes = [C.c_int, C.c_int, C.c_int, vp]
             d.sgx_pnp_debug_betas.argtypes = [C.c_int, vp, vp, vp]
             d.sgx_flow_debug_level_size.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+            d.sgx_flow_debug_read_slot.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int32)]
 
     def tap(self, name):
         """a test / tuning tap entry (include/sgx_debug.h); the product library has none"""

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <new>
+#include <algorithm>
 #include <vector>
 
 
@@ -46,7 +47,7 @@ extern "C" int sgx_flow_create(const sgx_flow_config *cfg, sgx_flow **out)
         if (nw <= cfg->win_size || nh <= cfg->win_size) break;
         w = nw; hh = nh;
     }
-    g.img_stride = (io + 15u + 64u) & ~15u;       // + slack: the 4-dword row loads of k_lk_pyrdown may run a few bytes past a level's last row
+    g.img_stride = (io + 15u + 64u) & ~15u;       // + slack: the 16-byte row loads of the pyrDown tasks may run a few bytes past a level's last row
     for (int s = 0; s < 2; s++)
         if (hipMalloc((void **)&h->img[s], (size_t)g.img_stride * cfg->max_batch) != hipSuccess) { sgx_flow_destroy(h); return SGX_ERR_NOMEM; }
     *out = h;
@@ -70,10 +71,21 @@ static int build_pyramid(sgx_flow *h, int slot, const uint8_t *d_gray, int pitch
     uint8_t *base = h->img[slot];
     sgx_prof_begin(SGX_K_LK_PYR, st);
     auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); };      // ceil(2^32 / d): exact quotients for the kernels' index split (index < 2^21, d < 2^11)
-    SGX_LAUNCH(k_lk_copy, dim3(((g.pitch[0] >> 2) * g.h[0] + 255) / 256, batch), dim3(256), st, d_gray, g.w[0], g.h[0], pitch, base, g.pitch[0], g.img_stride, magic(g.pitch[0] >> 2));
-    for (int l = 1; l < g.nl; l++)
-        SGX_LAUNCH(k_lk_pyrdown, dim3(((g.pitch[l] >> 2) * g.h[l] + 255) / 256, batch), dim3(256), st, (const uint8_t *)(base + g.ioff[l - 1]), g.w[l - 1], g.h[l - 1], g.pitch[l - 1],
-                   g.img_stride, base + g.ioff[l], g.w[l], g.h[l], g.pitch[l], g.img_stride, magic(g.pitch[l] >> 2));
+    if (g.nl == 1)
+        SGX_LAUNCH(k_lk_copy, dim3(((g.pitch[0] >> 2) * g.h[0] + 255) / 256, batch), dim3(256), st, d_gray, g.w[0], g.h[0], pitch, base, g.pitch[0], g.img_stride, magic(g.pitch[0] >> 2));
+    else {
+        // per destination level: groups 1 .. gf-1 of a row load their 16 source bytes 2X-4 .. 2X+11 inside the source pitch and need no reflection (taps 2X-2 .. 2X+8); group 0 and groups gf .. are border groups
+        SgxLkDiv dv;
+        memset(&dv, 0, sizeof dv);
+        for (int l = 1; l < g.nl; l++) {
+            const int sw = g.w[l - 1], sp = l == 1 ? pitch : g.pitch[l - 1], qw = g.pitch[l] >> 2;
+            const int gf = std::max(1, std::min(qw, std::min((sw - 9) >> 3, (sp - 12) >> 3) + 1));
+            dv.gf[l] = gf; dv.plain[l] = magic(gf - 1); dv.border[l] = magic(qw - gf + 1);
+        }
+        const int nrp = (g.h[1] + 1) >> 1, plain_blocks = ((dv.gf[1] - 1) * nrp + 255) / 256, border_blocks = (((g.pitch[1] >> 2) - dv.gf[1] + 1) * nrp + 255) / 256;
+        SGX_LAUNCH(k_lk_pyr01, dim3(plain_blocks + border_blocks, batch), dim3(256), st, d_gray, pitch, g, base, dv, plain_blocks);
+        if (g.nl > 2) SGX_LAUNCH(k_lk_pyrtail, dim3(batch), dim3(1024), st, g, base, dv);
+    }
     sgx_prof_end(SGX_K_LK_PYR, st);
     SGX_CHECK_HIP(hipGetLastError());
     return SGX_OK;
@@ -153,6 +165,16 @@ SGX_TAP int sgx_flow_debug_read_level(sgx_flow *h, int slot, int frame, int leve
         SGX_CHECK_HIP(hipMemcpy(t.data(), h->img[slot] + (size_t)frame * g.img_stride + g.ioff[level], t.size(), hipMemcpyDeviceToHost));
         for (int y = 0; y < g.h[level]; y++) memcpy(img + (size_t)y * g.w[level], &t[(size_t)y * g.pitch[level]], (size_t)g.w[level]);
     }
+    return SGX_OK;
+}
+SGX_TAP int sgx_flow_debug_read_slot(sgx_flow *h, int slot, int frame, int level, uint8_t *img /* pitch*h: the level as stored, padding columns included */, int32_t *pitch)
+{
+    if (!h || slot < 0 || slot > 1 || frame < 0 || frame >= h->cfg.max_batch || level < 0 || level >= h->g.nl || !pitch) return SGX_ERR_INVALID;
+    const SgxLkGeom &g = h->g;
+    *pitch = g.pitch[level];
+    if (!img) return SGX_OK;
+    SGX_CHECK_HIP(hipDeviceSynchronize());
+    SGX_CHECK_HIP(hipMemcpy(img, h->img[slot] + (size_t)frame * g.img_stride + g.ioff[level], (size_t)g.pitch[level] * g.h[level], hipMemcpyDeviceToHost));
     return SGX_OK;
 }
 SGX_TAP int sgx_flow_debug_level_size(const sgx_flow *h, int level, int32_t *w, int32_t *hh)

@@ -6,8 +6,10 @@
 // OpenCV 3.4 algorithms as restated in oracle/flow_oracle.c (lkpyramid.cpp, pyramids.cpp, fundam.cpp, ptsetreg.cpp).
 //
 // Kernels
-//   k_lk_copy       level 0 of the LK pyramid = a pitch-aligned copy of the frame (it becomes "imGrayPre" of the next call)
-//   k_lk_pyrdown    cv::pyrDown: 5x5 [1 4 6 4 1]^2, (sum + 128) >> 8, REFLECT_101 — four outputs per thread from aligned dwords
+//   k_lk_pyr01      levels 0 and 1 of the LK pyramid from one read of the frame: level 0 = a pitch-aligned copy (it becomes "imGrayPre" of the next call), level 1 = cv::pyrDown
+//                   (5x5 [1 4 6 4 1]^2, (sum + 128) >> 8, REFLECT_101), 2 x 4 outputs per thread from 16-byte row loads and byte dot products
+//   k_lk_pyrtail    levels 2 .. : one workgroup per frame, level after level
+//   k_lk_copy       level 0 alone, for a pyramid that has no other level
 //   k_lk_track      LKTrackerInvoker: ONE WAVE PER KEYPOINT, all pyramid levels chained in one launch.  Lane (r, s) owns window row r and the seven
 //                   columns 7s..7s+6 (63 lanes = 21 x 21 samples): its window intensities and Scharr derivatives (calcSharrDeriv evaluated on the fly from an
 //                   LDS-staged patch of the image — no derivative plane ever exists in HBM) stay in registers for all iterations; the
@@ -23,6 +25,7 @@
 #pragma once
 #include "sgx_rt.h"
 #include "sgx_block.h"
+#include "sgx_lane.h"
 #include <float.h>
 #include <math.h>
 
@@ -75,41 +78,99 @@ SGX_KERNEL(256) k_lk_copy(const uint8_t *src, int w, int h, int spitch, uint8_t 
     SGX_THREADS_END
 }
 
-// cv::pyrDown (pyramids.cpp, pyrDown_<FixPtCast<uchar,8>>): dst(x, y) = (sum_{i,j} k_i k_j src(2x-2+i, 2y-2+j) + 128) >> 8, k = [1 4 6 4 1]
-SGX_KERNEL(256) k_lk_pyrdown(const uint8_t *src, int sw, int sh, int spitch, unsigned sstride, uint8_t *dst, int dw, int dh, int dpitch, unsigned dstride, unsigned qw_magic)
+// cv::pyrDown (pyramids.cpp, pyrDown_<FixPtCast<uchar,8>>): dst(x, y) = (sum_{i,j} k_i k_j src(2x-2+i, 2y-2+j) + 128) >> 8, k = [1 4 6 4 1], REFLECT_101.
+// One thread = one TASK = two output rows (2 yp, 2 yp + 1) of one dword group (columns X .. X+3, X = 4 G).  It reads the seven source rows 4 yp - 2 .. 4 yp + 4 (three of them serve
+// both output rows), of each the four dwords at columns 2X-4 .. 2X+11, and forms the 5 x 5 sum in exact integers with two v_dot4_u32_u8 per (source row, output row, output):
+// the byte window at columns 2X-2+2o .. +3 against (1 4 6 4) k_row, and the fifth tap as byte 0 of the window two further along.  (sum + 128) >> 8 is the only rounding.
+// Only HOW the four dwords arrive differs at the border (FAST = false): eleven byte loads at reflected columns instead of one 16-byte load.  The tasks of a level are numbered
+// with all plain groups first (groups 1 .. gf-1 of every row pair) and the border groups (0 and gf ..) after them, so a wave runs one of the two forms, never both.
+// With COPY the task also writes the source bytes it owns (rows 4 yp .. 4 yp + 3, columns 2X .. 2X+7) to the pitch-aligned level-0 slot: the frame is read from HBM once.
+// Every reflection is a single one: a level is only halved while both sides of the result exceed the window, so a source side is >= 43 and no index is more than 12 outside.
+SGX_DEV int sgx_lk_reflect(int p, int len) { p = p < 0 ? -p : p; return p >= len ? 2 * len - 2 - p : p; }
+template <bool COPY, bool FAST>
+SGX_DEV void sgx_lk_down_task(const uint8_t *S, int sw, int sh, int spitch, uint8_t *D, int dh, int dpitch, uint8_t *C, int cpitch, int yp, int G)
+{
+    const int X = 4 * G, y0 = 2 * yp;
+    uint32_t acc[2][4];
+#pragma unroll
+    for (int o = 0; o < 4; o++) acc[0][o] = acc[1][o] = 128u;
+    int xi[11]; uint32_t keep[2] = { ~0u, ~0u };                    /* border form: reflected columns 2X-2 .. 2X+8; the bytes of the copy that are image (the padding of the last group is 0) */
+    if (!FAST) {
+#pragma unroll
+        for (int i = 0; i < 11; i++) xi[i] = sgx_lk_reflect(2 * X - 2 + i, sw);
+#pragma unroll
+        for (int i = 0; i < 8; i++) if (2 * X + i >= sw) keep[i >> 2] &= ~(0xFFu << (8 * (i & 3)));
+    }
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        const int r = 2 * y0 - 2 + k;
+        const uint8_t *row = S + (size_t)sgx_lk_reflect(r, sh) * spitch;      /* the second output row may not exist (odd height): its extra rows still reflect into the image */
+        uint32_t v[4];
+        if (FAST) __builtin_memcpy(v, row + 2 * X - 4, 16);
+        else {
+            v[0] = ((uint32_t)row[xi[0]] << 16) | ((uint32_t)row[xi[1]] << 24); v[3] = row[xi[10]];      /* the bytes no tap uses stay 0 */
+#pragma unroll
+            for (int j = 1; j < 3; j++) v[j] = (uint32_t)row[xi[4 * j - 2]] | ((uint32_t)row[xi[4 * j - 1]] << 8) | ((uint32_t)row[xi[4 * j]] << 16) | ((uint32_t)row[xi[4 * j + 1]] << 24);
+        }
+        const uint32_t W[6] = { sgx_alignbyte(v[1], v[0], 2), v[1], sgx_alignbyte(v[2], v[1], 2), v[2], sgx_alignbyte(v[3], v[2], 2), v[3] };      /* windows at columns 2X-2, 2X, .. 2X+8 */
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int kk = k - 2 * j;                               /* this source row's tap index for output row y0 + j */
+            if (kk < 0 || kk > 4) continue;
+            const uint32_t wk = kk == 0 || kk == 4 ? 1u : kk == 2 ? 6u : 4u;
+#pragma unroll
+            for (int o = 0; o < 4; o++) acc[j][o] = sgx_udot4(W[o + 2], wk, sgx_udot4(W[o], wk * 0x04060401u, acc[j][o]));
+        }
+        if (COPY && k >= 2 && k <= 5 && r < sh) {
+            uint8_t *c = C + (size_t)r * cpitch + 2 * X;
+            if (FAST || 2 * X < cpitch) *(uint32_t *)c = v[1] & keep[0];
+            if (FAST || 2 * X + 4 < cpitch) *(uint32_t *)(c + 4) = v[2] & keep[1];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; j++)                                      /* sum + 128 < 2^16: byte 1 of each accumulator is the pixel; columns >= dw of the last group are padding */
+        if (y0 + j < dh) *(uint32_t *)(D + (size_t)(y0 + j) * dpitch + X) = sgx_perm(acc[j][1], acc[j][0], 0x0c0c0501u) | sgx_perm(acc[j][3], acc[j][2], 0x05010c0cu);
+}
+/* task q of a level: [0, nplain) = plain groups 1 .. gf-1, [nplain, ntasks) = border groups 0, gf .. qw-1; m_plain / m_border = ceil(2^32 / groups of that kind) (sgx_lk_udiv) */
+template <bool COPY>
+SGX_DEV void sgx_lk_down(int q, int nplain, int ntasks, int gf, int qw, unsigned m_plain, unsigned m_border,
+                         const uint8_t *S, int sw, int sh, int spitch, uint8_t *D, int dh, int dpitch, uint8_t *C, int cpitch)
+{
+    if (q < nplain) {
+        const int yp = (int)sgx_lk_udiv((unsigned)q, m_plain), G = 1 + q - yp * (gf - 1);
+        sgx_lk_down_task<COPY, true>(S, sw, sh, spitch, D, dh, dpitch, C, cpitch, yp, G);
+    } else if (q < ntasks) {
+        const int e = q - nplain, nb = qw - gf + 1, yp = (int)sgx_lk_udiv((unsigned)e, m_border), i = e - yp * nb;
+        sgx_lk_down_task<COPY, false>(S, sw, sh, spitch, D, dh, dpitch, C, cpitch, yp, i == 0 ? 0 : gf + i - 1);
+    }
+}
+struct SgxLkDiv { int gf[SGX_LK_MAXL]; unsigned plain[SGX_LK_MAXL], border[SGX_LK_MAXL]; };      /* per destination level, from the host: first border group on the right, the two reciprocals of sgx_lk_down */
+
+// levels 0 and 1 of every frame from one read of the frame.  grid = (plain blocks + border blocks, frames): a block holds tasks of one kind
+SGX_KERNEL(256) k_lk_pyr01(const uint8_t *src, int spitch, SgxLkGeom g, uint8_t *base, SgxLkDiv dv, int plain_blocks)
 {
     SGX_THREADS_BEGIN(tid)
-    const int f = (int)blockIdx.y, qw = dpitch >> 2, q = (int)blockIdx.x * 256 + tid;
-    if (q < qw * dh) {
-        const int y = (int)sgx_lk_udiv((unsigned)q, qw_magic), X = (q - y * qw) * 4;
-        const uint8_t *S = src + (size_t)f * sstride;
-        int acc[4] = { 0, 0, 0, 0 };
-        const bool fast = X >= 2 && 2 * X + 11 < spitch && 2 * X + 8 <= sw - 1;
-#pragma unroll
-        for (int k = 0; k < 5; k++) {
-            const int wk = k == 0 || k == 4 ? 1 : k == 2 ? 6 : 4;
-            const uint8_t *row = S + (size_t)sgx_reflect101(2 * y - 2 + k, sh) * spitch;
-            int p[11];
-            if (fast) {
-                const uint32_t *r4 = (const uint32_t *)(row + 2 * X - 4);
-                const uint32_t a = r4[0], b = r4[1], c = r4[2], d = r4[3];
-                p[0] = (a >> 16) & 255; p[1] = a >> 24;
-                p[2] = b & 255; p[3] = (b >> 8) & 255; p[4] = (b >> 16) & 255; p[5] = b >> 24;
-                p[6] = c & 255; p[7] = (c >> 8) & 255; p[8] = (c >> 16) & 255; p[9] = c >> 24;
-                p[10] = d & 255;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 11; i++) p[i] = row[sgx_reflect101(2 * X - 2 + i, sw)];
-            }
-#pragma unroll
-            for (int o = 0; o < 4; o++) acc[o] += wk * (p[2 * o + 2] * 6 + (p[2 * o + 1] + p[2 * o + 3]) * 4 + p[2 * o] + p[2 * o + 4]);
-        }
-        uint32_t out = 0;
-#pragma unroll
-        for (int o = 0; o < 4; o++) out |= (uint32_t)((acc[o] + 128) >> 8) << (8 * o);       /* columns >= dw of the last quad are padding */
-        *(uint32_t *)(dst + (size_t)f * dstride + (size_t)y * dpitch + X) = out;
-    }
+    const int f = (int)blockIdx.y, qw = g.pitch[1] >> 2, nrp = (g.h[1] + 1) >> 1, gf = dv.gf[1];
+    const int nplain = (gf - 1) * nrp, ntasks = qw * nrp;
+    const int q = (int)blockIdx.x < plain_blocks ? min((int)blockIdx.x * 256 + tid, nplain) : nplain + ((int)blockIdx.x - plain_blocks) * 256 + tid;      /* a plain block's spare threads get no task */
+    uint8_t *img = base + (size_t)f * g.img_stride;
+    if ((int)blockIdx.x >= plain_blocks || q < nplain)
+        sgx_lk_down<true>(q, nplain, ntasks, gf, qw, dv.plain[1], dv.border[1], src + (size_t)f * g.h[0] * spitch, g.w[0], g.h[0], spitch, img + g.ioff[1], g.h[1], g.pitch[1], img, g.pitch[0]);
     SGX_THREADS_END
+}
+// levels 2 .. of a frame (6 % of the pyramid's pixels) by one workgroup, level after level: it reads back what it wrote itself before the barrier.  grid = frames
+SGX_KERNEL(1024) k_lk_pyrtail(SgxLkGeom g, uint8_t *base, SgxLkDiv dv)
+{
+    uint8_t *img = base + (size_t)blockIdx.x * g.img_stride;
+    for (int l = 2; l < g.nl; l++) {
+        const int qw = g.pitch[l] >> 2, nrp = (g.h[l] + 1) >> 1, gf = dv.gf[l];
+        const int nplain = (gf - 1) * nrp, ntasks = qw * nrp;
+        SGX_THREADS_BEGIN(tid)
+        for (int q = tid; q < ntasks; q += (int)blockDim.x)
+            sgx_lk_down<false>(q, nplain, ntasks, gf, qw, dv.plain[l], dv.border[l], img + g.ioff[l - 1], g.w[l - 1], g.h[l - 1], g.pitch[l - 1], img + g.ioff[l], g.h[l], g.pitch[l], nullptr, 0);
+        SGX_THREADS_END
+        SGX_SYNC();
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -29,7 +29,7 @@ struct sgx_orb {
     SgxXTab *d_xt[SGX_MAX_LEVELS] = {};
     SgxYTab *d_yt[SGX_MAX_LEVELS] = {};
     // fused pyramid (k_pyramid): concatenated tables, per (tile, level) rects
-    SgxXTab *d_xt_all = nullptr; SgxYTab *d_yt_all = nullptr; SgxPyrRect *d_pyr_rects = nullptr; SgxPyrTabs pyr_tabs; int pyr_tiles = 0, pyr_lds = 0;
+    SgxXGroup *d_xg_all = nullptr; SgxYTab *d_yt_all = nullptr; SgxPyrRect *d_pyr_rects = nullptr; SgxPyrTabs pyr_tabs; int pyr_tiles = 0, pyr_lds = 0;
     int *d_umax = nullptr;
     signed char *d_pattern = nullptr;
     // device workspace (sized for cfg.max_batch)
@@ -130,7 +130,7 @@ extern "C" void sgx_orb_destroy(sgx_orb *h)
     (void)hipFree(h->d_cand_count); (void)hipFree(h->d_node_scratch); (void)hipFree(h->d_sel); (void)hipFree(h->d_sel_count); (void)hipFree(h->d_status);
     (void)hipFree(h->d_gray1); (void)hipFree(h->d_kps1); (void)hipFree(h->d_desc1); (void)hipFree(h->d_count1);
     for (int l = 0; l < SGX_MAX_LEVELS; l++) { (void)hipFree(h->d_xt[l]); (void)hipFree(h->d_yt[l]); }
-    (void)hipFree(h->d_xt_all); (void)hipFree(h->d_yt_all); (void)hipFree(h->d_pyr_rects); (void)hipFree(h->d_blur); (void)hipFree(h->d_blur_tiles);
+    (void)hipFree(h->d_xg_all); (void)hipFree(h->d_yt_all); (void)hipFree(h->d_pyr_rects); (void)hipFree(h->d_blur); (void)hipFree(h->d_blur_tiles);
     delete h;
 }
 
@@ -258,16 +258,31 @@ extern "C" int sgx_orb_create(const sgx_orb_config *cfg, sgx_orb **out)
     SGX_CHECK_HIP(hipStreamSynchronize(0));
     if (nl > 1) {   // ---- k_pyramid plan: tiles are a fixed partition of every level; needed regions are propagated from the coarsest level up
         std::vector<std::vector<SgxXTab>> xts(nl); std::vector<std::vector<SgxYTab>> yts(nl);
-        std::vector<SgxXTab> xall; std::vector<SgxYTab> yall;
+        std::vector<SgxXGroup> xall; std::vector<SgxYTab> yall;
+        bool span_ok = true;                                        // every dword group finds its source bytes within SGX_PYR_SPAN of its first one
         memset(&h->pyr_tabs, 0, sizeof h->pyr_tabs);
         for (int l = 1; l < nl; l++) {
             build_resize_tables(g.lv[l - 1].w, g.lv[l - 1].h, g.lv[l].w, g.lv[l].h, xts[l], yts[l]);
             h->pyr_tabs.xoff[l] = (int)xall.size(); h->pyr_tabs.yoff[l] = (int)yall.size();
-            xall.insert(xall.end(), xts[l].begin(), xts[l].end()); yall.insert(yall.end(), yts[l].begin(), yts[l].end());
+            yall.insert(yall.end(), yts[l].begin(), yts[l].end());
+            for (int x4 = 0; x4 < g.lv[l].w; x4 += 4) {                // the x coefficients per dword group, in the form k_pyramid keeps in registers
+                SgxXGroup G; memset(&G, 0, sizeof G);
+                G.sx0 = xts[l][x4].sx;
+                for (int i = 0; i < 4; i++) {
+                    G.sel[i] = 0x0c0c0c0cu;
+                    if (x4 + i >= g.lv[l].w) continue;
+                    const SgxXTab &t = xts[l][x4 + i];
+                    const int o0 = t.sx - G.sx0, o1 = t.sx1 - G.sx0;
+                    if (o0 < 0 || o1 < 0 || o0 >= SGX_PYR_SPAN || o1 >= SGX_PYR_SPAN || t.a0 < 0 || t.a1 < 0) { span_ok = false; continue; }
+                    G.sel[i] = (uint32_t)o0 | 0x0c00u | ((uint32_t)o1 << 16) | 0x0c000000u;
+                    G.a01[i] = (uint32_t)t.a0 | ((uint32_t)t.a1 << 16);
+                }
+                xall.push_back(G);
+            }
         }
         const int T = 32, ntx = (g.lv[nl - 1].w + T - 1) / T, nty = (g.lv[nl - 1].h + T - 1) / T;
         std::vector<SgxPyrRect> rects((size_t)ntx * nty * nl);
-        int max_a = 0, max_b = 0, max_x = 0, max_y = 0;
+        int max_a = 0, max_b = 0, max_y = 0;
         for (int j = 0; j < nty; j++) for (int i = 0; i < ntx; i++) {
             SgxPyrRect *R = &rects[((size_t)j * ntx + i) * nl];
             int nx0 = 0, nx1 = 0, ny0 = 0, ny1 = 0;                 // needed region of level l+1 (exclusive ends)
@@ -286,22 +301,22 @@ extern "C" int sgx_orb_create(const sgx_orb_config *cfg, sgx_orb **out)
                 }
                 ax0 &= ~3; ax1 = (ax1 + 3) & ~3;                     // dword groups; groups past the image width are computed as zeros / read inside the row pitch
                 r.nx0 = (short)ax0; r.ny0 = (short)ay0; r.nw = (short)(ax1 - ax0); r.nh = (short)(ay1 - ay0);
-                const int q = r.nw / 4; r.qmagic = q <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)q - 1) / (unsigned)q); r.pad = 0;
+                const int q = r.nw / 4; r.qmagic = q <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)q - 1) / (unsigned)q); r.pad0 = r.pad1 = 0;
                 const int bytes = (int)r.nw * r.nh;
                 if (l & 1) max_b = std::max(max_b, bytes); else max_a = std::max(max_a, bytes);
                 nx0 = ax0; nx1 = ax1; ny0 = ay0; ny1 = ay1;
             }
-            int xo = 0, yo = 0;
-            for (int l = 1; l < nl; l++) { R[l].xo = xo; R[l].yo = yo; xo += R[l].nw; yo += R[l].nh; }
-            R[0].xo = R[0].yo = 0;
-            max_x = std::max(max_x, xo); max_y = std::max(max_y, yo);
+            int yo = 0;
+            for (int l = 1; l < nl; l++) { R[l].yo = yo; yo += R[l].nh; }
+            R[0].yo = 0;
+            max_y = std::max(max_y, yo);
         }
-        h->pyr_tabs.lds_a = (max_a + 15) & ~15; h->pyr_tabs.lds_b = (max_b + 15) & ~15; h->pyr_tabs.lds_x = max_x * (int)sizeof(SgxXTab);
-        h->pyr_lds = h->pyr_tabs.lds_a + h->pyr_tabs.lds_b + h->pyr_tabs.lds_x + max_y * (int)sizeof(SgxYTab);
+        h->pyr_tabs.lds_a = (max_a + SGX_PYR_SPAN + 15) & ~15; h->pyr_tabs.lds_b = (max_b + SGX_PYR_SPAN + 15) & ~15;      // + the reach of the last row's 8-byte reads
+        h->pyr_lds = h->pyr_tabs.lds_a + h->pyr_tabs.lds_b + max_y * (int)sizeof(SgxYTab);
         h->pyr_tiles = ntx * nty;
-        if (h->pyr_lds > 64 * 1024) h->pyr_tiles = 0;               // geometry too large for the fused plan: per-level k_resize launches
-        SGX_ALLOC(h->d_xt_all, xall.size() * sizeof(SgxXTab)); SGX_ALLOC(h->d_yt_all, yall.size() * sizeof(SgxYTab)); SGX_ALLOC(h->d_pyr_rects, rects.size() * sizeof(SgxPyrRect));
-        SGX_CHECK_HIP(hipMemcpy(h->d_xt_all, xall.data(), xall.size() * sizeof(SgxXTab), hipMemcpyHostToDevice));
+        if (h->pyr_lds > 64 * 1024 || !span_ok) h->pyr_tiles = 0;   // geometry too large (or a scale factor too steep) for the fused plan: per-level k_resize launches
+        SGX_ALLOC(h->d_xg_all, xall.size() * sizeof(SgxXGroup)); SGX_ALLOC(h->d_yt_all, yall.size() * sizeof(SgxYTab)); SGX_ALLOC(h->d_pyr_rects, rects.size() * sizeof(SgxPyrRect));
+        SGX_CHECK_HIP(hipMemcpy(h->d_xg_all, xall.data(), xall.size() * sizeof(SgxXGroup), hipMemcpyHostToDevice));
         SGX_CHECK_HIP(hipMemcpy(h->d_yt_all, yall.data(), yall.size() * sizeof(SgxYTab), hipMemcpyHostToDevice));
         SGX_CHECK_HIP(hipMemcpy(h->d_pyr_rects, rects.data(), rects.size() * sizeof(SgxPyrRect), hipMemcpyHostToDevice));
     }
@@ -359,7 +374,7 @@ extern "C" int sgx_orb_extract_batch_dev(sgx_orb *h, const uint8_t *d_gray, int 
     sgx_prof_begin(SGX_K_RESIZE, stream);
     static const int pyr_threads = sgx_getenv("SGX_TUNE_PYR_THREADS") ? atoi(sgx_getenv("SGX_TUNE_PYR_THREADS")) : 512;      // workgroup size (measured: 0.130 / 0.086 / 0.073 ms per 64 frames at 128 / 256 / 512); env = tuning tap (64..1024)
     if (h->pyr_tiles > 0 && !g_orb_unfused_pyramid)
-        SGX_LAUNCH_DYN(k_pyramid, dim3(h->pyr_tiles, batch), dim3(pyr_threads), h->pyr_lds, stream, g, h->pyr_tabs, d_gray, pitch, h->d_pyr, h->d_xt_all, h->d_yt_all, h->d_pyr_rects);
+        SGX_LAUNCH_DYN(k_pyramid, dim3(h->pyr_tiles, batch), dim3(pyr_threads), h->pyr_lds, stream, g, h->pyr_tabs, d_gray, pitch, h->d_pyr, h->d_xg_all, h->d_yt_all, h->d_pyr_rects);
     else
         for (int l = 1; l < nl; l++) {
             dim3 grid((g.lv[l].w + 255) / 256, (g.lv[l].h + 3) / 4, batch);

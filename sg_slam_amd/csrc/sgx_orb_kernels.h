@@ -10,6 +10,7 @@
 #pragma once
 #include "sgx_rt.h"
 #include "sgx_block.h"
+#include "sgx_lane.h"
 
 #define SGX_MAX_LEVELS 12
 #define SGX_EDGE 19            /* EDGE_THRESHOLD, ORBextractor.cc:75 */
@@ -105,12 +106,18 @@ SGX_KERNEL(256) k_resize(SgxOrbGeom g, int level, const uint8_t *gray, int gray_
 // level l-1 -> l are evaluated tile by tile: a workgroup owns one tile of every level (a fixed 1/(ntx*nty) partition of each
 // level, x boundaries multiples of 4), stages the level-0 footprint of its tiles in LDS, and walks down the chain with two
 // ping-pong LDS buffers, computing at each level the region the next level needs plus the part it owns (a few halo columns /
-// rows are recomputed by neighbouring workgroups), and writing only the owned part to HBM as dwords.  Same tables and integer
+// rows are recomputed by neighbouring workgroups), and writing only the owned part to HBM as dwords.  Same coefficients and integer
 // formula as k_resize, so the pyramid is byte-identical; level l-1 is never re-read from HBM.
 // Host-built per (tile, level) rects: needed region (x0 and width multiples of 4) and owned region.  grid = (ntiles, B).
+// A thread owns one dword group (four columns) of the needed region and walks down a segment of its rows.  What depends on the columns alone stays in registers for the
+// whole walk (SgxXGroup, from the host: where the group's source bytes start, and per column a v_perm selector that widens (S[sx], S[sx+1]) to a 16-bit pair plus the packed
+// (a0, a1)), so a horizontal sample is one 8-byte LDS read per (group, source row) and one v_perm + one v_dot2_u32_u16 (a0 + a1 = 2048, pixels < 256: the sum fits 19 bits) + the
+// >> 4 per column.  Source rows only move down along the walk, and the lower row of one output row is the upper row of the next most of the time: its four samples are kept.
 // ---------------------------------------------------------------------------------------------
-struct SgxPyrRect { short nx0, ny0, nw, nh, ox0, oy0, ox1, oy1; unsigned qmagic; int xo, yo, pad; };   // qmagic = ceil(2^32 / (nw/4)); xo / yo: slots of this level's table slices in LDS
-struct SgxPyrTabs { int xoff[SGX_MAX_LEVELS], yoff[SGX_MAX_LEVELS]; int lds_a, lds_b, lds_x; };        // LDS carve: [buffer A | buffer B | x-table slices | y-table slices]
+struct SgxPyrRect { short nx0, ny0, nw, nh, ox0, oy0, ox1, oy1; unsigned qmagic; int yo, pad0, pad1; };   // qmagic = ceil(2^32 / (nw/4)); yo: slot of this level's y-table slice in LDS
+struct SgxPyrTabs { int xoff[SGX_MAX_LEVELS], yoff[SGX_MAX_LEVELS]; int lds_a, lds_b; };               // xoff: first SgxXGroup of a level; LDS carve: [buffer A | buffer B | y-table slices]
+struct SgxXGroup { int sx0; uint32_t sel[4], a01[4]; };      // columns 4c .. 4c+3 of a level: sx0 = sx of the first one; sel = byte selectors of (sx - sx0, sx1 - sx0) within 8 bytes; a01 = a0 | a1 << 16 (0 for a column past the width: it resizes to 0)
+#define SGX_PYR_SPAN 8         /* source bytes one group may reach from sx0 (host-checked; a 1.2x chain needs 6) */
 
 SGX_DEV unsigned sgx_udiv_magic(unsigned n, unsigned m)
 {
@@ -120,16 +127,24 @@ SGX_DEV unsigned sgx_udiv_magic(unsigned n, unsigned m)
     return m ? (unsigned)(((unsigned long long)n * m) >> 32) : n;
 #endif
 }
+/* the four horizontal samples (h >> 4 of k_resize) of a group on one source row; `row` = the row's byte at sx0 */
+SGX_DEV void sgx_pyr_hrow(const uint8_t *row, const SgxXGroup &xg, uint32_t (&H)[4])
+{
+    uint32_t w[2];
+    __builtin_memcpy(w, row, SGX_PYR_SPAN);
+#pragma unroll
+    for (int i = 0; i < 4; i++) H[i] = sgx_udot2(sgx_perm(w[1], w[0], xg.sel[i]), xg.a01[i], 0u) >> 4;
+}
 
-SGX_KERNEL(1024) k_pyramid(SgxOrbGeom g, SgxPyrTabs tb, const uint8_t *gray, int gray_pitch, uint8_t *pyr, const SgxXTab *xt, const SgxYTab *yt,
+SGX_KERNEL(1024) k_pyramid(SgxOrbGeom g, SgxPyrTabs tb, const uint8_t *gray, int gray_pitch, uint8_t *pyr, const SgxXGroup *xg, const SgxYTab *yt,
                           const SgxPyrRect *rects)
 {
     SGX_DYN_LDS(smem);
     const int tile = (int)blockIdx.x, frame = (int)blockIdx.y, nl = g.nlevels;
     const SgxPyrRect *R = rects + (size_t)tile * nl;
     uint8_t *cur = smem, *nxt = smem + tb.lds_a;
-    SgxXTab *xtl_lds = (SgxXTab *)(smem + tb.lds_a + tb.lds_b); SgxYTab *ytl_lds = (SgxYTab *)(smem + tb.lds_a + tb.lds_b + tb.lds_x);
-    {   // level-0 footprint, dword loads (x0 and width are multiples of 4; the row pitch is a multiple of 4) + this tile's slices of every level's tables
+    SgxYTab *ytl_lds = (SgxYTab *)(smem + tb.lds_a + tb.lds_b);
+    {   // level-0 footprint, dword loads (x0 and width are multiples of 4; the row pitch is a multiple of 4) + this tile's slices of every level's row table
         const SgxPyrRect r0 = R[0];
         const uint8_t *src = gray + (size_t)frame * gray_pitch * g.H;
         const int q = r0.nw >> 2, groups = q * r0.nh;
@@ -140,8 +155,6 @@ SGX_KERNEL(1024) k_pyramid(SgxOrbGeom g, SgxPyrTabs tb, const uint8_t *gray, int
         }
         for (int l = 1; l < nl; l++) {
             const SgxPyrRect r = R[l];
-            const int nx = min((int)r.nw, g.lv[l].w - r.nx0);
-            for (int i = tid; i < nx; i += (int)blockDim.x) xtl_lds[r.xo + i] = xt[tb.xoff[l] + r.nx0 + i];
             for (int i = tid; i < r.nh; i += (int)blockDim.x) ytl_lds[r.yo + i] = yt[tb.yoff[l] + r.ny0 + i];
         }
         SGX_THREADS_END
@@ -149,30 +162,35 @@ SGX_KERNEL(1024) k_pyramid(SgxOrbGeom g, SgxPyrTabs tb, const uint8_t *gray, int
     SGX_SYNC();
     for (int l = 1; l < nl; l++) {
         const SgxPyrRect rp = R[l - 1], r = R[l];
-        const int W = g.lv[l].w, dstride = g.lv[l].stride;
+        const int dstride = g.lv[l].stride;
         uint8_t *dst = pyr + (size_t)frame * g.pyr_pitch + g.lv[l].off;
-        const SgxXTab *xtl = xtl_lds + r.xo - r.nx0; const SgxYTab *ytl = ytl_lds + r.yo - r.ny0;
-        const int q = r.nw >> 2, groups = q * r.nh;
+        const SgxYTab *ytl = ytl_lds + r.yo;
+        const SgxXGroup *xgl = xg + tb.xoff[l] + (r.nx0 >> 2);
+        const int q = r.nw >> 2, nseg = q > 0 ? max(1, min((int)r.nh, (int)blockDim.x / q)) : 1, rs = (r.nh + nseg - 1) / nseg, tasks = q * nseg;      /* row segments: as many as give every thread a task */
         SGX_THREADS_BEGIN(tid)
-        for (int idx = tid; idx < groups; idx += (int)blockDim.x) {
-            const int y = (int)sgx_udiv_magic((unsigned)idx, r.qmagic), x4 = (idx - y * q) * 4;
-            const int gy = r.ny0 + y, gx4 = r.nx0 + x4;
-            const SgxYTab ty = ytl[gy];
-            const uint8_t *r0 = cur + (ty.sy0 - rp.ny0) * rp.nw - rp.nx0, *r1 = cur + (ty.sy1 - rp.ny0) * rp.nw - rp.nx0;
-            uint32_t out = 0;
+        for (int t = tid; t < tasks; t += (int)blockDim.x) {
+            const int sg = (int)sgx_udiv_magic((unsigned)t, r.qmagic), c = t - sg * q, x4 = 4 * c, gx4 = r.nx0 + x4;
+            const SgxXGroup xc = xgl[c];
+            const uint8_t *col = cur + (xc.sx0 - rp.nx0);
+            const bool own_x = gx4 >= r.ox0 && gx4 < r.ox1;
+            uint32_t HA[4], HB[4] = { 0, 0, 0, 0 }; int rowB = -1;                   /* HB = the samples of source row rowB (relative to the staged region) */
+            const int y1 = min(sg * rs + rs, (int)r.nh);
+            for (int y = sg * rs; y < y1; y++) {
+                const int gy = r.ny0 + y;
+                const SgxYTab ty = ytl[y];
+                const int s0 = ty.sy0 - rp.ny0, s1 = ty.sy1 - rp.ny0;
+                if (s0 == rowB) { HA[0] = HB[0]; HA[1] = HB[1]; HA[2] = HB[2]; HA[3] = HB[3]; }
+                else sgx_pyr_hrow(col + s0 * rp.nw, xc, HA);
+                if (s1 == s0) { HB[0] = HA[0]; HB[1] = HA[1]; HB[2] = HA[2]; HB[3] = HA[3]; }
+                else sgx_pyr_hrow(col + s1 * rp.nw, xc, HB);
+                rowB = s1;
+                uint32_t v[4];
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int x = gx4 + i;
-                if (x < W) {
-                    const SgxXTab tx = xtl[x];
-                    const int h0 = r0[tx.sx] * tx.a0 + r0[tx.sx1] * tx.a1;
-                    const int h1 = r1[tx.sx] * tx.a0 + r1[tx.sx1] * tx.a1;
-                    const int v = (((ty.b0 * (h0 >> 4)) >> 16) + ((ty.b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-                    out |= (uint32_t)(v & 255) << (8 * i);
-                }
+                for (int i = 0; i < 4; i++) v[i] = ((sgx_umul24((uint32_t)ty.b0, HA[i]) >> 16) + (sgx_umul24((uint32_t)ty.b1, HB[i]) >> 16) + 2u) >> 2;      /* <= 255: b0 + b1 = 2048, H <= 255 * 128 */
+                const uint32_t out = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+                *(uint32_t *)(nxt + y * r.nw + x4) = out;
+                if (own_x && gy >= r.oy0 && gy < r.oy1) *(uint32_t *)(dst + (size_t)gy * dstride + gx4) = out;   // stride is a multiple of 64: in-bounds, aligned
             }
-            *(uint32_t *)(nxt + y * r.nw + x4) = out;
-            if (gy >= r.oy0 && gy < r.oy1 && gx4 >= r.ox0 && gx4 < r.ox1) *(uint32_t *)(dst + (size_t)gy * dstride + gx4) = out;   // stride is a multiple of 64: in-bounds, aligned
         }
         SGX_THREADS_END
         SGX_SYNC();
@@ -192,36 +210,6 @@ SGX_KERNEL(1024) k_pyramid(SgxOrbGeom g, SgxPyrTabs tb, const uint8_t *gray, int
 // with x,y relative to the (16,16) border origin (ORBextractor.cc:823-824); k_octree does not
 // depend on their order.
 // ---------------------------------------------------------------------------------------------
-// ((hi:lo) >> 8*sh) as 32 bits (v_alignbyte_b32)
-SGX_DEV uint32_t sgx_alignbyte(uint32_t hi, uint32_t lo, int sh)
-{
-#ifndef SGX_EMU
-    return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)sh);
-#else
-    return (uint32_t)((((unsigned long long)hi << 32) | lo) >> (8 * sh));
-#endif
-}
-
-// exact integer dot products of packed operands: 4 x u8 (v_dot4_u32_u8) and 2 x u16 (v_dot2_u32_u16), 32-bit accumulate, no clamp
-SGX_DEV uint32_t sgx_udot4(uint32_t a, uint32_t b, uint32_t c)
-{
-#ifndef SGX_EMU
-    return __builtin_amdgcn_udot4(a, b, c, false);
-#else
-    for (int i = 0; i < 4; i++) c += ((a >> (8 * i)) & 255u) * ((b >> (8 * i)) & 255u);
-    return c;
-#endif
-}
-SGX_DEV uint32_t sgx_udot2(uint32_t a, uint32_t b, uint32_t c)
-{
-#ifndef SGX_EMU
-    typedef unsigned short sgx_us2 __attribute__((ext_vector_type(2)));
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(sgx_us2, a), __builtin_bit_cast(sgx_us2, b), c, false);
-#else
-    return c + (a & 0xFFFFu) * (b & 0xFFFFu) + (a >> 16) * (b >> 16);
-#endif
-}
-
 // packed 2 x u16 helpers (v_pk_sub_u16 clamp / v_pk_min_u16 on the device)
 #ifndef SGX_EMU
 typedef unsigned short sgx_u16x2 __attribute__((ext_vector_type(2)));

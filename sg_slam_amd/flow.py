@@ -59,6 +59,15 @@ class OpticalFlowLK:
         self.lib.check(self.lib.tap('sgx_flow_debug_read_level')(self.h, slot, frame, level, _vp(img)), 'flow debug_read_level')
         return img
 
+    def debug_slot(self, slot, frame, level):
+        """the level as the pyramid slot stores it: (h, pitch) bytes, the padding columns of the last dword group included"""
+        w, h, p = C.c_int32(), C.c_int32(), C.c_int32()
+        self.lib.check(self.lib.tap('sgx_flow_debug_level_size')(self.h, level, C.byref(w), C.byref(h)))
+        self.lib.check(self.lib.tap('sgx_flow_debug_read_slot')(self.h, slot, frame, level, None, C.byref(p)))
+        img = np.zeros((h.value, p.value), np.uint8)
+        self.lib.check(self.lib.tap('sgx_flow_debug_read_slot')(self.h, slot, frame, level, _vp(img), C.byref(p)), 'flow debug_read_slot')
+        return img
+
 
 def find_fundamental_mat(pts1, pts2, threshold=1.0, confidence=0.99, lib=None):
     """cv::findFundamentalMat(pts1, pts2, FM_RANSAC, threshold, confidence): (ok, F[3,3] f64, stats[4])."""

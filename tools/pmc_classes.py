@@ -5,7 +5,7 @@ CLASS = [('k_pyramid', 'pyramid_resize'), ('k_resize', 'pyramid_resize'), ('k_gr
          ('k_match_project_local', 'match_project_local'), ('k_pose_opt', 'pose_opt'), ('k_unproject', 'unproject'),
          ('k_make_map_points', 'map_point_glue'), ('k_merge_matches', 'map_point_glue'), ('k_gather_xw', 'map_point_glue'),
          ('k_dynamic_mask', 'dynamic_mask'), ('k_compact_keys', 'dynamic_mask'),
-         ('k_lk_copy', 'lk_pyramid'), ('k_lk_pyrdown', 'lk_pyramid'), ('k_lk_track', 'lk_track'), ('k_fm_ransac', 'fm_ransac'),
+         ('k_lk_copy', 'lk_pyramid'), ('k_lk_pyr', 'lk_pyramid'), ('k_lk_track', 'lk_track'), ('k_fm_ransac', 'fm_ransac'),
          ('k_det_preprocess', 'det_forward'), ('k_stem_pre', 'det_forward'), ('k_conv_pw', 'det_forward'), ('k_conv_kxk', 'det_forward'), ('k_conv_dw', 'det_forward'), ('k_conv_stem', 'det_forward'), ('k_binary', 'det_forward'), ('k_unary', 'det_forward'),
          ('k_copy_into', 'det_forward'), ('k_permute_hwc_into', 'det_forward'), ('k_softmax_rows', 'det_forward'), ('k_fused_block', 'det_forward'),
          ('k_irb', 'det_forward'), ('k_se_gate', 'det_forward'),
@@ -71,7 +71,7 @@ def unclassified_share(rows, name_key='Name', dur_key='TotalDurationNs'):
 
 # dispatches per bench step of the kernels that run more than once per step (everything else: once); used to find out in how many of the profiled steps a class
 # ran at all — the first step of a run has no previous frame, so the tracking-stage kernels (LK, RANSAC, matchers, pose optimisation ...) run in one step fewer
-DISPATCHES_PER_STEP = {'k_pose_opt': 2, 'k_merge_matches': 2, 'k_lk_pyrdown': 3, 'k_resize': 7}
+DISPATCHES_PER_STEP = {'k_pose_opt': 2, 'k_merge_matches': 2, 'k_resize': 7}
 
 
 def steps_ran(dispatch_counts):
