@@ -311,6 +311,63 @@ int sgx_pnp_batch_iterate_dev(sgx_pnp_batch *t, int n_iterations, const int32_t 
                               uint8_t *inliers_dev, void *stream);
 void sgx_pnp_batch_destroy(sgx_pnp_batch *t);
 
+/* ---- Detector3D (src/sg-slam/include/Detector3D.h, src/sg-slam/src/Detector3D.cc) and ObjectDatabase (src/sg-slam/src/ObjectDatabase.cc) ---------------------------
+ * Detector3D::DetectOne (:41-168) for one Object2D of Detector2D (mvObjects2D), as PointCloudMapping::generatePointCloud calls it for every keyframe
+ * (PointcloudMapping.cc:145-151, :189-190): the crop of the box's central 60 % (rows / columns (size_t)h * 0.2 .. (size_t)h * 0.8, depth inside
+ * [camera_valid_depth_min, camera_valid_depth_max] and not NaN), the world points of the crop (camera point in float as PointcloudMapping.cc:176-178 writes it, Twc in
+ * double as pcl::transformPointCloud applies it), pcl::StatisticalOutlierRemoval (mean_k, stddev_mul), pcl::EuclideanClusterExtraction (tolerance, min / max size)
+ * and the selection loop (:101-140: compute3DCentroid, the world-z test against camera_valid_depth_min, GetProjectedROI, GetSimilarity, the `>` / `else if >`
+ * bookkeeping and the DetectSimilarCompareRatio test).  PCL and FLANN are restated from their published algorithms (tests/obj3d_ref.py), unpinned.
+ * Defined cases: fewer than mean_k + 1 crop points, or no cluster chosen: found = 0 (the reference reads past the neighbour list / returns an object with an
+ * uninitialised centroid); equal-size clusters are ordered by their smallest point; powf(x, 2) = x * x; a NaN similarity never wins.  voxel_leaf_size is read and
+ * unused, as in the reference (its voxel filter is commented out).
+ * SGX_ERR_INVALID: mean_k < 1, depth bounds or tolerance that are not finite, a rect that is not inside the image (x, y, w, h >= 0, x + w <= width, y + h <= height),
+ * a crop of more than max_crop_points cells.  Twc must be finite.
+ * The diagnostics are part of the record: crop_points (points of the crop), kept_points (after the filter), components (of the kept points, any size), clusters
+ * (min <= size <= max), best_cluster_size / best_similar1 / best_similar2 / best_roi (x, y, width, height) of the selection loop (also when the ratio test then
+ * rejects; -1 / 0 when no cluster was chosen), larger_window_points (points whose neighbour search needed more than the first pixel window: an implementation
+ * figure, equal between the device and the emulator).  centroid and size are 0 when found == 0. */
+typedef struct sgx_obj3d_params {
+    double sor_stddev_mul;                                  /* Detector3D.Sor_StddevMulThresh */
+    int32_t sor_mean_k;                                     /* Detector3D.Sor_MeanK */
+    int32_t cluster_min_size, cluster_max_size;             /* Detector3D.EuclideanClusterMinSize / MaxSize */
+    float voxel_leaf_size;                                  /* Detector3D.Voxel_LeafSize: unused */
+    float cluster_tolerance;                                /* Detector3D.EuclideanClusterTolerance */
+    float similar_compare_ratio;                            /* Detector3D.DetectSimilarCompareRatio */
+    float camera_valid_depth_min, camera_valid_depth_max;   /* PointCloudMapping.camera_valid_depth_Min / Max */
+} sgx_obj3d_params;
+typedef struct sgx_obj3d_job { int32_t image, class_id; float prob, x, y, w, h; } sgx_obj3d_job;        /* image index in the batch; Object2D id, prob, rect */
+typedef struct sgx_obj3d_result {
+    int32_t found, class_id; float prob, centroid[3], size[3];
+    int32_t crop_points, kept_points, components, clusters, best_cluster_size, larger_window_points;
+    float best_similar1, best_similar2, best_roi[4];
+} sgx_obj3d_result;
+typedef struct sgx_obj3d sgx_obj3d;
+/* width x height images, at most max_images images and max_jobs jobs per batch, at most max_crop_points cells per crop; 0 = the largest crop there is:
+ * Detector2D only clamps its boxes to the image (Detector2D.cc:63-71), so a box can be the whole image and its crop the central 60 % of it, 384 x 288 = 110 592 cells
+ * of a 640 x 480 image.  The workspace is 32 bytes per cell and job, plus 64 bytes per job for every max_crop_points / max(cluster_min_size, 1) cells: the surviving
+ * clusters are ranked pairwise by one workgroup, so a cluster_min_size of a few points on a large crop costs (cells / min_size)^2 reads there. */
+int sgx_obj3d_create(int width, int height, int max_images, int max_jobs, int max_crop_points, const sgx_obj3d_params *params, sgx_obj3d **out);
+void sgx_obj3d_destroy(sgx_obj3d *h);
+/* n_jobs jobs over n_images depth images (device, float metres as mImDep, n_images x height x pitch floats), cam4 = fx, fy, cx, cy (host), twc_dev = n_images x 16
+ * doubles (device, Twc row-major), jobs (host; copied before the call returns), results_dev = n_jobs records (device).  One launch sequence, asynchronous on
+ * `stream`.  A handle serves one batch at a time: batches of one handle must be ordered by their streams. */
+int sgx_obj3d_detect_batch_dev(sgx_obj3d *h, const float *depth_dev, int pitch, int n_images, const float *cam4, const double *twc_dev, const sgx_obj3d_job *jobs,
+                               int n_jobs, sgx_obj3d_result *results_dev, void *stream);
+/* one job (image 0) from host memory: depth = height x width floats, twc = 16 doubles.  Synchronous. */
+int sgx_obj3d_detect(sgx_obj3d *h, const float *depth, const float *cam4, const double *twc, const sgx_obj3d_job *job, sgx_obj3d_result *result);
+/* ObjectDatabase::addObject (:44-112), host code: objects of the same class (the reference compares object_name = class_names[class_id]) within mvSizes[class_id]
+ * (0.6; bottle 5: 0.2, chair 9: 1.0, tvmonitor 20: 0.5) of the nearest one, searched from center_distance = 100, are merged by a mean of prob, centroid and size;
+ * otherwise the object is appended with object_id = ++DataBaseSize.  class_id outside 0..20 is SGX_ERR_INVALID (the reference indexes mvSizes with it).
+ * *object_id = the id appended or merged into, *merged = 1 when merged (either may be NULL). */
+typedef struct sgx_semantic_object { int32_t class_id, object_id; float prob, centroid[3], size[3]; } sgx_semantic_object;
+typedef struct sgx_objdb sgx_objdb;
+int sgx_objdb_create(sgx_objdb **out);
+void sgx_objdb_destroy(sgx_objdb *db);
+int sgx_objdb_add(sgx_objdb *db, const sgx_semantic_object *obj, int32_t *object_id, int32_t *merged);
+int sgx_objdb_size(const sgx_objdb *db);                                      /* number of objects (mvSemanticObject.size()) */
+int sgx_objdb_get(const sgx_objdb *db, int index, sgx_semantic_object *out);  /* mvSemanticObject[index] */
+
 /* ---- ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (src/sg-slam/include/ORBVocabulary.h:31-32) ----------------------------------------------
  * The bag-of-words transform behind Frame::ComputeBoW (src/sg-slam/src/Frame.cc:422-429) and KeyFrame::ComputeBoW (src/sg-slam/src/KeyFrame.cc:60-69):
  *     mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4)          src/sg-slam/Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1139-1206

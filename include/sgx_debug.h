@@ -35,6 +35,9 @@ int sgx_flow_debug_level_size(const sgx_flow *h, int level, int32_t *w, int32_t 
 /* test tap: one step of the device EPnP (sg_slam_amd/csrc/sgx_pnp_kernels.h) on caller values, on one lane: which = 0 runs gauss_newton (five steps, no update on a singular
  * qr_solve) on betas in place; which = 1..3 writes find_betas_approx_<which> (IEEE division by betas[0]).  L = 6 x 10, rho = 6, betas = 4 doubles (host arrays). */
 int sgx_pnp_debug_betas(int which, const double *L, const double *rho, double *betas);
+/* test tap: the per-point state of job `job` of the handle's last batch, over its *n crop points in the reference's order (ascending flat index): kept[i] = the
+ * outlier filter kept point i, labels[i] = the smallest point of its component (-1 when the point was removed).  Synchronises; SGX_ERR_OVERFLOW when *n > cap. */
+int sgx_obj3d_debug_read(sgx_obj3d *h, int job, uint8_t *kept, int32_t *labels, int cap, int *n);
 int sgx_debug_corun_bf16(int blocks, int iters, int launches, void *stream);      /* test tap: `launches` launches of a kernel that only issues bf16 matrix products, asynchronous on `stream` (co-runner of the packed-fp32 regression test) */
 /* test tap: DetectionOutput + detect() filtering alone on caller-supplied head outputs (host arrays: loc batch x num_priors x 4, conf batch x num_priors x num_class) */
 int sgx_det_debug_detection_output(sgx_det *h, const float *loc, const float *conf, int batch, sgx_det_result *results);

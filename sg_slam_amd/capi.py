@@ -53,6 +53,25 @@ class TrackerConfig(C.Structure):
                 ('local_map', C.c_int32), ('dynamic_mask', C.c_int32), ('max_boxes', C.c_int32), ('pipelined', C.c_int32)]
 
 
+class Obj3dParams(C.Structure):
+    _fields_ = [('sor_stddev_mul', C.c_double), ('sor_mean_k', C.c_int32), ('cluster_min_size', C.c_int32), ('cluster_max_size', C.c_int32),
+                ('voxel_leaf_size', C.c_float), ('cluster_tolerance', C.c_float), ('similar_compare_ratio', C.c_float),
+                ('camera_valid_depth_min', C.c_float), ('camera_valid_depth_max', C.c_float)]
+
+
+class Obj3dJob(C.Structure):
+    _fields_ = [('image', C.c_int32), ('class_id', C.c_int32)] + [(k, C.c_float) for k in ('prob', 'x', 'y', 'w', 'h')]
+
+
+OBJ3D_RESULT_DTYPE = np.dtype([('found', 'i4'), ('class_id', 'i4'), ('prob', 'f4'), ('centroid', 'f4', 3), ('size', 'f4', 3), ('crop_points', 'i4'), ('kept_points', 'i4'),
+                               ('components', 'i4'), ('clusters', 'i4'), ('best_cluster_size', 'i4'), ('larger_window_points', 'i4'), ('best_similar1', 'f4'),
+                               ('best_similar2', 'f4'), ('best_roi', 'f4', 4)])   # sgx_obj3d_result, 84 B
+
+
+class SemanticObjectRecord(C.Structure):
+    _fields_ = [('class_id', C.c_int32), ('object_id', C.c_int32), ('prob', C.c_float), ('centroid', C.c_float * 3), ('size', C.c_float * 3)]
+
+
 class OrbConfig(C.Structure):
     _fields_ = [('nfeatures', C.c_int32), ('scale_factor', C.c_float), ('nlevels', C.c_int32),
                 ('ini_th_fast', C.c_int32), ('min_th_fast', C.c_int32), ('width', C.c_int32),
@@ -83,6 +102,8 @@ SYMBOLS = [
     'sgx_optimize_essential_graph', 'sgx_correct_map_points', 'sgx_undistort_points', 'sgx_frame_undistort_stereo_rgbd_batch_dev', 'sgx_frame_image_bounds',
     'sgx_tracker_set_distortion', 'sgx_tracker_frame_keys_un_dev', 'sgx_pnp_solver_create', 'sgx_pnp_solver_set_ransac_parameters', 'sgx_pnp_solver_iterate',
     'sgx_pnp_solver_get_estimate', 'sgx_pnp_solver_destroy', 'sgx_pnp_batch_create', 'sgx_pnp_batch_set_dev', 'sgx_pnp_batch_iterate_dev', 'sgx_pnp_batch_destroy',
+    'sgx_obj3d_create', 'sgx_obj3d_destroy', 'sgx_obj3d_detect_batch_dev', 'sgx_obj3d_detect', 'sgx_objdb_create', 'sgx_objdb_destroy', 'sgx_objdb_add', 'sgx_objdb_size',
+    'sgx_objdb_get',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -90,7 +111,7 @@ TAP_SYMBOLS = [
     'sgx_orb_debug_run_octree', 'sgx_pose_opt_debug_set_threads', 'sgx_ba_debug_set_solver', 'sgx_ba_debug_set_jobs', 'sgx_ba_debug_set_init', 'sgx_ba_debug_last_plan', 'sgx_det_debug_read_blob',
     'sgx_det_debug_detection_output', 'sgx_det_debug_continued', 'sgx_debug_flow_affine_batch_dev', 'sgx_det_debug_set_fusion', 'sgx_det_debug_set_legacy_kernels',
     'sgx_det_debug_set_block_fusion', 'sgx_det_debug_set_irb', 'sgx_det_debug_set_gemm', 'sgx_det_debug_time_ops', 'sgx_det_debug_run_step', 'sgx_flow_debug_read_level',
-    'sgx_flow_debug_level_size', 'sgx_flow_debug_read_slot', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas',
+    'sgx_flow_debug_level_size', 'sgx_flow_debug_read_slot', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas', 'sgx_obj3d_debug_read',
 ]
 
 
@@ -211,6 +232,15 @@ class SgxLib:
         d.sgx_pnp_batch_set_dev.argtypes = [vp, C.c_int] + [vp] * 8
         d.sgx_pnp_batch_iterate_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
         d.sgx_pnp_batch_destroy.argtypes = [vp]; d.sgx_pnp_batch_destroy.restype = None
+        d.sgx_obj3d_create.argtypes = [C.c_int] * 5 + [C.POINTER(Obj3dParams), C.POINTER(vp)]
+        d.sgx_obj3d_destroy.argtypes = [vp]; d.sgx_obj3d_destroy.restype = None
+        d.sgx_obj3d_detect_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+        d.sgx_obj3d_detect.argtypes = [vp, vp, vp, vp, C.POINTER(Obj3dJob), vp]
+        d.sgx_objdb_create.argtypes = [C.POINTER(vp)]
+        d.sgx_objdb_destroy.argtypes = [vp]; d.sgx_objdb_destroy.restype = None
+        d.sgx_objdb_add.argtypes = [vp, C.POINTER(SemanticObjectRecord), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        d.sgx_objdb_size.argtypes = [vp]
+        d.sgx_objdb_get.argtypes = [vp, C.c_int, C.POINTER(SemanticObjectRecord)]
         d.sgx_mappoint_update_normal_and_depth.argtypes = [C.c_int] + [vp] * 6 + [C.c_int, vp, vp, vp]
         d.sgx_mappoint_distinctive_descriptors.argtypes = [C.c_int, vp, vp, vp, vp]
         d.sgx_triangulate_new_map_points.argtypes = [C.c_int, vp] + [C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 5 + [vp, vp, vp, C.c_int, vp, vp, vp]
@@ -250,6 +280,7 @@ class SgxLib:
             d.sgx_flow_debug_read_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
             d.sgx_debug_corun_bf16.argtypes = [C.c_int, C.c_int, C.c_int, vp]
             d.sgx_pnp_debug_betas.argtypes = [C.c_int, vp, vp, vp]
+            d.sgx_obj3d_debug_read.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int)]
             d.sgx_flow_debug_level_size.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
             d.sgx_flow_debug_read_slot.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int32)]
 

@@ -516,6 +516,72 @@ public:
     sgx_det *handle() { return h_; }
 };
 
+// ObjectDatabase (ObjectDatabase.h:12-45) and Detector3D (Detector3D.h:46-76): the semantic objects of a keyframe from its Object2D boxes, its depth image and its pose
+struct SemanticObject { float centroid[3], size[3]; float prob; int class_id, object_id; };      // object_name = class_names[class_id]
+class ObjectDatabase {
+public:
+    ObjectDatabase() { check(sgx_objdb_create(&h_), "sgx_objdb_create"); }
+    ~ObjectDatabase() { if (h_) sgx_objdb_destroy(h_); }
+    ObjectDatabase(const ObjectDatabase &) = delete; ObjectDatabase &operator=(const ObjectDatabase &) = delete;
+    void addObject(SemanticObject &cluster)                          // void addObject(SemanticObject& cluster): cluster.object_id is set when the object is appended
+    {
+        sgx_semantic_object o; o.class_id = cluster.class_id; o.object_id = 0; o.prob = cluster.prob;
+        for (int i = 0; i < 3; i++) { o.centroid[i] = cluster.centroid[i]; o.size[i] = cluster.size[i]; }
+        int32_t id = 0, merged = 0;
+        check(sgx_objdb_add(h_, &o, &id, &merged), "sgx_objdb_add");
+        if (!merged) cluster.object_id = id;
+    }
+    int getDataBaseSize() const { return sgx_objdb_size(h_); }
+    SemanticObject getObjectByID(int objectID) const                 // mvSemanticObject[objectID - 1]
+    {
+        sgx_semantic_object o; check(sgx_objdb_get(h_, objectID - 1, &o), "sgx_objdb_get");
+        SemanticObject s; s.class_id = o.class_id; s.object_id = o.object_id; s.prob = o.prob;
+        for (int i = 0; i < 3; i++) { s.centroid[i] = o.centroid[i]; s.size[i] = o.size[i]; }
+        return s;
+    }
+private:
+    sgx_objdb *h_ = nullptr;
+};
+
+class Detector3D {
+public:
+    // the reference's constructor arguments (Detector3D.h:49-51) plus what it reads from its members and the keyframe: the valid depth range, the image size and
+    // the camera (fx, fy, cx, cy)
+    Detector3D(int Detect3D_Sor_MeanK_, double Detect3D_Sor_StddevMulThresh_, float Detect3D_Voxel_LeafSize_, float EuclideanClusterTolerance_, int EuclideanClusterMinSize_,
+               int EuclideanClusterMaxSize_, float DetectSimilarCompareRatio_, float camera_valid_depth_Min_, float camera_valid_depth_Max_, int width, int height,
+               const float cam[4], int max_crop_points = 0 /* the crop of a box that is the whole image */)
+    {
+        sgx_obj3d_params p; p.sor_stddev_mul = Detect3D_Sor_StddevMulThresh_; p.sor_mean_k = Detect3D_Sor_MeanK_; p.cluster_min_size = EuclideanClusterMinSize_;
+        p.cluster_max_size = EuclideanClusterMaxSize_; p.voxel_leaf_size = Detect3D_Voxel_LeafSize_; p.cluster_tolerance = EuclideanClusterTolerance_;
+        p.similar_compare_ratio = DetectSimilarCompareRatio_; p.camera_valid_depth_min = camera_valid_depth_Min_; p.camera_valid_depth_max = camera_valid_depth_Max_;
+        for (int i = 0; i < 4; i++) cam_[i] = cam[i];
+        check(sgx_obj3d_create(width, height, 1, 1, max_crop_points, &p, &h_), "sgx_obj3d_create");
+        mpObjectDatabase = new ObjectDatabase;
+    }
+    ~Detector3D() { delete mpObjectDatabase; if (h_) sgx_obj3d_destroy(h_); }
+    Detector3D(const Detector3D &) = delete; Detector3D &operator=(const Detector3D &) = delete;
+    // void Detect(vector<Object2D>&, cv::Mat &depth, PointCloud::ConstPtr): depth = mImDep (float metres, height x width, tight), Twc = the 4 x 4 double matrix the
+    // caller passes to pcl::transformPointCloud (row-major) in place of the transformed cloud
+    void Detect(const std::vector<Object2D> &vobject2d, const float *depth, const double Twc[16])
+    {
+        for (const Object2D &o : vobject2d) { SemanticObject s; if (DetectOne(o, s, depth, Twc)) mpObjectDatabase->addObject(s); }
+    }
+    bool DetectOne(const Object2D &object2d, SemanticObject &semantic_object, const float *depth, const double Twc[16], sgx_obj3d_result *record = nullptr)
+    {
+        sgx_obj3d_job j; j.image = 0; j.class_id = object2d.id; j.prob = object2d.prob; j.x = object2d.x; j.y = object2d.y; j.w = object2d.w; j.h = object2d.h;
+        sgx_obj3d_result r;
+        check(sgx_obj3d_detect(h_, depth, cam_, Twc, &j, &r), "sgx_obj3d_detect");
+        if (record) *record = r;
+        if (!r.found) return false;
+        semantic_object.class_id = r.class_id; semantic_object.prob = r.prob; semantic_object.object_id = 0;
+        for (int i = 0; i < 3; i++) { semantic_object.centroid[i] = r.centroid[i]; semantic_object.size[i] = r.size[i]; }
+        return true;
+    }
+    ObjectDatabase *mpObjectDatabase = nullptr;
+private:
+    sgx_obj3d *h_ = nullptr; float cam_[4];
+};
+
 // cv::undistortPoints(points, out, K, D, noArray(), K) as Frame::UndistortKeyPoints calls it (Frame.cc:654-684), and Frame::ComputeImageBounds (:686-714);
 // K4 = fx, fy, cx, cy, distCoef = 4, 5 or 8 coefficients.  Points are (x, y) pairs.
 inline std::vector<float> UndistortPoints(const std::vector<float> &points, const float K4[4], const std::vector<float> &distCoef)

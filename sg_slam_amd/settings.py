@@ -39,3 +39,16 @@ def load(path):
                nlevels=int(kv.get('ORBextractor.nLevels', 8)), ini_th_fast=int(kv.get('ORBextractor.iniThFAST', 20)), min_th_fast=int(kv.get('ORBextractor.minThFAST', 7)))
     return dict(cam=cam, dist=np.array(dist, 'f4'), rgb=int(float(kv.get('Camera.RGB', 1))), orb=orb,
                 width=int(float(kv.get('Camera.width', 640))), height=int(float(kv.get('Camera.height', 480))))
+
+
+def load_mapping(path):
+    """The semantic-mapping parameters System::System reads (System.cc:92 ff.): Detector3D.* as the Detector3D constructor takes them (Sor_MeanK,
+    Sor_StddevMulThresh (double), Voxel_LeafSize, EuclideanClusterTolerance, EuclideanClusterMinSize, EuclideanClusterMaxSize, DetectSimilarCompareRatio) and
+    PointCloudMapping.camera_valid_depth_Min / Max.  A missing key raises KeyError: the reference has no defaults for them."""
+    kv = parse(path)
+    d = lambda k: float(kv['Detector3D.' + k])
+    return dict(Sor_MeanK=int(d('Sor_MeanK')), Sor_StddevMulThresh=d('Sor_StddevMulThresh'), Voxel_LeafSize=_f32(kv, 'Detector3D.Voxel_LeafSize'),
+                EuclideanClusterTolerance=float(np.float32(d('EuclideanClusterTolerance'))), EuclideanClusterMinSize=int(d('EuclideanClusterMinSize')),
+                EuclideanClusterMaxSize=int(d('EuclideanClusterMaxSize')), DetectSimilarCompareRatio=float(np.float32(d('DetectSimilarCompareRatio'))),
+                camera_valid_depth_Min=float(np.float32(float(kv['PointCloudMapping.camera_valid_depth_Min']))),
+                camera_valid_depth_Max=float(np.float32(float(kv['PointCloudMapping.camera_valid_depth_Max']))))
