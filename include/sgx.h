@@ -311,6 +311,47 @@ int sgx_pnp_batch_iterate_dev(sgx_pnp_batch *t, int n_iterations, const int32_t 
                               uint8_t *inliers_dev, void *stream);
 void sgx_pnp_batch_destroy(sgx_pnp_batch *t);
 
+/* ---- Initializer (src/sg-slam/include/Initializer.h, src/sg-slam/src/Initializer.cc), the two-view initialisation of Tracking::MonocularInitialization
+ * (Tracking.cc:605-671): the consumer of sgx_match_search_for_initialization ---------------------------------------------------------------------------------------
+ * create = the constructor (:33-42): keys1_un = ReferenceFrame.mvKeysUn, cam4 = fx, fy, cx, cy, sigma and iterations as Tracking passes them (1.0, 200).
+ * initialize = Initialize (:44-121) with keys2_un = CurrentFrame.mvKeysUn and matches12 = vMatches12 (n1 entries, -1 = unmatched): the 8-point sets of every
+ * iteration, FindHomography and FindFundamental over all of them (Normalize runs over ALL keys of each frame; the float score is summed in match order; the first
+ * strictly greater score wins), RH = SH / (SH + SF), ReconstructH (RH > 0.40; `minParallax` 1.0, `minTriangulated` 50) or ReconstructF with CheckRT / Triangulate,
+ * all on the device (sg_slam_amd/csrc/sgx_init_kernels.h states the OpenCV algebra it restates).
+ * Outputs: *ok = the return value; R21 (3 x 3 row-major), t21; p3d (n1 x 3) and triangulated (n1) = vP3D and vbTriangulated, indexed by the keypoint index of frame 1
+ * (a point that passes every gate of CheckRT is written even when its cosParallax >= 0.99998 leaves triangulated 0); all zero when *ok = 0.  inliers (n1) =
+ * vbMatchesInliers of the chosen model, scattered to the keypoint index of frame 1.  report (optional): the scores, the chosen model (0 H, 1 F), N, the inlier counts
+ * of both winners, the number of motion hypotheses checked (8, 4, or 0 when ReconstructH left at `d1/d2 < 1.00001 || d2/d3 < 1.00001`), per hypothesis nGood, the
+ * selected cosine vCosParallax[min(50, nGood - 1)] and its parallax in degrees, best_hyp = bestSolutionIdx (H) or the first hypothesis with maxGood (F; -1 = none),
+ * and the winning H21 / F21 (zero when no hypothesis scored above 0).
+ * parallax = (float)(acos((double)cos) * 180 / CV_PI) is evaluated on the host; the device applies the two gates as cosine thresholds derived from that expression.
+ * Defined where the reference is undefined: fewer than 8 matches -> *ok = 0 and no random number is consumed; no hypothesis of the chosen model scored above 0 (the
+ * reference decomposes an empty matrix) -> *ok = 0; a hypothesis whose score is NaN never wins; matches12[i] >= n2 counts as unmatched.
+ * Random numbers: the reference draws 8 x iterations values from the process-global rand() after SeedRandOnce(0).  rand_draws = those raw rand() values, or NULL: the
+ * object's replica of glibc's rand(), srand(rand_seed) at creation, continuing across calls (seed 0 = a process's first Initialize).  Synchronous, host pointers. */
+typedef struct sgx_initializer sgx_initializer;
+typedef struct sgx_init_report {
+    float SH, SF, RH; int32_t model /* 0 H, 1 F */, n_matches, n_inliers_h, n_inliers_f, n_hyp /* 8, 4 or 0 */, best_hyp;
+    int32_t n_good[8]; float cos_parallax[8], parallax[8]; float H21[9], F21[9];
+} sgx_init_report;
+int sgx_initializer_create(int n1, const sgx_keypoint *keys1_un, const float *cam4, float sigma, int iterations, unsigned rand_seed, sgx_initializer **out);
+int sgx_initializer_initialize(sgx_initializer *s, int n2, const sgx_keypoint *keys2_un, const int32_t *matches12, const int32_t *rand_draws, float *R21, float *t21,
+                               float *p3d, uint8_t *triangulated, uint8_t *inliers, int32_t *ok, sgx_init_report *report);
+void sgx_initializer_destroy(sgx_initializer *s);
+/* Batch: B independent frame pairs, one launch sequence for all of them.  create: max_keys = capacity of each concatenated key array, max_matches = capacity of the
+ * concatenated matches12 array (one entry per key of frame 1), iterations = mMaxIterations of every pair.  run_dev: offsets1 / offsets2 (host, B + 1) delimit pair b's
+ * keys in keys1_dev / keys2_dev; matches12_dev, p3d_dev, triangulated_dev and inliers_dev follow offsets1; cam (host, B x 4), sigma (host, B); rand_seeds (host, B)
+ * re-seeds the pairs' rand() replicas before this run (NULL: they continue; all start as srand(0)); rand_draws_dev (device, optional) = pair b's 8 x iterations raw
+ * rand() values at b * draw_stride.  Outputs on the device: R21_dev (B x 9), t21_dev (B x 3), ok_dev (B), report_dev (B; its parallax[] stays 0: the host
+ * evaluates acos).  Asynchronous on `stream`. */
+typedef struct sgx_init_batch sgx_init_batch;
+int sgx_init_batch_create(int max_pairs, int max_keys, int max_matches, int iterations, sgx_init_batch **out);
+int sgx_init_batch_run_dev(sgx_init_batch *t, int B, const int32_t *offsets1, const sgx_keypoint *keys1_dev, const int32_t *matches12_dev, const int32_t *offsets2,
+                           const sgx_keypoint *keys2_dev, const float *cam, const float *sigma, const uint32_t *rand_seeds, const int32_t *rand_draws_dev, int draw_stride,
+                           float *R21_dev, float *t21_dev, float *p3d_dev, uint8_t *triangulated_dev, uint8_t *inliers_dev, int32_t *ok_dev, sgx_init_report *report_dev,
+                           void *stream);
+void sgx_init_batch_destroy(sgx_init_batch *t);
+
 /* ---- Detector3D (src/sg-slam/include/Detector3D.h, src/sg-slam/src/Detector3D.cc) and ObjectDatabase (src/sg-slam/src/ObjectDatabase.cc) ---------------------------
  * Detector3D::DetectOne (:41-168) for one Object2D of Detector2D (mvObjects2D), as PointCloudMapping::generatePointCloud calls it for every keyframe
  * (PointcloudMapping.cc:145-151, :189-190): the crop of the box's central 60 % (rows / columns (size_t)h * 0.2 .. (size_t)h * 0.8, depth inside

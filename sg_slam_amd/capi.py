@@ -72,6 +72,12 @@ class SemanticObjectRecord(C.Structure):
     _fields_ = [('class_id', C.c_int32), ('object_id', C.c_int32), ('prob', C.c_float), ('centroid', C.c_float * 3), ('size', C.c_float * 3)]
 
 
+class InitReport(C.Structure):
+    _fields_ = [('SH', C.c_float), ('SF', C.c_float), ('RH', C.c_float), ('model', C.c_int32), ('n_matches', C.c_int32), ('n_inliers_h', C.c_int32),
+                ('n_inliers_f', C.c_int32), ('n_hyp', C.c_int32), ('best_hyp', C.c_int32), ('n_good', C.c_int32 * 8), ('cos_parallax', C.c_float * 8),
+                ('parallax', C.c_float * 8), ('H21', C.c_float * 9), ('F21', C.c_float * 9)]
+
+
 class OrbConfig(C.Structure):
     _fields_ = [('nfeatures', C.c_int32), ('scale_factor', C.c_float), ('nlevels', C.c_int32),
                 ('ini_th_fast', C.c_int32), ('min_th_fast', C.c_int32), ('width', C.c_int32),
@@ -103,7 +109,8 @@ SYMBOLS = [
     'sgx_tracker_set_distortion', 'sgx_tracker_frame_keys_un_dev', 'sgx_pnp_solver_create', 'sgx_pnp_solver_set_ransac_parameters', 'sgx_pnp_solver_iterate',
     'sgx_pnp_solver_get_estimate', 'sgx_pnp_solver_destroy', 'sgx_pnp_batch_create', 'sgx_pnp_batch_set_dev', 'sgx_pnp_batch_iterate_dev', 'sgx_pnp_batch_destroy',
     'sgx_obj3d_create', 'sgx_obj3d_destroy', 'sgx_obj3d_detect_batch_dev', 'sgx_obj3d_detect', 'sgx_objdb_create', 'sgx_objdb_destroy', 'sgx_objdb_add', 'sgx_objdb_size',
-    'sgx_objdb_get',
+    'sgx_objdb_get', 'sgx_initializer_create', 'sgx_initializer_initialize', 'sgx_initializer_destroy', 'sgx_init_batch_create', 'sgx_init_batch_run_dev',
+    'sgx_init_batch_destroy',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -232,6 +239,12 @@ class SgxLib:
         d.sgx_pnp_batch_set_dev.argtypes = [vp, C.c_int] + [vp] * 8
         d.sgx_pnp_batch_iterate_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
         d.sgx_pnp_batch_destroy.argtypes = [vp]; d.sgx_pnp_batch_destroy.restype = None
+        d.sgx_initializer_create.argtypes = [C.c_int, vp, vp, C.c_float, C.c_int, C.c_uint, vp]
+        d.sgx_initializer_initialize.argtypes = [vp, C.c_int] + [vp] * 10
+        d.sgx_initializer_destroy.argtypes = [vp]; d.sgx_initializer_destroy.restype = None
+        d.sgx_init_batch_create.argtypes = [C.c_int] * 4 + [vp]
+        d.sgx_init_batch_run_dev.argtypes = [vp, C.c_int] + [vp] * 9 + [C.c_int] + [vp] * 8
+        d.sgx_init_batch_destroy.argtypes = [vp]; d.sgx_init_batch_destroy.restype = None
         d.sgx_obj3d_create.argtypes = [C.c_int] * 5 + [C.POINTER(Obj3dParams), C.POINTER(vp)]
         d.sgx_obj3d_destroy.argtypes = [vp]; d.sgx_obj3d_destroy.restype = None
         d.sgx_obj3d_detect_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]

@@ -351,6 +351,35 @@ private:
     sgx_pnp_solver *h_ = nullptr; std::vector<int32_t> idx_; int N_, n_;
 };
 
+// Initializer (src/sg-slam/include/Initializer.h:32-96), the two-view initialisation of Tracking::MonocularInitialization (Tracking.cc:605-671), on the device
+class Initializer {
+public:
+    // Initializer(const Frame &ReferenceFrame, float sigma = 1.0, int iterations = 200): K = (fx, fy, cx, cy) is ReferenceFrame.mK, mvKeys1 = ReferenceFrame.mvKeysUn
+    Initializer(const FrameView &ReferenceFrame, const float K[4], float sigma = 1.0f, int iterations = 200, unsigned randSeed = 0) : n1_(ReferenceFrame.N)
+    { check(sgx_initializer_create(n1_, ReferenceFrame.mvKeysUn.data(), K, sigma, iterations, randSeed, &h_), "sgx_initializer_create"); }
+    ~Initializer() { if (h_) sgx_initializer_destroy(h_); }
+    Initializer(const Initializer &) = delete; Initializer &operator=(const Initializer &) = delete;
+    // bool Initialize(const Frame &CurrentFrame, const vector<int> &vMatches12, cv::Mat &R21, cv::Mat &t21, vector<cv::Point3f> &vP3D, vector<bool> &vbTriangulated):
+    // R21 3 x 3 row-major, vP3D n1 x 3; the outputs are written on success only, as in the reference.  randDraws (optional): the 8 x iterations raw rand() values of
+    // mvSets for callers that share the process-global stream; otherwise the object's glibc-compatible replica is used.  report (optional): scores, model, per-hypothesis counts.
+    bool Initialize(const FrameView &CurrentFrame, const std::vector<int32_t> &vMatches12, float R21[9], float t21[3], std::vector<float> &vP3D, std::vector<bool> &vbTriangulated,
+                    const std::vector<int32_t> *randDraws = nullptr, sgx_init_report *report = nullptr)
+    {
+        if ((int)vMatches12.size() != n1_) throw std::runtime_error("Initializer::Initialize: vMatches12 has one entry per key of the reference frame");
+        const size_t n = (size_t)(n1_ > 0 ? n1_ : 1);
+        std::vector<float> p3d(3 * n, 0.f); std::vector<uint8_t> tri(n, 0), inl(n, 0); float R[9], t[3]; int32_t ok = 0;
+        check(sgx_initializer_initialize(h_, CurrentFrame.N, CurrentFrame.mvKeysUn.data(), vMatches12.data(), randDraws ? randDraws->data() : nullptr, R, t, p3d.data(), tri.data(),
+                                         inl.data(), &ok, report), "sgx_initializer_initialize");
+        if (!ok) return false;
+        std::memcpy(R21, R, sizeof R); std::memcpy(t21, t, sizeof t);
+        vP3D.assign(p3d.begin(), p3d.begin() + 3 * (size_t)n1_); vbTriangulated.assign((size_t)n1_, false);
+        for (int i = 0; i < n1_; i++) vbTriangulated[(size_t)i] = tri[(size_t)i] != 0;
+        return true;
+    }
+private:
+    sgx_initializer *h_ = nullptr; int n1_;
+};
+
 // ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (src/sg-slam/include/ORBVocabulary.h:31-32): the members the reference calls
 class ORBVocabulary {
 public:
