@@ -72,6 +72,17 @@ int sgx_orb_get_tables(const sgx_orb *h, float *scale, float *inv_scale, float *
  * Asynchronous on `stream`.  cap must be >= sgx_orb_keypoint_capacity(). */
 int sgx_orb_extract_batch_dev(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch,
                               sgx_keypoint *d_kps, uint8_t *d_desc, int32_t *d_count, int cap, void *stream);
+/* The same extraction in two calls, for a caller that erases keypoints in between (Frame::RmDynamicPointWithSemanticAndGeometry needs positions only): orientation and
+ * descriptors are then computed for the survivors alone.  detect -> [anything that reads positions] -> sgx_frame_compact_keys_src_batch_dev -> describe gives, keypoint for
+ * keypoint and byte for byte, what sgx_orb_extract_batch_dev -> sgx_frame_compact_keys_batch_dev gives.
+ *   sgx_orb_detect_batch_dev: pyramid, FAST, octree.  d_kps / d_count as above, every field final except `angle`, which holds -1 (cv::KeyPoint's "not applicable") until
+ *     the describe call.  Raises the overflow status under the same condition as the one-shot call.  The pyramid and the selection lists stay in the handle.
+ *   sgx_orb_describe_batch_dev: same d_gray / pitch / batch as the detect call it follows on the same stream (SGX_ERR_INVALID without one; any other extraction on the
+ *     handle in between invalidates it).  d_n_kept[f] keypoints of frame f survive; d_src[f * cap + j] is the index that compacted keypoint j had in the detect call's
+ *     output, ascending.  Writes the angle of d_kps[f * cap + j] and descriptor row d_desc[(f * cap + j) * 32 ..] for j < d_n_kept[f], nothing else. */
+int sgx_orb_detect_batch_dev(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch, sgx_keypoint *d_kps, int32_t *d_count, int cap, void *stream);
+int sgx_orb_describe_batch_dev(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch, const int32_t *d_src, const int32_t *d_n_kept,
+                               sgx_keypoint *d_kps, uint8_t *d_desc, int cap, void *stream);
 /* Single host frame == ORBextractor::operator() (ORBextractor.cc:1045-1106).  Synchronous. */
 int sgx_orb_extract(sgx_orb *h, const uint8_t *gray, int stride, sgx_keypoint *kps, uint8_t *desc, int cap, int *n);
 /* device-side overflow/status word of the last batched call (synchronises `stream`) */
@@ -608,6 +619,10 @@ int sgx_dynamic_mask_batch_dev(int batch, int cap, const sgx_keypoint *d_keys, c
  * keypoints of the frame are restored (:599-604).  Out of place; d_have_dynamic may be NULL (no dynamic object in any frame). */
 int sgx_frame_compact_keys_batch_dev(int batch, int cap, const sgx_keypoint *d_keys, const uint8_t *d_desc, const int32_t *d_n, const uint8_t *d_keep,
                                      const int32_t *d_have_dynamic, int nfeatures, sgx_keypoint *d_keys_out, uint8_t *d_desc_out, int32_t *d_n_out, void *stream);
+/* The same erase step where descriptors do not exist yet (after sgx_orb_detect_batch_dev): keypoints only; d_src_out[f * cap + j] = index in d_keys of output keypoint j,
+ * ascending (the identity when everything is restored) — what sgx_orb_describe_batch_dev takes. */
+int sgx_frame_compact_keys_src_batch_dev(int batch, int cap, const sgx_keypoint *d_keys, const int32_t *d_n, const uint8_t *d_keep, const int32_t *d_have_dynamic,
+                                         int nfeatures, sgx_keypoint *d_keys_out, int32_t *d_src_out, int32_t *d_n_out, void *stream);
 
 
 /* ---- inputs of the dynamic-feature mask: optical flow + fundamental matrix ------------------------

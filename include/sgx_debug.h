@@ -57,6 +57,13 @@ int sgx_det_debug_run_step(sgx_det *h, const uint8_t *d_img, int pitch, int batc
 /* run the octree-distribution kernel alone on packed candidates (x | y<<12 | score<<24, coordinates
  * relative to the (16,16) border origin) for `level`; returns the selected packed entries in list order */
 int sgx_orb_debug_run_octree(sgx_orb *h, int level, const uint32_t *packed, int n, uint32_t *out_sel, int cap, int *nsel);
+/* test / A-B tap: 1 = the NEXT sgx_tracker_create of this thread builds a tracker that orients and describes every raw keypoint before the dynamic mask (one-shot
+ * extraction, descriptor rows moved by the erase step) instead of the survivors after it; 0 = the product order; -1 = default (SGX_TRK_DESCRIBE_EARLY set, or the product
+ * order).  Bit-identical results either way. */
+int sgx_tracker_debug_set_describe_early(int on);
+/* test tap: person rectangles for the following steps of a tracker created WITHOUT a detector (host arrays: streams x max_boxes x (x, y, w, h), streams counts, streams
+ * have-dynamic flags), in place of the empty set it would mask with.  Synchronises. */
+int sgx_tracker_debug_set_boxes(sgx_tracker *t, const float *boxes, const int32_t *nboxes, const int32_t *have_dynamic);
 
 #ifdef __cplusplus
 }

@@ -110,7 +110,7 @@ SYMBOLS = [
     'sgx_pnp_solver_get_estimate', 'sgx_pnp_solver_destroy', 'sgx_pnp_batch_create', 'sgx_pnp_batch_set_dev', 'sgx_pnp_batch_iterate_dev', 'sgx_pnp_batch_destroy',
     'sgx_obj3d_create', 'sgx_obj3d_destroy', 'sgx_obj3d_detect_batch_dev', 'sgx_obj3d_detect', 'sgx_objdb_create', 'sgx_objdb_destroy', 'sgx_objdb_add', 'sgx_objdb_size',
     'sgx_objdb_get', 'sgx_initializer_create', 'sgx_initializer_initialize', 'sgx_initializer_destroy', 'sgx_init_batch_create', 'sgx_init_batch_run_dev',
-    'sgx_init_batch_destroy',
+    'sgx_init_batch_destroy', 'sgx_orb_detect_batch_dev', 'sgx_orb_describe_batch_dev', 'sgx_frame_compact_keys_src_batch_dev',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -119,6 +119,7 @@ TAP_SYMBOLS = [
     'sgx_det_debug_detection_output', 'sgx_det_debug_continued', 'sgx_debug_flow_affine_batch_dev', 'sgx_det_debug_set_fusion', 'sgx_det_debug_set_legacy_kernels',
     'sgx_det_debug_set_block_fusion', 'sgx_det_debug_set_irb', 'sgx_det_debug_set_gemm', 'sgx_det_debug_time_ops', 'sgx_det_debug_run_step', 'sgx_flow_debug_read_level',
     'sgx_flow_debug_level_size', 'sgx_flow_debug_read_slot', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas', 'sgx_obj3d_debug_read',
+    'sgx_tracker_debug_set_describe_early', 'sgx_tracker_debug_set_boxes',
 ]
 
 
@@ -148,6 +149,8 @@ class SgxLib:
         d.sgx_orb_get_tables.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         d.sgx_orb_extract_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_int, C.c_void_p]
+        d.sgx_orb_detect_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        d.sgx_orb_describe_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         d.sgx_orb_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         d.sgx_orb_last_status.argtypes = [C.c_void_p, C.c_void_p]
 
@@ -198,6 +201,7 @@ class SgxLib:
         d.sgx_dynamic_mask_batch_dev.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp]
         d.sgx_frame_gray_from_color_batch_dev.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
         d.sgx_frame_compact_keys_batch_dev.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+        d.sgx_frame_compact_keys_src_batch_dev.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
         d.sgx_match_project_local.argtypes = [C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 7 + [C.POINTER(Camera), vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp]
         d.sgx_match_project_local_batch_dev.argtypes = [C.c_int, C.c_int] + [vp] * 6 + [C.c_int] + [vp] * 8 + [C.POINTER(Camera), vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]
         d.sgx_undistort_points.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp]
@@ -296,6 +300,8 @@ class SgxLib:
             d.sgx_obj3d_debug_read.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int)]
             d.sgx_flow_debug_level_size.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
             d.sgx_flow_debug_read_slot.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int32)]
+            d.sgx_tracker_debug_set_describe_early.argtypes = [C.c_int]
+            d.sgx_tracker_debug_set_boxes.argtypes = [vp, vp, vp, vp]
 
     def tap(self, name):
         """a test / tuning tap entry (include/sgx_debug.h); the product library has none"""

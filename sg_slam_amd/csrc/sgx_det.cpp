@@ -1427,7 +1427,20 @@ extern "C" int sgx_frame_compact_keys_batch_dev(int batch, int cap, const sgx_ke
     if (batch < 1 || cap < 1 || !d_keys || !d_desc || !d_n || !d_keep || !d_keys_out || !d_desc_out || !d_n_out || (const void *)d_keys == (const void *)d_keys_out) return SGX_ERR_INVALID;
     sgx_prof_begin(SGX_K_MASK, (sgx_stream_t)stream);
     SGX_LAUNCH(k_compact_keys, dim3(batch), dim3(256), (sgx_stream_t)stream, cap, (const uint8_t *)d_keys, d_desc, d_n, d_keep, d_have_dynamic, (float)nfeatures * 0.1f,
-               (uint8_t *)d_keys_out, d_desc_out, d_n_out);
+               (uint8_t *)d_keys_out, d_desc_out, d_n_out, (int *)nullptr);
+    sgx_prof_end(SGX_K_MASK, (sgx_stream_t)stream);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+// the erase step before the descriptors exist (sgx_orb_detect_batch_dev ... sgx_orb_describe_batch_dev): keypoints only, plus the source index of every survivor
+extern "C" int sgx_frame_compact_keys_src_batch_dev(int batch, int cap, const sgx_keypoint *d_keys, const int32_t *d_n, const uint8_t *d_keep, const int32_t *d_have_dynamic,
+                                                    int nfeatures, sgx_keypoint *d_keys_out, int32_t *d_src_out, int32_t *d_n_out, void *stream)
+{
+    if (batch < 1 || cap < 1 || !d_keys || !d_n || !d_keep || !d_keys_out || !d_src_out || !d_n_out || (const void *)d_keys == (const void *)d_keys_out) return SGX_ERR_INVALID;
+    sgx_prof_begin(SGX_K_MASK, (sgx_stream_t)stream);
+    SGX_LAUNCH(k_compact_keys, dim3(batch), dim3(256), (sgx_stream_t)stream, cap, (const uint8_t *)d_keys, (const uint8_t *)nullptr, d_n, d_keep, d_have_dynamic, (float)nfeatures * 0.1f,
+               (uint8_t *)d_keys_out, (uint8_t *)nullptr, d_n_out, d_src_out);
     sgx_prof_end(SGX_K_MASK, (sgx_stream_t)stream);
     SGX_CHECK_HIP(hipGetLastError());
     return SGX_OK;

@@ -1056,9 +1056,11 @@ SGX_KERNEL(256) k_dynamic_mask(int cap, const uint8_t *keys_raw, const int *n, c
 // descriptor rows are removed, order preserved (the reference erases from mvKeys / rebuilds mDescriptors row by row); when a dynamic
 // object is present and fewer than 0.1 * nFeatures keypoints survive, everything is restored (:599-604).  One workgroup per frame:
 // block scan of the keep flags, then each record (28 B keypoint + 32 B descriptor) moves as dwords.  Out of place.
+// desc == NULL (sgx_frame_compact_keys_src_batch_dev): keypoints only, the descriptors do not exist yet; src_out (optional) gets the source index of every output record,
+// ascending — the identity when everything is restored.
 // ---------------------------------------------------------------------------------------------
 SGX_KERNEL(256) k_compact_keys(int cap, const uint8_t *keys, const uint8_t *desc, const int *n, const uint8_t *keep, const int *have_dynamic, float restore_below,
-                               uint8_t *keys_out, uint8_t *desc_out, int *n_out)
+                               uint8_t *keys_out, uint8_t *desc_out, int *n_out, int *src_out)
 {
     SGX_LDS int scan[256];
     SGX_LDS int s_total;
@@ -1078,12 +1080,17 @@ SGX_KERNEL(256) k_compact_keys(int cap, const uint8_t *keys, const uint8_t *desc
     int pos = restore ? tid * CH : scan[tid];
     for (int i = tid * CH; i < min(N, (tid + 1) * CH); i++) {
         if (!restore && !keep[(size_t)f * cap + i]) continue;
-        const uint32_t *ks = (const uint32_t *)(keys + ((size_t)f * cap + i) * 28), *ds = (const uint32_t *)(desc + ((size_t)f * cap + i) * 32);
-        uint32_t *kd = (uint32_t *)(keys_out + ((size_t)f * cap + pos) * 28), *dd = (uint32_t *)(desc_out + ((size_t)f * cap + pos) * 32);
+        const uint32_t *ks = (const uint32_t *)(keys + ((size_t)f * cap + i) * 28);
+        uint32_t *kd = (uint32_t *)(keys_out + ((size_t)f * cap + pos) * 28);
 #pragma unroll
         for (int w = 0; w < 7; w++) kd[w] = ks[w];
+        if (desc) {
+            const uint32_t *ds = (const uint32_t *)(desc + ((size_t)f * cap + i) * 32);
+            uint32_t *dd = (uint32_t *)(desc_out + ((size_t)f * cap + pos) * 32);
 #pragma unroll
-        for (int w = 0; w < 8; w++) dd[w] = ds[w];
+            for (int w = 0; w < 8; w++) dd[w] = ds[w];
+        }
+        if (src_out) src_out[(size_t)f * cap + pos] = i;
         pos++;
     }
     if (tid == 0) n_out[f] = restore ? N : s_total;

@@ -44,6 +44,7 @@ struct sgx_orb {
     // single-frame staging for sgx_orb_extract
     uint8_t *d_gray1 = nullptr; uint8_t *d_kps1 = nullptr; uint8_t *d_desc1 = nullptr; int *d_count1 = nullptr;
     int last_batch = 0;
+    int detected_batch = 0;        // batch of the last sgx_orb_detect_batch_dev whose pyramid and sel lists are still in the workspace (0: none; any other extraction clears it)
     int oct_maxlim = 0;            // largest octree list capacity over the levels (quota + 3 or 4*nIni)
 };
 
@@ -361,12 +362,10 @@ static void launch_octree(sgx_orb *h, int batch, sgx_stream_t stream)
     }
 }
 
-extern "C" int sgx_orb_extract_batch_dev(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch,
-                                         sgx_keypoint *d_kps, uint8_t *d_desc, int32_t *d_count, int cap, void *stream_)
+// ComputePyramid, ComputeKeyPointsOctTree (ORBextractor.cc:1045-1084): pyramid, FAST cells, octree -> the per-(frame, level) sel lists in the handle;
+// with d_kps, also the keypoint records without orientation (sgx_orb_detect_batch_dev)
+static int launch_detect(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch, sgx_stream_t stream, sgx_keypoint *d_kps = nullptr, int32_t *d_count = nullptr, int cap = 0)
 {
-    if (!h || !d_gray || !d_kps || !d_desc || !d_count) return SGX_ERR_INVALID;
-    if (batch < 1 || batch > h->cfg.max_batch || pitch < h->g.W || (pitch & 3) || ((uintptr_t)d_gray & 3) || cap < h->g.kp_cap) return SGX_ERR_INVALID;
-    sgx_stream_t stream = (sgx_stream_t)stream_;
     const SgxOrbGeom &g = h->g;
     const int nl = g.nlevels;
     h->last_batch = batch;
@@ -389,10 +388,41 @@ extern "C" int sgx_orb_extract_batch_dev(sgx_orb *h, const uint8_t *d_gray, int 
     sgx_prof_end(SGX_K_FAST, stream);
     sgx_prof_begin(SGX_K_OCTREE, stream);
     launch_octree(h, batch, stream);
+    if (d_kps) SGX_LAUNCH(k_octree_keys, dim3((g.kp_cap + 255) / 256, batch), dim3(256), stream, g, h->d_sel, h->d_sel_count, (uint8_t *)d_kps, d_count, cap, h->d_status);
     sgx_prof_end(SGX_K_OCTREE, stream);
+    return SGX_OK;
+}
+
+static unsigned long long umax_packed_of(const sgx_orb *h)
+{
+    unsigned long long v = 0;
+    for (int i = 0; i < 16; i++) v |= (unsigned long long)(h->umax_h[i] & 15) << (4 * i);
+    return v;
+}
+
+// GaussianBlur of every level (ORBextractor.cc:1086-1087) into h->d_blur
+static void launch_blur(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch, sgx_stream_t stream)
+{
+    const SgxOrbGeom &g = h->g;
+    static const int blur_threads = sgx_getenv("SGX_TUNE_BLUR_THREADS") ? atoi(sgx_getenv("SGX_TUNE_BLUR_THREADS")) : 256;   // env = tuning tap (64..512)
+    // persistent workgroups: `parts` per frame, each walks a contiguous range of the frame's tiles (see k_blur_levels); about 4 096 workgroups = 16 per CU
+    const int blur_grid = sgx_getenv("SGX_TUNE_ORB_BLUR_GRID") ? atoi(sgx_getenv("SGX_TUNE_ORB_BLUR_GRID")) : 4096;          // tuning tap: target grid size (measured at 512 frames with the round-3 walk: 0.59 / 0.48 / 0.46 ms at 1 024 / 2 048 / 4 096)
+    const int parts = std::min(g.nblur_tiles, std::max(1, blur_grid / batch));
+    SGX_LAUNCH(k_blur_levels, dim3(parts * batch), dim3(std::min(512, std::max(256, blur_threads))), stream, g, h->d_blur_tiles, d_gray, pitch, h->d_pyr, h->d_blur, batch);
+}
+
+extern "C" int sgx_orb_extract_batch_dev(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch,
+                                         sgx_keypoint *d_kps, uint8_t *d_desc, int32_t *d_count, int cap, void *stream_)
+{
+    if (!h || !d_gray || !d_kps || !d_desc || !d_count) return SGX_ERR_INVALID;
+    if (batch < 1 || batch > h->cfg.max_batch || pitch < h->g.W || (pitch & 3) || ((uintptr_t)d_gray & 3) || cap < h->g.kp_cap) return SGX_ERR_INVALID;
+    sgx_stream_t stream = (sgx_stream_t)stream_;
+    const SgxOrbGeom &g = h->g;
+    h->detected_batch = 0;
+    { const int rc = launch_detect(h, d_gray, pitch, batch, stream); if (rc != SGX_OK) return rc; }
+    static const int e_extra = sgx_getenv("SGX_TUNE_E_EXTRA_LDS") ? atoi(sgx_getenv("SGX_TUNE_E_EXTRA_LDS")) : 0;   // tuning tap: pad the extraction kernels' LDS to cap their occupancy
     sgx_prof_begin(SGX_K_ORIENT_DESC, stream);
-    unsigned long long umax_packed = 0;
-    for (int i = 0; i < 16; i++) umax_packed |= (unsigned long long)(h->umax_h[i] & 15) << (4 * i);
+    const unsigned long long umax_packed = umax_packed_of(h);
     // default: blur whole levels once (k_blur_levels), then a light per-keypoint kernel; SGX_TUNE_ORB_PATCH_BLUR=1 selects the first design (blur of a
     // 37x37 window per keypoint inside k_orient_desc) — identical bytes (tests), ~45 vs ~20+ VALU operations per pixel-equivalent
 #ifdef SGX_DEBUG_TAPS      // the superseded descriptor kernels (k_orient_desc: blur per keypoint window; k_orient_desc2: one keypoint per wave) exist in the tap build only
@@ -403,12 +433,7 @@ extern "C" int sgx_orb_extract_batch_dev(sgx_orb *h, const uint8_t *d_gray, int 
     } else
 #endif
     {
-        static const int blur_threads = sgx_getenv("SGX_TUNE_BLUR_THREADS") ? atoi(sgx_getenv("SGX_TUNE_BLUR_THREADS")) : 256;   // env = tuning tap (64..512)
-        {   // persistent workgroups: `parts` per frame, each walks a contiguous range of the frame's tiles (see k_blur_levels); about 4 096 workgroups = 16 per CU
-            const int blur_grid = sgx_getenv("SGX_TUNE_ORB_BLUR_GRID") ? atoi(sgx_getenv("SGX_TUNE_ORB_BLUR_GRID")) : 4096;          // tuning tap: target grid size (measured at 512 frames with the round-3 walk: 0.59 / 0.48 / 0.46 ms at 1 024 / 2 048 / 4 096)
-            const int parts = std::min(g.nblur_tiles, std::max(1, blur_grid / batch));
-            SGX_LAUNCH(k_blur_levels, dim3(parts * batch), dim3(std::min(512, std::max(256, blur_threads))), stream, g, h->d_blur_tiles, d_gray, pitch, h->d_pyr, h->d_blur, batch);
-        }
+        launch_blur(h, d_gray, pitch, batch, stream);
 #ifdef SGX_DEBUG_TAPS
         static const bool one_per_wave = sgx_getenv("SGX_TUNE_ORB_DESC_ONE_PER_WAVE") != nullptr;       // tuning tap: k_orient_desc2 (one keypoint per wave)
         if (one_per_wave)
@@ -416,9 +441,37 @@ extern "C" int sgx_orb_extract_batch_dev(sgx_orb *h, const uint8_t *d_gray, int 
                        umax_packed, h->d_pattern, (uint8_t *)d_kps, d_desc, d_count, cap, batch, h->d_status);
         else
 #endif
-            SGX_LAUNCH(k_orient_desc4, dim3(((g.kp_cap + 3) / 4) * batch), dim3(64), stream, g, d_gray, pitch, h->d_pyr, h->d_blur, h->d_sel, h->d_sel_count,
-                       umax_packed, h->d_pattern, (uint8_t *)d_kps, d_desc, d_count, cap, batch, h->d_status);
+            SGX_LAUNCH(k_orient_desc4<false>, dim3(((g.kp_cap + 3) / 4) * batch), dim3(64), stream, g, d_gray, pitch, h->d_pyr, h->d_blur, h->d_sel, h->d_sel_count,
+                       umax_packed, h->d_pattern, (uint8_t *)d_kps, d_desc, d_count, cap, batch, h->d_status, (const int *)nullptr, (const int *)nullptr);
     }
+    sgx_prof_end(SGX_K_ORIENT_DESC, stream);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+// The extractor in two calls, for callers that erase keypoints between detection and description (the dynamic-feature mask): see include/sgx.h
+extern "C" int sgx_orb_detect_batch_dev(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch, sgx_keypoint *d_kps, int32_t *d_count, int cap, void *stream_)
+{
+    if (!h || !d_gray || !d_kps || !d_count) return SGX_ERR_INVALID;
+    if (batch < 1 || batch > h->cfg.max_batch || pitch < h->g.W || (pitch & 3) || ((uintptr_t)d_gray & 3) || cap < h->g.kp_cap) return SGX_ERR_INVALID;
+    h->detected_batch = 0;
+    { const int rc = launch_detect(h, d_gray, pitch, batch, (sgx_stream_t)stream_, d_kps, d_count, cap); if (rc != SGX_OK) return rc; }
+    SGX_CHECK_HIP(hipGetLastError());
+    h->detected_batch = batch;
+    return SGX_OK;
+}
+
+extern "C" int sgx_orb_describe_batch_dev(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch, const int32_t *d_src, const int32_t *d_n_kept,
+                                          sgx_keypoint *d_kps, uint8_t *d_desc, int cap, void *stream_)
+{
+    if (!h || !d_gray || !d_src || !d_n_kept || !d_kps || !d_desc) return SGX_ERR_INVALID;
+    if (batch < 1 || batch != h->detected_batch || pitch < h->g.W || (pitch & 3) || ((uintptr_t)d_gray & 3) || cap < h->g.kp_cap) return SGX_ERR_INVALID;
+    sgx_stream_t stream = (sgx_stream_t)stream_;
+    const SgxOrbGeom &g = h->g;
+    sgx_prof_begin(SGX_K_ORIENT_DESC, stream);
+    launch_blur(h, d_gray, pitch, batch, stream);
+    SGX_LAUNCH(k_orient_desc4<true>, dim3(((g.kp_cap + 3) / 4) * batch), dim3(64), stream, g, d_gray, pitch, h->d_pyr, h->d_blur, h->d_sel, h->d_sel_count,
+               umax_packed_of(h), h->d_pattern, (uint8_t *)d_kps, d_desc, (int *)nullptr, cap, batch, h->d_status, d_src, d_n_kept);
     sgx_prof_end(SGX_K_ORIENT_DESC, stream);
     SGX_CHECK_HIP(hipGetLastError());
     return SGX_OK;

@@ -1227,14 +1227,27 @@ SGX_KERNEL(64) k_orient_desc2(SgxOrbGeom g, const uint8_t *gray, int gray_pitch,
 }
 #endif      /* SGX_DEBUG_TAPS */
 
+// raw slot (index into the frame's concatenated per-level sel lists) of output slot `out`: itself in the one-shot path; src[out] after the erase step, `cap` (= nothing) past
+// the kept count or for an index no frame can hold
+template <bool KEPT> SGX_DEV int sgx_desc_raw_slot(const int *src, int frame, int cap, int out, int n_kept)
+{
+    if (!KEPT) return out;
+    if (out >= n_kept) return cap;
+    const int s = src[(size_t)frame * cap + out];
+    return (unsigned)s < (unsigned)cap ? s : cap;
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_orient_desc4: k_orient_desc2 with FOUR keypoints per wave (16 lanes each).  The serial part of a keypoint (fastAtan2 + the bit-exact sincosf, ~250
 // wave instructions executed for one active lane) is then shared by four keypoints, and the moment sums walk the staged patch as dwords (4 pixels per
 // lane step).  Same arithmetic per keypoint, so identical bytes.  block -> (group of 4 slots, frame), XCD-aware like k_orient_desc.
 // ---------------------------------------------------------------------------------------------
+// KEPT (sgx_orb_describe_batch_dev, after the dynamic mask erased keypoints): lane group j of a frame takes its raw slot from src[j] (j < n_kept) instead of j, and writes
+// only what sgx_orb_detect_batch_dev left open: the angle of compacted keypoint j and descriptor row j.  Everything between the look-up and the stores is the same code.
+template <bool KEPT>
 SGX_KERNEL(64) k_orient_desc4(SgxOrbGeom g, const uint8_t *gray, int gray_pitch, const uint8_t *pyr, const uint8_t *blur,
                               const uint32_t *sel, const int *sel_count, unsigned long long umax_packed, const signed char *pattern,
-                              uint8_t *kps_raw, uint8_t *desc, int *count, int cap, int batch, uint32_t *status)
+                              uint8_t *kps_raw, uint8_t *desc, int *count, int cap, int batch, uint32_t *status, const int *src, const int *n_kept)
 {
     SGX_LDS uint32_t patch_dw[4][31 * SGX_MS / 4];
     SGX_LDS uint8_t bits[4][256];
@@ -1248,8 +1261,9 @@ SGX_KERNEL(64) k_orient_desc4(SgxOrbGeom g, const uint8_t *gray, int gray_pitch,
     }
     // per-level counts of this frame (wave-uniform)
     int total = 0;
-    for (int l = 0; l < g.nlevels; l++) total += sel_count[frame * g.nlevels + l];
-    if (slot4 == 0) {
+    if (KEPT) total = min(n_kept[frame], cap);
+    else for (int l = 0; l < g.nlevels; l++) total += sel_count[frame * g.nlevels + l];
+    if (!KEPT && slot4 == 0) {
         SGX_THREADS_BEGIN(tid)
         if (tid == 0) { count[frame] = total < cap ? total : cap; if (total > cap) sgx_atomic_or(status, SGX_ST_KP_OVERFLOW); }
         SGX_THREADS_END
@@ -1259,7 +1273,7 @@ SGX_KERNEL(64) k_orient_desc4(SgxOrbGeom g, const uint8_t *gray, int gray_pitch,
     SGX_THREADS_BEGIN(tid)
     if (tid < 4) { s_m01[tid] = 0; s_m10[tid] = 0; }
     // stage the four 31x31 moment patches (aligned dwords, 36 bytes per row)
-    const int grp = tid >> 4, l16 = tid & 15, slot = 4 * slot4 + grp;
+    const int grp = tid >> 4, l16 = tid & 15, out = 4 * slot4 + grp, slot = sgx_desc_raw_slot<KEPT>(src, frame, cap, out, total);
     int level = -1, base = 0, acc_ = 0;
     for (int l = 0; l < g.nlevels; l++) {
         const int n = sel_count[frame * g.nlevels + l];
@@ -1280,7 +1294,7 @@ SGX_KERNEL(64) k_orient_desc4(SgxOrbGeom g, const uint8_t *gray, int gray_pitch,
     SGX_THREADS_END
     SGX_SYNC();
     SGX_THREADS_BEGIN(tid)
-    const int grp = tid >> 4, l16 = tid & 15, slot = 4 * slot4 + grp;
+    const int grp = tid >> 4, l16 = tid & 15, out = 4 * slot4 + grp, slot = sgx_desc_raw_slot<KEPT>(src, frame, cap, out, total);
     int level = -1, base = 0, acc_ = 0;
     for (int l = 0; l < g.nlevels; l++) {
         const int n = sel_count[frame * g.nlevels + l];
@@ -1309,7 +1323,7 @@ SGX_KERNEL(64) k_orient_desc4(SgxOrbGeom g, const uint8_t *gray, int gray_pitch,
     SGX_THREADS_END
     SGX_SYNC();
     SGX_THREADS_BEGIN(tid)
-    const int grp = tid >> 4, l16 = tid & 15, slot = 4 * slot4 + grp;
+    const int grp = tid >> 4, l16 = tid & 15, out = 4 * slot4 + grp, slot = sgx_desc_raw_slot<KEPT>(src, frame, cap, out, total);
     int level = -1, base = 0, acc_ = 0;
     for (int l = 0; l < g.nlevels; l++) {
         const int n = sel_count[frame * g.nlevels + l];
@@ -1325,16 +1339,19 @@ SGX_KERNEL(64) k_orient_desc4(SgxOrbGeom g, const uint8_t *gray, int gray_pitch,
         float sn, cs;
         sgx_sincosf(angle * factorPI, &sn, &cs);
         s_a[grp] = cs; s_b[grp] = sn;
-        float *kp = (float *)(kps_raw + ((size_t)frame * cap + slot) * 28);
+        float *kp = (float *)(kps_raw + ((size_t)frame * cap + out) * 28);
         float fx = (float)kx, fy = (float)ky;
         if (level != 0) { fx = fx * L.scale; fy = fy * L.scale; }
-        kp[0] = fx; kp[1] = fy; kp[2] = (float)L.patch_size; kp[3] = angle; kp[4] = (float)(e >> 24);
-        ((int *)kp)[5] = level; ((int *)kp)[6] = -1;
+        if (KEPT) kp[3] = angle;
+        else {
+            kp[0] = fx; kp[1] = fy; kp[2] = (float)L.patch_size; kp[3] = angle; kp[4] = (float)(e >> 24);
+            ((int *)kp)[5] = level; ((int *)kp)[6] = -1;
+        }
     }
     SGX_THREADS_END
     SGX_SYNC();
     SGX_THREADS_BEGIN(tid)
-    const int grp = tid >> 4, l16 = tid & 15, slot = 4 * slot4 + grp;
+    const int grp = tid >> 4, l16 = tid & 15, out = 4 * slot4 + grp, slot = sgx_desc_raw_slot<KEPT>(src, frame, cap, out, total);
     int level = -1, base = 0, acc_ = 0;
     for (int l = 0; l < g.nlevels; l++) {
         const int n = sel_count[frame * g.nlevels + l];
@@ -1360,16 +1377,47 @@ SGX_KERNEL(64) k_orient_desc4(SgxOrbGeom g, const uint8_t *gray, int gray_pitch,
     SGX_THREADS_END
     SGX_SYNC();
     SGX_THREADS_BEGIN(tid)
-    const int grp = tid >> 4, l16 = tid & 15, slot = 4 * slot4 + grp;
-    if (slot < total && slot < cap) {
+    const int grp = tid >> 4, l16 = tid & 15, out = 4 * slot4 + grp;
+    if (out < total && out < cap) {
 #pragma unroll
         for (int h2 = 0; h2 < 2; h2++) {
             const int byte = 2 * l16 + h2;
             int v = 0;
 #pragma unroll
             for (int j = 0; j < 8; j++) v |= bits[grp][8 * byte + j] << j;
-            desc[((size_t)frame * cap + slot) * 32 + byte] = (uint8_t)v;
+            desc[((size_t)frame * cap + out) * 32 + byte] = (uint8_t)v;
         }
+    }
+    SGX_THREADS_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_octree_keys (sgx_orb_detect_batch_dev): the keypoint records of the octree's selection without orientation — position, size, response, octave, class_id exactly as
+// k_orient_desc4 writes them (same slot -> (level, entry) walk over sel_count, same float products), SGX_KP_ANGLE_PENDING in the angle field — plus the frame's count
+// and the overflow flag.  One thread per slot; grid (ceil(kp_cap / 256), batch).
+// ---------------------------------------------------------------------------------------------
+#define SGX_KP_ANGLE_PENDING (-1.0f)      /* cv::KeyPoint's own "no orientation" value */
+SGX_KERNEL(256) k_octree_keys(SgxOrbGeom g, const uint32_t *sel, const int *sel_count, uint8_t *kps_raw, int *count, int cap, uint32_t *status)
+{
+    const int frame = (int)blockIdx.y;
+    SGX_THREADS_BEGIN(tid)
+    const int slot = (int)blockIdx.x * 256 + tid;
+    int level = -1, base = 0, total = 0;
+    for (int l = 0; l < g.nlevels; l++) {
+        const int n = sel_count[frame * g.nlevels + l];
+        if (level < 0 && slot < total + n) { level = l; base = total; }
+        total += n;
+    }
+    if (slot == 0) { count[frame] = total < cap ? total : cap; if (total > cap) sgx_atomic_or(status, SGX_ST_KP_OVERFLOW); }
+    if (level >= 0 && slot < cap) {
+        const SgxLevel L = g.lv[level];
+        const uint32_t e = sel[((size_t)frame * g.nlevels + level) * SGX_OCT_MAXN + (slot - base)];
+        const int kx = (int)(e & 0xFFF) + SGX_BORDER, ky = (int)((e >> 12) & 0xFFF) + SGX_BORDER;
+        float *kp = (float *)(kps_raw + ((size_t)frame * cap + slot) * 28);
+        float fx = (float)kx, fy = (float)ky;
+        if (level != 0) { fx = fx * L.scale; fy = fy * L.scale; }
+        kp[0] = fx; kp[1] = fy; kp[2] = (float)L.patch_size; kp[3] = SGX_KP_ANGLE_PENDING; kp[4] = (float)(e >> 24);
+        ((int *)kp)[5] = level; ((int *)kp)[6] = -1;
     }
     SGX_THREADS_END
 }

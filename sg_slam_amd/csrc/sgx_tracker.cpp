@@ -8,7 +8,8 @@
 // in "visual odometry" form (the map points a frame is tracked against are the previous frame's keypoints unprojected with their measured depth,
 // Tracking::UpdateLastFrame :840-904; the local map is the points of frames t-2 and t-3), with the stages spread over three HIP streams:
 //     D  Detector2D::detect of frame t            (the reference runs it on its own thread, Detector2D::Run; Frame.cc:478 waits for it)
-//     E  ORB extract -> LK flow -> RANSAC F -> [event: detector done] -> dynamic mask + erase -> [UndistortKeyPoints +] stereo-from-RGBD   of frame t + 1
+//     E  ORB detect -> LK flow -> RANSAC F -> [event: detector done] -> dynamic mask + erase -> ORB orientation + descriptors of the survivors -> [UndistortKeyPoints +] stereo-from-RGBD   of frame t + 1
+//        (the reference describes every keypoint first, ORBextractor::operator(), and erases descriptor rows with the keypoints; nothing in between reads them, so the bytes are the same)
 //     T  motion model -> SearchByProjection(cur,last) -> PoseOptimization -> SearchLocalPoints -> PoseOptimization -> unproject -> map points   of frame t
 // Frame state is triple-buffered (frame t lives in slot t % 3); events order the streams; nothing synchronises with the host inside a step.
 // An optional upload stream U takes host frames (pinned staging buffers the caller fills, as cv::imread would) to the device and converts
@@ -90,7 +91,10 @@ struct sgx_tracker {
     float *lm_xw, *lm_normal, *lm_min, *lm_max; uint8_t *lm_desc, *lm_skip; int32_t *lm_obs, *lm_n;
     int32_t *match_local, *nmatch_local, *merged, *cur_mp_obs, *ninl2; uint8_t *in_view, *outlier2; float *xw_all;
     // mask stage
-    sgx_keypoint *rkeys; uint8_t *rdesc, *keep, *lk_status; int32_t *rn; float *prev_xy; double *F; int32_t *f_ok, *f_stats;
+    // rkeys / rn: the frame's keypoints before the erase step (positions final, orientation pending: sgx_orb_detect_batch_dev); src: raw index of every survivor
+    sgx_keypoint *rkeys; uint8_t *keep, *lk_status; int32_t *rn, *src; float *prev_xy; double *F; int32_t *f_ok, *f_stats;
+    uint8_t *rdesc = nullptr;               // tap build, describe_early only: the descriptors of all raw keypoints (the order before describe-after-mask, kept as its A/B arm)
+    bool describe_early = false;
     float *pre_boxes; int32_t *pre_nboxes, *pre_have;
     float *no_boxes; int32_t *no_nboxes, *no_have;
     // detector results, double-buffered
@@ -120,6 +124,9 @@ struct sgx_tracker {
         dev.push_back(q); *p = (Tp *)q; return SGX_OK;
     }
 };
+
+static thread_local int g_trk_describe_early = -1;      // test tap: the next sgx_tracker_create of this thread; -1 = SGX_TRK_DESCRIBE_EARLY (tap build) or off
+SGX_TAP int sgx_tracker_debug_set_describe_early(int on) { g_trk_describe_early = on < 0 ? -1 : (on ? 1 : 0); return SGX_OK; }
 
 extern "C" void sgx_tracker_destroy(sgx_tracker *t)
 {
@@ -170,7 +177,12 @@ extern "C" int sgx_tracker_create(const sgx_tracker_config *cfg, sgx_det *detect
         if (hipMemcpy(t->lm_skip, ones.data(), ones.size(), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(t->lm_obs, one.data(), one.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(t->lm_n, full.data(), full.size() * 4, hipMemcpyHostToDevice) != hipSuccess) FAIL(SGX_ERR_DEVICE);
     }
-    if (t->alloc(&t->rkeys, (size_t)S * cap) || t->alloc(&t->rdesc, (size_t)S * cap * 32) || t->alloc(&t->keep, (size_t)S * cap) || t->alloc(&t->lk_status, (size_t)S * cap) ||
+    {   // A/B arm (tap build): orientation + descriptors of every raw keypoint before the mask, erased rows copied out by the compaction
+        static const bool env_early = sgx_getenv("SGX_TRK_DESCRIBE_EARLY") != nullptr;
+        t->describe_early = g_trk_describe_early < 0 ? env_early : g_trk_describe_early != 0;
+        if (t->describe_early && t->alloc(&t->rdesc, (size_t)S * cap * 32)) FAIL(SGX_ERR_NOMEM);
+    }
+    if (t->alloc(&t->rkeys, (size_t)S * cap) || t->alloc(&t->src, (size_t)S * cap) || t->alloc(&t->keep, (size_t)S * cap) || t->alloc(&t->lk_status, (size_t)S * cap) ||
         t->alloc(&t->rn, S) || t->alloc(&t->prev_xy, (size_t)S * cap * 2) || t->alloc(&t->F, (size_t)S * 9) || t->alloc(&t->f_ok, S) || t->alloc(&t->f_stats, (size_t)S * 4) ||
         t->alloc(&t->pre_boxes, (size_t)S * MB * 4) || t->alloc(&t->pre_nboxes, S) || t->alloc(&t->pre_have, S) || t->alloc(&t->no_boxes, (size_t)S * MB * 4) ||
         t->alloc(&t->no_nboxes, S) || t->alloc(&t->no_have, S)) FAIL(SGX_ERR_NOMEM);
@@ -269,12 +281,18 @@ extern "C" int sgx_tracker_step_dev(sgx_tracker *t, const uint8_t *d_gray, int g
             TRK_CHECK(sgx_orb_extract_batch_dev(t->ex, d_gray, gray_pitch, S, t->keys[c], t->desc[c], t->n[c], cap, sE));
             TRK_CHECK(sgx_flow_lk_batch_dev(t->flow, d_gray, gray_pitch, S, nullptr, nullptr, cap, nullptr, nullptr, nullptr, sE));      // first frame: pyramid only (imGrayPre empty, Frame.cc:155-163)
         } else {
-            TRK_CHECK(sgx_orb_extract_batch_dev(t->ex, d_gray, gray_pitch, S, t->rkeys, t->rdesc, t->rn, cap, sE));
+            // LK, RANSAC and the mask read positions only: orientation and descriptors wait until the erase step has decided who survives
+            if (t->describe_early) TRK_CHECK(sgx_orb_extract_batch_dev(t->ex, d_gray, gray_pitch, S, t->rkeys, t->rdesc, t->rn, cap, sE));
+            else TRK_CHECK(sgx_orb_detect_batch_dev(t->ex, d_gray, gray_pitch, S, t->rkeys, t->rn, cap, sE));
             TRK_CHECK(sgx_flow_lk_batch_dev(t->flow, d_gray, gray_pitch, S, t->rkeys, t->rn, cap, t->prev_xy, t->lk_status, nullptr, sE));
             TRK_CHECK(sgx_fundamental_ransac_batch_dev(S, cap, t->rkeys, t->rn, t->prev_xy, t->pre_have, t->pre_boxes, t->pre_nboxes, MB, 1.0, 0.99, t->F, t->f_ok, t->f_stats, sE));
             if (with_det && t->pipelined) st_wait(sE, t->ev_det[b]);             // Frame.cc:478: while(!isDetectImageFinished())
             TRK_CHECK(sgx_dynamic_mask_batch_dev(S, cap, t->rkeys, t->rn, t->prev_xy, t->F, boxes, nboxes, MB, t->keep, sE));
-            TRK_CHECK(sgx_frame_compact_keys_batch_dev(S, cap, t->rkeys, t->rdesc, t->rn, t->keep, have, cf.nfeatures, t->keys[c], t->desc[c], t->n[c], sE));
+            if (t->describe_early) TRK_CHECK(sgx_frame_compact_keys_batch_dev(S, cap, t->rkeys, t->rdesc, t->rn, t->keep, have, cf.nfeatures, t->keys[c], t->desc[c], t->n[c], sE));
+            else {
+                TRK_CHECK(sgx_frame_compact_keys_src_batch_dev(S, cap, t->rkeys, t->rn, t->keep, have, cf.nfeatures, t->keys[c], t->src, t->n[c], sE));
+                TRK_CHECK(sgx_orb_describe_batch_dev(t->ex, d_gray, gray_pitch, S, t->src, t->n[c], t->keys[c], t->desc[c], cap, sE));
+            }
             // Frame.cc:482-499: this frame's detector results become the "previous frame" state of the next call
             TRK_HIP(hipMemcpyAsync(t->pre_boxes, boxes, (size_t)S * MB * 16, hipMemcpyDeviceToDevice, sE));
             TRK_HIP(hipMemcpyAsync(t->pre_nboxes, nboxes, (size_t)S * 4, hipMemcpyDeviceToDevice, sE));
@@ -450,6 +468,18 @@ extern "C" int sgx_tracker_frame_keys_un_dev(sgx_tracker *t, const sgx_keypoint 
 {
     if (!t || !d_keys_un || t->frame_idx < 1) return SGX_ERR_INVALID;
     *d_keys_un = t->undistort ? t->keys_un[t->cur] : t->keys[t->cur];
+    return SGX_OK;
+}
+
+// test tap: person rectangles of the steps that follow for a tracker WITHOUT a detector (host arrays: S x max_boxes x (x, y, w, h), S counts, S have-dynamic flags), in
+// place of the empty set such a tracker masks with
+SGX_TAP int sgx_tracker_debug_set_boxes(sgx_tracker *t, const float *boxes, const int32_t *nboxes, const int32_t *have_dynamic)
+{
+    if (!t || !boxes || !nboxes || !have_dynamic) return SGX_ERR_INVALID;
+    TRK_CHECK(sgx_tracker_sync(t));
+    TRK_HIP(hipMemcpy(t->no_boxes, boxes, (size_t)t->S * t->MB * 16, hipMemcpyHostToDevice));
+    TRK_HIP(hipMemcpy(t->no_nboxes, nboxes, (size_t)t->S * 4, hipMemcpyHostToDevice));
+    TRK_HIP(hipMemcpy(t->no_have, have_dynamic, (size_t)t->S * 4, hipMemcpyHostToDevice));
     return SGX_OK;
 }
 

@@ -59,6 +59,16 @@ class ORBextractor:
         self.lib.check(self.lib.dll.sgx_orb_extract_batch_dev(self.h, _vp(d_gray), pitch, batch, _vp(d_kps), _vp(d_desc),
                                                               _vp(d_count), self.capacity, _vp(stream)), 'sgx_orb_extract_batch_dev')
 
+    def detect_batch_dev(self, d_gray, pitch, batch, d_kps, d_count, stream=None):
+        """Pyramid, FAST and octree only: keypoint records complete except for the angle (-1 until describe_batch_dev)."""
+        self.lib.check(self.lib.dll.sgx_orb_detect_batch_dev(self.h, _vp(d_gray), pitch, batch, _vp(d_kps), _vp(d_count), self.capacity, _vp(stream)),
+                       'sgx_orb_detect_batch_dev')
+
+    def describe_batch_dev(self, d_gray, pitch, batch, d_src, d_n_kept, d_kps, d_desc, stream=None):
+        """IC_Angle + steered BRIEF of the d_n_kept[f] survivors of the detect call before; d_src: their indices in its output (frame.compact_keys_src_batch)."""
+        self.lib.check(self.lib.dll.sgx_orb_describe_batch_dev(self.h, _vp(d_gray), pitch, batch, _vp(d_src), _vp(d_n_kept), _vp(d_kps), _vp(d_desc),
+                                                               self.capacity, _vp(stream)), 'sgx_orb_describe_batch_dev')
+
     def last_status(self, stream=None):
         self.lib.check(self.lib.dll.sgx_orb_last_status(self.h, _vp(stream)), 'sgx_orb_last_status')
 

@@ -8,7 +8,8 @@ from .matcher import camera_struct
 
 
 class TrackerNative:
-    def __init__(self, lib, streams, cam, width=640, height=480, nfeatures=1000, th=15.0, pipelined=True, local_map=True, dynamic_mask=True, max_boxes=8, detector=None, dist=None):
+    def __init__(self, lib, streams, cam, width=640, height=480, nfeatures=1000, th=15.0, pipelined=True, local_map=True, dynamic_mask=True, max_boxes=8, detector=None, dist=None,
+                 describe_early=None):
         self.lib, self.S, self.W, self.H = lib, int(streams), int(width), int(height)
         cfg = TrackerConfig()
         cfg.streams, cfg.width, cfg.height = self.S, width, height
@@ -17,7 +18,12 @@ class TrackerNative:
         cfg.local_map, cfg.dynamic_mask, cfg.max_boxes, cfg.pipelined = int(local_map), int(dynamic_mask), int(max_boxes), int(pipelined)
         self.detector = detector                                  # keeps the Detector2D wrapper (and its handle) alive
         h = C.c_void_p()
-        lib.check(lib.dll.sgx_tracker_create(C.byref(cfg), None if detector is None else detector.h, C.byref(h)), 'sgx_tracker_create')
+        if describe_early is not None:                            # tap builds only: the A/B arm that orients and describes every raw keypoint before the mask
+            lib.check(lib.tap('sgx_tracker_debug_set_describe_early')(int(bool(describe_early))))
+        try:
+            lib.check(lib.dll.sgx_tracker_create(C.byref(cfg), None if detector is None else detector.h, C.byref(h)), 'sgx_tracker_create')
+        finally:
+            if describe_early is not None: lib.tap('sgx_tracker_debug_set_describe_early')(-1)
         self.h = h
         self.cap = lib.dll.sgx_tracker_keypoint_capacity(h)
         self.rec_bytes = lib.dll.sgx_tracker_record_bytes(h)
@@ -96,6 +102,12 @@ class TrackerNative:
         p = C.c_void_p()
         self.lib.check(self.lib.dll.sgx_tracker_frame_keys_un_dev(self.h, C.byref(p)))
         return p.value
+
+    def debug_set_boxes(self, boxes, nboxes, have_dynamic):
+        """tap builds only, tracker without a detector: person rectangles (S, max_boxes, 4) as (x, y, w, h), their counts and the have-dynamic flags for the steps that follow"""
+        b = np.ascontiguousarray(boxes, 'f4').reshape(self.S, self.max_boxes, 4); nb = np.ascontiguousarray(nboxes, 'i4').reshape(self.S)
+        hv = np.ascontiguousarray(have_dynamic, 'i4').reshape(self.S)
+        self.lib.check(self.lib.tap('sgx_tracker_debug_set_boxes')(self.h, _vp(b), _vp(nb), _vp(hv)), 'sgx_tracker_debug_set_boxes')
 
     def last_status(self, stream=None):
         self.lib.check(self.lib.dll.sgx_orb_last_status(self.lib.dll.sgx_tracker_extractor(self.h), None if stream is None else C.c_void_p(stream)))

@@ -1,5 +1,5 @@
 """Kernel name -> bench.py per-kernel class (the sgx_profile_* classes of sgx_prof.h), shared by the PMC post-processing tools."""
-CLASS = [('k_pyramid', 'pyramid_resize'), ('k_resize', 'pyramid_resize'), ('k_gray_from_color', 'pyramid_resize'), ('k_fast_cells', 'fast_cells'), ('k_octree', 'octree'),
+CLASS = [('k_pyramid', 'pyramid_resize'), ('k_resize', 'pyramid_resize'), ('k_gray_from_color', 'pyramid_resize'), ('k_fast_cells', 'fast_cells'), ('k_octree_keys', 'octree'), ('k_octree', 'octree'),
          ('k_blur_levels', 'orient_desc'), ('k_orient_desc', 'orient_desc'),
          ('k_stereo_from_rgbd', 'stereo_from_rgbd'), ('k_motion_model', 'motion_model'), ('k_match_project_frame', 'match_project_frame'),
          ('k_match_project_local', 'match_project_local'), ('k_pose_opt', 'pose_opt'), ('k_unproject', 'unproject'),
