@@ -140,16 +140,18 @@ extern "C" int sgx_flow_lk(sgx_flow *h, const uint8_t *gray_from, const uint8_t 
     for (int y = 0; y < H; y++) { memcpy(&pack[(size_t)y * P], gray_to + (size_t)y * stride, (size_t)W); memcpy(&pack[(size_t)(H + y) * P], gray_from + (size_t)y * stride, (size_t)W); }
     std::vector<sgx_keypoint> kp((size_t)n);
     for (int i = 0; i < n; i++) { memset(&kp[(size_t)i], 0, sizeof(sgx_keypoint)); kp[(size_t)i].x = pts[2 * i]; kp[(size_t)i].y = pts[2 * i + 1]; }
-    SgxStaged dI, dK, dN, dO, dS;
+    SgxStaging st(SGX_STAGE_SHARED);
+    const uint8_t *dI = st.in(pack.data(), pack.size()); const sgx_keypoint *dK = st.in(kp.data(), kp.size()); const int32_t *dN = st.in(&n, 1);
+    float *dO = st.out<float>((size_t)n * 2); uint8_t *dS = st.out<uint8_t>(n);
+    if (st.rc != SGX_OK) return st.rc;
     int rc;
-    if ((rc = dI.put(0, pack.data(), pack.size())) != SGX_OK || (rc = dK.put(1, kp.data(), kp.size() * sizeof(sgx_keypoint))) != SGX_OK ||
-        (rc = dN.put(2, &n, sizeof n)) != SGX_OK || (rc = dO.put(3, nullptr, (size_t)n * 8)) != SGX_OK || (rc = dS.put(4, nullptr, (size_t)n)) != SGX_OK) return rc;
     const int keep_cur = h->cur, keep_prev = h->prev_batch;
-    if ((rc = build_pyramid(h, 1, (const uint8_t *)dI.p, P, 1, 0)) != SGX_OK) return rc;                        // to-image ("nextImg") -> slot 1
-    if ((rc = build_pyramid(h, 0, (const uint8_t *)dI.p + (size_t)P * H, P, 1, 0)) != SGX_OK) return rc;          // from-image -> slot 0
-    if ((rc = track(h, 0, 1, 1, (const sgx_keypoint *)dK.p, (const int32_t *)dN.p, n, (float *)dO.p, (uint8_t *)dS.p, 0)) != SGX_OK) return rc;
-    SGX_CHECK_HIP(hipMemcpy(next_pts, dO.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (status) SGX_CHECK_HIP(hipMemcpy(status, dS.p, (size_t)n, hipMemcpyDeviceToHost));
+    if ((rc = build_pyramid(h, 1, dI, P, 1, 0)) != SGX_OK) return rc;                        // to-image ("nextImg") -> slot 1
+    if ((rc = build_pyramid(h, 0, dI + (size_t)P * H, P, 1, 0)) != SGX_OK) return rc;          // from-image -> slot 0
+    if ((rc = track(h, 0, 1, 1, dK, dN, n, dO, dS, 0)) != SGX_OK) return rc;
+    st.back(next_pts, dO, (size_t)n * 2);
+    if (status) st.back(status, dS, n);
+    if (st.rc != SGX_OK) return st.rc;
     h->cur = keep_cur; h->prev_batch = 0; (void)keep_prev;       // the host call used both slots: the streaming state starts over
     return SGX_OK;
 }
@@ -245,16 +247,14 @@ extern "C" int sgx_find_fundamental_mat(const float *pts1, const float *pts2, in
     std::vector<sgx_keypoint> kp((size_t)cap);
     memset(kp.data(), 0, kp.size() * sizeof(sgx_keypoint));
     for (int i = 0; i < n; i++) { kp[(size_t)i].x = pts1[2 * i]; kp[(size_t)i].y = pts1[2 * i + 1]; }
-    SgxStaged dK, dN, dP, dF, dO, dS;
-    int rc;
-    if ((rc = dK.put(0, kp.data(), kp.size() * sizeof(sgx_keypoint))) != SGX_OK || (rc = dN.put(1, &n, sizeof n)) != SGX_OK ||
-        (rc = dP.put(2, n ? pts2 : nullptr, (size_t)cap * 8)) != SGX_OK || (rc = dF.put(3, nullptr, 72)) != SGX_OK || (rc = dO.put(4, nullptr, 4)) != SGX_OK ||
-        (rc = dS.put(5, nullptr, 16)) != SGX_OK) return rc;
-    rc = sgx_fundamental_ransac_batch_dev(1, cap, (const sgx_keypoint *)dK.p, (const int32_t *)dN.p, (const float *)dP.p, nullptr, nullptr, nullptr, 0, threshold, confidence,
-                                          (double *)dF.p, (int32_t *)dO.p, (int32_t *)dS.p, nullptr);
+    SgxStaging st(SGX_STAGE_SHARED);
+    const sgx_keypoint *dK = st.in(kp.data(), kp.size()); const int32_t *dN = st.in(&n, 1);
+    const float *dP = n ? st.in(pts2, (size_t)n * 2) : st.out<float>(2);          // cap points: with n == 0 one unread point
+    double *dF = st.out<double>(9); int32_t *dO = st.out<int32_t>(1), *dS = st.out<int32_t>(4);
+    if (st.rc != SGX_OK) return st.rc;
+    const int rc = sgx_fundamental_ransac_batch_dev(1, cap, dK, dN, dP, nullptr, nullptr, nullptr, 0, threshold, confidence, dF, dO, dS, nullptr);
     if (rc != SGX_OK) return rc;
-    SGX_CHECK_HIP(hipMemcpy(F, dF.p, 72, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(ok, dO.p, 4, hipMemcpyDeviceToHost));
-    if (stats) SGX_CHECK_HIP(hipMemcpy(stats, dS.p, 16, hipMemcpyDeviceToHost));
-    return SGX_OK;
+    st.back(F, dF, 9); st.back(ok, dO, 1);
+    if (stats) st.back(stats, dS, 4);
+    return st.rc;
 }

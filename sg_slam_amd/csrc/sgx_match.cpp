@@ -1,6 +1,7 @@
 // sgx_match.cpp — host side of the matcher / frame-glue C-ABI (include/sgx.h).
 // Reference behaviour: src/sg-slam/src/ORBmatcher.cc:1332-1472, src/sg-slam/src/Frame.cc:893-932.
 #include "sgx_match_kernels.h"
+#include "sgx_host_args.h"
 #include "sgx_prof.h"
 #include "sgx_stage.h"
 #include "../../include/sgx.h"
@@ -13,8 +14,6 @@
 #include <vector>
 
 
-static SgxCam to_cam(const sgx_camera *c) { SgxCam k; k.fx = c->fx; k.fy = c->fy; k.cx = c->cx; k.cy = c->cy; k.bf = c->bf; k.minX = c->min_x; k.maxX = c->max_x; k.minY = c->min_y; k.maxY = c->max_y; return k; }
-
 extern "C" int sgx_match_project_frame_batch_dev(
     int batch, int cap,
     const sgx_keypoint *d_ckeys, const uint8_t *d_cdesc, const float *d_curight, const int32_t *d_cn, const float *d_cTcw,
@@ -26,8 +25,7 @@ extern "C" int sgx_match_project_frame_batch_dev(
     if (batch < 1 || cap < 1 || cap > SGX_MATCH_CAP || !cam || !scale_factors || nlevels < 1 || nlevels > 12) return SGX_ERR_INVALID;
     if (!d_ckeys || !d_cdesc || !d_curight || !d_cn || !d_cTcw || !d_lkeys || !d_ln || !d_l_has_mp || !d_l_outlier || !d_l_xw ||
         !d_l_obs || !d_l_mpdesc || !d_lTcw || !d_cur_match || !d_nmatches) return SGX_ERR_INVALID;
-    SgxScales sc; memset(&sc, 0, sizeof sc);
-    for (int i = 0; i < nlevels; i++) sc.s[i] = scale_factors[i];
+    const SgxScales sc = to_scales(scale_factors, nlevels);
     sgx_prof_begin(SGX_K_MATCH, (sgx_stream_t)stream);
     static const int mthreads = sgx_getenv("SGX_TUNE_MATCH_THREADS") ? atoi(sgx_getenv("SGX_TUNE_MATCH_THREADS")) : SGX_MATCH_THREADS;   // env = tuning tap (64..1024)
     SGX_LAUNCH(k_match_project_frame, dim3(batch), dim3(mthreads), (sgx_stream_t)stream, cap,
@@ -74,8 +72,7 @@ extern "C" int sgx_match_project_local_batch_dev(
     if (batch < 1 || cap < 1 || cap > SGX_MATCH_CAP || mcap < 1 || mcap > SGX_LOCAL_CAP || !cam || !scale_factors || nlevels < 1 || nlevels > 12) return SGX_ERR_INVALID;
     if (!d_ckeys || !d_cdesc || !d_curight || !d_cn || !d_cTcw || !d_mn || !d_m_xw || !d_m_normal || !d_m_min_dist || !d_m_max_dist || !d_m_desc || !d_m_obs ||
         !d_m_skip || !d_cur_match || !d_nmatches || !d_in_view) return SGX_ERR_INVALID;
-    SgxScales sc; memset(&sc, 0, sizeof sc);
-    for (int i = 0; i < nlevels; i++) sc.s[i] = scale_factors[i];
+    const SgxScales sc = to_scales(scale_factors, nlevels);
     sgx_prof_begin(SGX_K_MATCH_LOCAL, (sgx_stream_t)stream);
     SGX_LAUNCH(k_match_project_local, dim3(batch), dim3(SGX_MATCH_THREADS), (sgx_stream_t)stream, cap, (const uint8_t *)d_ckeys, d_cdesc, d_curight, d_cn, d_cTcw,
                d_cur_mp_obs, mcap, d_mn, d_m_xw, d_m_normal, d_m_min_dist, d_m_max_dist, d_m_desc, d_m_obs, d_m_skip, to_cam(cam), sc, nlevels, log_scale_factor,
@@ -91,8 +88,7 @@ extern "C" int sgx_frame_make_map_points_batch_dev(int batch, int cap, int half,
 {
     if (batch < 1 || cap < 1 || half < 0 || half > 1 || !d_keys || !d_n || !d_xw || !d_has || !d_desc || !d_Tcw || !scale_factors || nlevels < 1 || nlevels > 12 ||
         !d_m_xw || !d_m_normal || !d_m_min_dist || !d_m_max_dist || !d_m_desc || !d_m_skip) return SGX_ERR_INVALID;
-    SgxScales sc; memset(&sc, 0, sizeof sc);
-    for (int i = 0; i < nlevels; i++) sc.s[i] = scale_factors[i];
+    const SgxScales sc = to_scales(scale_factors, nlevels);
     sgx_prof_begin(SGX_K_MAPGLUE, (sgx_stream_t)stream);
     SGX_LAUNCH(k_make_map_points, dim3((cap + 255) / 256, batch), dim3(256), (sgx_stream_t)stream, cap, half, (const uint8_t *)d_keys, d_n, d_xw, d_has, d_desc, d_Tcw, sc, nlevels,
                d_m_xw, d_m_normal, d_m_min_dist, d_m_max_dist, d_m_desc, d_m_skip);
@@ -125,14 +121,8 @@ extern "C" int sgx_frame_motion_model_batch_dev(int batch, const float *d_Tcw_cu
 }
 
 // Host-pointer, single pair: the drop-in for ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono).
-namespace {
-// device staging of the host-pointer entries: per-thread slots that persist from call to call (sgx_stage.h); slot ranges: frame matcher 0.., local matcher 20..
-struct DevBuf {
-    void *p = nullptr; int slot = 0;
-    int put(const void *src, size_t n) { SgxStaged s; const int rc = s.put(slot, src, n); p = s.p; return rc; }
-};
-}
-
+// Device staging of the host-pointer entries: per-thread slots that persist from call to call; this entry, sgx_match_project_local and sgx_pose_optimization
+// each have a slot range of their own (SGX_STAGE_*, sgx_stage.h).
 extern "C" int sgx_match_project_frame(
     int nc, const sgx_keypoint *ckeys, const uint8_t *cdesc, const float *curight, const float *cTcw,
     int nl, const sgx_keypoint *lkeys, const uint8_t *l_has_mp, const uint8_t *l_outlier, const float *l_xw,
@@ -144,37 +134,30 @@ extern "C" int sgx_match_project_frame(
     if (nc > 0 && (!ckeys || !cdesc || !curight)) return SGX_ERR_INVALID;
     if (nl > 0 && (!lkeys || !l_has_mp || !l_outlier || !l_xw || !l_obs || !l_mpdesc)) return SGX_ERR_INVALID;
     int cap = nc > nl ? nc : nl; if (cap < 1) cap = 1;
-    DevBuf b[16]; for (int i = 0; i < 16; i++) b[i].slot = i;
+    SgxStaging st(SGX_STAGE_FRAME_MATCH);
+    // the kernel reads `cap` elements of every array: each is zero-padded to cap through one host vector, so every upload has to finish before the next overwrites it
     std::vector<uint8_t> pad;
-    auto up = [&](int k, const void *src, size_t elem, int n) -> int {
+    auto padded = [&](auto *src, int per, int n) {
+        const size_t elem = (size_t)per * sizeof *src;
         pad.assign((size_t)cap * elem, 0);
         if (n > 0 && src) memcpy(pad.data(), src, (size_t)n * elem);
-        int rc = b[k].put(pad.data(), pad.size());
-        if (rc == SGX_OK && hipStreamSynchronize(0) != hipSuccess) rc = SGX_ERR_DEVICE;
-        return rc;
+        const uint8_t *d = st.in(pad.data(), pad.size());
+        if (st.rc == SGX_OK) st.hip(hipStreamSynchronize(0));
+        return (decltype(src))d;
     };
-    int rc;
-#define UP(k, src, elem, n) if ((rc = up(k, src, elem, n)) != SGX_OK) return rc
-    UP(0, ckeys, 28, nc); UP(1, cdesc, 32, nc); UP(2, curight, 4, nc); UP(3, lkeys, 28, nl); UP(4, l_has_mp, 1, nl); UP(5, l_outlier, 1, nl);
-    UP(6, l_xw, 12, nl); UP(7, l_obs, 4, nl); UP(8, l_mpdesc, 32, nl);
-#undef UP
-    if ((rc = b[9].put(&nc, 4)) != SGX_OK) return rc;
-    if ((rc = b[10].put(&nl, 4)) != SGX_OK) return rc;
-    if ((rc = b[11].put(cTcw, 64)) != SGX_OK) return rc;
-    if ((rc = b[12].put(lTcw, 64)) != SGX_OK) return rc;
-    if ((rc = b[13].put(nullptr, (size_t)cap * 4)) != SGX_OK) return rc;
-    if ((rc = b[14].put(nullptr, 4)) != SGX_OK) return rc;
+    const sgx_keypoint *d_ckeys = padded(ckeys, 1, nc); const uint8_t *d_cdesc = padded(cdesc, 32, nc); const float *d_curight = padded(curight, 1, nc);
+    const sgx_keypoint *d_lkeys = padded(lkeys, 1, nl); const uint8_t *d_has = padded(l_has_mp, 1, nl), *d_outlier = padded(l_outlier, 1, nl);
+    const float *d_lxw = padded(l_xw, 3, nl); const int32_t *d_lobs = padded(l_obs, 1, nl); const uint8_t *d_mpdesc = padded(l_mpdesc, 32, nl);
+    const int32_t *d_nc = st.in(&nc, 1), *d_nl = st.in(&nl, 1);
+    const float *d_cTcw = st.in(cTcw, 16), *d_lTcw = st.in(lTcw, 16);
+    int32_t *d_match = st.out<int32_t>(cap), *d_nmatches = st.out<int32_t>(1);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_CHECK_HIP(hipStreamSynchronize(0));
-    rc = sgx_match_project_frame_batch_dev(1, cap, (const sgx_keypoint *)b[0].p, (const uint8_t *)b[1].p, (const float *)b[2].p, (const int32_t *)b[9].p,
-                                           (const float *)b[11].p, (const sgx_keypoint *)b[3].p, (const int32_t *)b[10].p, (const uint8_t *)b[4].p,
-                                           (const uint8_t *)b[5].p, (const float *)b[6].p, (const int32_t *)b[7].p, (const uint8_t *)b[8].p,
-                                           (const float *)b[12].p, cam, scale_factors, nlevels, th, b_mono, check_orientation,
-                                           (int32_t *)b[13].p, (int32_t *)b[14].p, nullptr);
+    const int rc = sgx_match_project_frame_batch_dev(1, cap, d_ckeys, d_cdesc, d_curight, d_nc, d_cTcw, d_lkeys, d_nl, d_has, d_outlier, d_lxw, d_lobs, d_mpdesc, d_lTcw,
+                                                     cam, scale_factors, nlevels, th, b_mono, check_orientation, d_match, d_nmatches, nullptr);
     if (rc != SGX_OK) return rc;
-    SGX_CHECK_HIP(hipMemcpyAsync(cur_match, b[13].p, (size_t)nc * 4, hipMemcpyDeviceToHost, 0));
-    SGX_CHECK_HIP(hipMemcpyAsync(nmatches, b[14].p, 4, hipMemcpyDeviceToHost, 0));
-    SGX_CHECK_HIP(hipStreamSynchronize(0));
-    return SGX_OK;
+    st.back(cur_match, d_match, nc); st.back(nmatches, d_nmatches, 1);
+    return st.rc;
 }
 
 // Host pointers, one frame: the drop-in for Tracking::SearchLocalPoints' isInFrustum loop + ORBmatcher::SearchByProjection(Frame &F, vpMapPoints, th).
@@ -189,28 +172,23 @@ extern "C" int sgx_match_project_local(
     if (in_view) memset(in_view, 0, (size_t)nm);
     *nmatches = 0;
     if (nc == 0 || nm == 0) return SGX_OK;                       // the reference's loops do not execute (ORBmatcher.cc:52-127)
-    DevBuf b[18]; for (int i = 0; i < 18; i++) b[i].slot = 20 + i;
-    int rc;
     std::vector<int32_t> no_obs;
     if (!cur_mp_obs) { no_obs.assign((size_t)nc, -1); cur_mp_obs = no_obs.data(); }
-#define UP(k, src, bytes) if ((rc = b[k].put(src, (size_t)(bytes))) != SGX_OK) return rc
-    UP(0, ckeys, (size_t)nc * 28); UP(1, cdesc, (size_t)nc * 32); UP(2, curight, (size_t)nc * 4); UP(3, &nc, 4); UP(4, cTcw, 64); UP(5, cur_mp_obs, (size_t)nc * 4);
-    UP(6, &nm, 4); UP(7, m_xw, (size_t)nm * 12); UP(8, m_normal, (size_t)nm * 12); UP(9, m_min_dist, (size_t)nm * 4); UP(10, m_max_dist, (size_t)nm * 4);
-    UP(11, m_desc, (size_t)nm * 32); UP(12, m_obs, (size_t)nm * 4); UP(13, m_skip, (size_t)nm);
-    UP(14, nullptr, (size_t)nc * 4); UP(15, nullptr, 4); UP(16, nullptr, (size_t)nm);
-#undef UP
+    SgxStaging st(SGX_STAGE_LOCAL_MATCH);
+    const sgx_keypoint *d_ckeys = st.in(ckeys, nc); const uint8_t *d_cdesc = st.in(cdesc, (size_t)nc * 32); const float *d_curight = st.in(curight, nc);
+    const int32_t *d_nc = st.in(&nc, 1); const float *d_cTcw = st.in(cTcw, 16); const int32_t *d_obs = st.in(cur_mp_obs, nc);
+    const int32_t *d_nm = st.in(&nm, 1); const float *d_xw = st.in(m_xw, (size_t)nm * 3), *d_normal = st.in(m_normal, (size_t)nm * 3);
+    const float *d_min = st.in(m_min_dist, nm), *d_max = st.in(m_max_dist, nm);
+    const uint8_t *d_mdesc = st.in(m_desc, (size_t)nm * 32); const int32_t *d_mobs = st.in(m_obs, nm); const uint8_t *d_skip = st.in(m_skip, nm);
+    int32_t *d_match = st.out<int32_t>(nc), *d_nmatches = st.out<int32_t>(1); uint8_t *d_in_view = st.out<uint8_t>(nm);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_CHECK_HIP(hipStreamSynchronize(0));
-    rc = sgx_match_project_local_batch_dev(1, nc, (const sgx_keypoint *)b[0].p, (const uint8_t *)b[1].p, (const float *)b[2].p, (const int32_t *)b[3].p, (const float *)b[4].p,
-                                           (const int32_t *)b[5].p, nm, (const int32_t *)b[6].p, (const float *)b[7].p, (const float *)b[8].p, (const float *)b[9].p,
-                                           (const float *)b[10].p, (const uint8_t *)b[11].p, (const int32_t *)b[12].p, (const uint8_t *)b[13].p,
-                                           cam, scale_factors, nlevels, log_scale_factor, th, nnratio, viewing_cos_limit,
-                                           (int32_t *)b[14].p, (int32_t *)b[15].p, (uint8_t *)b[16].p, nullptr);
+    const int rc = sgx_match_project_local_batch_dev(1, nc, d_ckeys, d_cdesc, d_curight, d_nc, d_cTcw, d_obs, nm, d_nm, d_xw, d_normal, d_min, d_max, d_mdesc, d_mobs, d_skip,
+                                                     cam, scale_factors, nlevels, log_scale_factor, th, nnratio, viewing_cos_limit, d_match, d_nmatches, d_in_view, nullptr);
     if (rc != SGX_OK) return rc;
-    SGX_CHECK_HIP(hipMemcpyAsync(cur_match, b[14].p, (size_t)nc * 4, hipMemcpyDeviceToHost, 0));
-    SGX_CHECK_HIP(hipMemcpyAsync(nmatches, b[15].p, 4, hipMemcpyDeviceToHost, 0));
-    if (in_view) SGX_CHECK_HIP(hipMemcpyAsync(in_view, b[16].p, (size_t)nm, hipMemcpyDeviceToHost, 0));
-    SGX_CHECK_HIP(hipStreamSynchronize(0));
-    return SGX_OK;
+    st.back(cur_match, d_match, nc); st.back(nmatches, d_nmatches, 1);
+    if (in_view) st.back(in_view, d_in_view, nm);
+    return st.rc;
 }
 
 extern "C" int sgx_frame_gray_from_color_batch_dev(int batch, int width, int height, const uint8_t *d_src, int src_pitch, int channels, int blue_first,

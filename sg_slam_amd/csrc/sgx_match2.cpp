@@ -1,6 +1,8 @@
-// sgx_match2.cpp — host side of the LocalMapping matcher gates (include/sgx.h): sgx_hamming_matrix, sgx_match_search_for_triangulation.
+// sgx_match2.cpp — host side of the LocalMapping / LoopClosing / initialiser matcher gates and the MapPoint post-steps (include/sgx.h), host pointers, synchronous.
+// Every entry: validate, build the kernel argument struct, stage each buffer where its argument is set (SgxStaging, sgx_stage.h), launch, read back.
 // Reference behaviour: src/sg-slam/src/ORBmatcher.cc:659-827, :1649-1665.
 #include "sgx_match2_kernels.h"
+#include "sgx_host_args.h"
 #include "sgx_stage.h"
 #include "../../include/sgx.h"
 #ifdef SGX_DEBUG_TAPS
@@ -25,11 +27,14 @@ extern "C" int sgx_hamming_matrix(const uint8_t *desc_a, int na, const uint8_t *
 {
     if (na < 0 || nb < 0 || (na > 0 && !desc_a) || (nb > 0 && !desc_b) || (na > 0 && nb > 0 && !out)) return SGX_ERR_INVALID;
     if (na == 0 || nb == 0) return SGX_OK;
-    SgxStaged dA, dB, dO; int rc;
-    if ((rc = dA.put(0, desc_a, (size_t)na * 32)) != SGX_OK || (rc = dB.put(1, desc_b, (size_t)nb * 32)) != SGX_OK || (rc = dO.put(2, nullptr, (size_t)na * nb * 2)) != SGX_OK) return rc;
-    if ((rc = sgx_hamming_matrix_dev((const uint8_t *)dA.p, na, (const uint8_t *)dB.p, nb, (uint16_t *)dO.p, nullptr)) != SGX_OK) return rc;
-    SGX_CHECK_HIP(hipMemcpy(out, dO.p, (size_t)na * nb * 2, hipMemcpyDeviceToHost));
-    return SGX_OK;
+    SgxStaging st(SGX_STAGE_SHARED);
+    const uint8_t *dA = st.in(desc_a, (size_t)na * 32), *dB = st.in(desc_b, (size_t)nb * 32);
+    uint16_t *dO = st.out<uint16_t>((size_t)na * nb);
+    if (st.rc != SGX_OK) return st.rc;
+    const int rc = sgx_hamming_matrix_dev(dA, na, dB, nb, dO, nullptr);
+    if (rc != SGX_OK) return rc;
+    st.back(out, dO, (size_t)na * nb);
+    return st.rc;
 }
 
 // FeatureVector (std::map<NodeId, std::vector<unsigned>>) of one keyframe from the per-feature node ids: nodes ascending, feature indices ascending inside a node
@@ -42,11 +47,57 @@ static void group_by_node(const int32_t *node, int n, std::vector<int> &items, s
     start.push_back((int)items.size());
 }
 
+// the lock-step walk of the two FeatureVectors (ORBmatcher.cc:692-776, :184-281): one job (begin1, end1, begin2, end2 into items1 / items2) per node both keyframes have
+static std::vector<int> common_node_jobs(const int32_t *node1, int n1, std::vector<int> &items1, const int32_t *node2, int n2, std::vector<int> &items2)
+{
+    std::vector<int> id1, st1, id2, st2, job;
+    group_by_node(node1, n1, items1, id1, st1); group_by_node(node2, n2, items2, id2, st2);
+    for (size_t a = 0, b = 0; a < id1.size() && b < id2.size();) {
+        if (id1[a] == id2[b]) { job.push_back(st1[a]); job.push_back(st1[a + 1]); job.push_back(st2[b]); job.push_back(st2[b + 1]); a++; b++; }
+        else if (id1[a] < id2[b]) a++; else b++;
+    }
+    if (items1.empty()) items1.push_back(0);          // the kernels get no empty buffer: one unused element
+    if (items2.empty()) items2.push_back(0);
+    if (job.empty()) job.push_back(0);
+    return job;
+}
+
 // keypoint octaves index the per-level tables of the kernel arguments (12 entries): reject frames whose octaves fall outside the extractor's levels
 static bool octaves_ok(const sgx_keypoint *k, int n, int nlevels)
 {
     for (int i = 0; i < n; i++) if (k[i].octave < 0 || k[i].octave >= nlevels) return false;
     return true;
+}
+
+// Ow = -R.t() * t as one cv::Mat expression (ORBmatcher.cc:305, :994, :1480): the transpose flag takes the generic gemm, which accumulates in double and applies
+// alpha = -1 last.  Rows of R are rstride floats apart, elements of t tstride.
+static void camera_centre(const float *R, int rstride, const float *t, int tstride, float Ow[3])
+{
+    for (int i = 0; i < 3; i++) {
+        double s = 0; for (int k = 0; k < 3; k++) s += (double)R[rstride * k + i] * (double)t[tstride * k];
+        Ow[i] = (float)(s * -1.0);
+    }
+}
+
+// Frame::mGrid / KeyFrame::mGrid (KeyFrame.cc:39-47 copies Frame::mGrid, built by AssignFeaturesToGrid / PosInGrid with round(), Frame.cc:257-272, :409-419) as CSR:
+// cell (ix, iy) -> ix * SGX_GRID_ROWS + iy, index order inside a cell; `items` holds one unused element when no keypoint falls into the grid
+enum { SGX_GRID_COLS = 64, SGX_GRID_ROWS = 48, SGX_GRID_CELLS = SGX_GRID_COLS * SGX_GRID_ROWS };
+struct SgxKfGrid { std::vector<int> start, items; };
+static SgxKfGrid build_kf_grid(int n, const sgx_keypoint *keys, const SgxCam &cam)
+{
+    const float invW = (float)SGX_GRID_COLS / (cam.maxX - cam.minX), invH = (float)SGX_GRID_ROWS / (cam.maxY - cam.minY);
+    std::vector<int> cell((size_t)n, -1), fill(SGX_GRID_CELLS, 0);
+    SgxKfGrid g;
+    g.start.assign(SGX_GRID_CELLS + 1, 0);
+    for (int i = 0; i < n; i++) {
+        const int px = (int)round((keys[i].x - cam.minX) * invW), py = (int)round((keys[i].y - cam.minY) * invH);
+        if (px < 0 || px >= SGX_GRID_COLS || py < 0 || py >= SGX_GRID_ROWS) continue;
+        cell[(size_t)i] = px * SGX_GRID_ROWS + py; g.start[(size_t)cell[(size_t)i] + 1]++;
+    }
+    for (int c = 0; c < SGX_GRID_CELLS; c++) g.start[(size_t)c + 1] += g.start[(size_t)c];
+    g.items.assign(g.start[SGX_GRID_CELLS] > 0 ? (size_t)g.start[SGX_GRID_CELLS] : 1, 0);
+    for (int i = 0; i < n; i++) if (cell[(size_t)i] >= 0) g.items[(size_t)g.start[(size_t)cell[(size_t)i]] + fill[(size_t)cell[(size_t)i]]++] = i;
+    return g;
 }
 
 extern "C" int sgx_match_search_for_triangulation(
@@ -60,12 +111,8 @@ extern "C" int sgx_match_search_for_triangulation(
     if (n1 == 0 || n2 == 0) return SGX_OK;
     if (!keys1_un || !desc1 || !uright1 || !has_mp1 || !feat_node1 || !keys2_un || !desc2 || !uright2 || !has_mp2 || !feat_node2 || !pairs) return SGX_ERR_INVALID;
     if (!octaves_ok(keys1_un, n1, nlevels) || !octaves_ok(keys2_un, n2, nlevels)) return SGX_ERR_INVALID;
-    std::vector<int> it1, id1, st1, it2, id2, st2, job;
-    group_by_node(feat_node1, n1, it1, id1, st1); group_by_node(feat_node2, n2, it2, id2, st2);
-    for (size_t a = 0, b = 0; a < id1.size() && b < id2.size();) {               // the lock-step walk of the two maps (:692-776)
-        if (id1[a] == id2[b]) { job.push_back(st1[a]); job.push_back(st1[a + 1]); job.push_back(st2[b]); job.push_back(st2[b + 1]); a++; b++; }
-        else if (id1[a] < id2[b]) a++; else b++;
-    }
+    std::vector<int> it1, it2;
+    const std::vector<int> job = common_node_jobs(feat_node1, n1, it1, feat_node2, n2, it2);
     SgxTriArgs A; memset(&A, 0, sizeof A);
     A.n1 = n1; A.n2 = n2; A.nnodes = (int)(job.size() / 4);
     // epipole of KF1's centre in KF2 (:666-674): cv::Mat float products, left to right
@@ -79,25 +126,19 @@ extern "C" int sgx_match_search_for_triangulation(
         A.ex = cam2->fx * C2[0] * invz + cam2->cx; A.ey = cam2->fy * C2[1] * invz + cam2->cy;
     }
     for (int i = 0; i < 9; i++) A.F12[i] = F12[i];
-    for (int i = 0; i < nlevels; i++) { A.scale2.s[i] = scale_factors2[i]; A.sigma2_2.s[i] = level_sigma2_2[i]; }
+    A.scale2 = to_scales(scale_factors2, nlevels); A.sigma2_2 = to_scales(level_sigma2_2, nlevels);
     A.only_stereo = only_stereo; A.check_ori = check_orientation;
-    SgxStaged b[16]; int rc;
-    const int dummy = 0;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, keys1_un, (size_t)n1 * 28); PUT(1, desc1, (size_t)n1 * 32); PUT(2, uright1, (size_t)n1 * 4); PUT(3, has_mp1, (size_t)n1);
-    PUT(4, keys2_un, (size_t)n2 * 28); PUT(5, desc2, (size_t)n2 * 32); PUT(6, uright2, (size_t)n2 * 4); PUT(7, has_mp2, (size_t)n2);
-    PUT(8, it1.empty() ? &dummy : it1.data(), it1.empty() ? 4 : it1.size() * 4); PUT(9, it2.empty() ? &dummy : it2.data(), it2.empty() ? 4 : it2.size() * 4);
-    PUT(10, job.empty() ? &dummy : job.data(), job.empty() ? 4 : job.size() * 4);
-    PUT(11, nullptr, (size_t)n1 * 4); PUT(12, nullptr, (size_t)n2); PUT(13, nullptr, 4);
-#undef PUT
-    A.keys1 = (const uint8_t *)b[0].p; A.desc1 = (const uint32_t *)b[1].p; A.uright1 = (const float *)b[2].p; A.has_mp1 = (const uint8_t *)b[3].p;
-    A.keys2 = (const uint8_t *)b[4].p; A.desc2 = (const uint32_t *)b[5].p; A.uright2 = (const float *)b[6].p; A.has_mp2 = (const uint8_t *)b[7].p;
-    A.items1 = (const int *)b[8].p; A.items2 = (const int *)b[9].p; A.job = (const int *)b[10].p;
-    A.match12 = (int *)b[11].p; A.matched2 = (uint8_t *)b[12].p; A.nmatches = (int *)b[13].p;
+    SgxStaging st(SGX_STAGE_SHARED);
+    A.keys1 = st.keys(keys1_un, n1); A.desc1 = st.desc(desc1, n1); A.uright1 = st.in(uright1, n1); A.has_mp1 = st.in(has_mp1, n1);
+    A.keys2 = st.keys(keys2_un, n2); A.desc2 = st.desc(desc2, n2); A.uright2 = st.in(uright2, n2); A.has_mp2 = st.in(has_mp2, n2);
+    A.items1 = st.in(it1.data(), it1.size()); A.items2 = st.in(it2.data(), it2.size()); A.job = st.in(job.data(), job.size());
+    A.match12 = st.out<int>(n1); A.matched2 = st.out<uint8_t>(n2); A.nmatches = st.out<int>(1);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_LAUNCH(k_search_triangulation, dim3(1), dim3(256), (sgx_stream_t)0, A);
     SGX_CHECK_HIP(hipGetLastError());
     std::vector<int> m12((size_t)n1);
-    SGX_CHECK_HIP(hipMemcpy(m12.data(), A.match12, (size_t)n1 * 4, hipMemcpyDeviceToHost));
+    st.back(m12.data(), A.match12, n1);
+    if (st.rc != SGX_OK) return st.rc;
     int n = 0;
     for (int i = 0; i < n1; i++) if (m12[(size_t)i] >= 0) { pairs[2 * n] = i; pairs[2 * n + 1] = m12[(size_t)i]; n++; }      // vMatchedPairs in ascending idx1 (:815-822)
     *npairs = n;
@@ -110,31 +151,21 @@ static int search_by_bow_impl(
     int nf, const sgx_keypoint *keys_f_un, const uint8_t *desc_f, const uint8_t *good_f, const int32_t *feat_node_f, float nnratio, int check_orientation, int th_low,
     int32_t *match_f, int32_t *nmatches)
 {
-    std::vector<int> it1, id1, st1, it2, id2, st2, job;
-    group_by_node(feat_node_kf, nk, it1, id1, st1); group_by_node(feat_node_f, nf, it2, id2, st2);
-    for (size_t a = 0, b = 0; a < id1.size() && b < id2.size();) {
-        if (id1[a] == id2[b]) { job.push_back(st1[a]); job.push_back(st1[a + 1]); job.push_back(st2[b]); job.push_back(st2[b + 1]); a++; b++; }
-        else if (id1[a] < id2[b]) a++; else b++;
-    }
+    std::vector<int> it1, it2;
+    const std::vector<int> job = common_node_jobs(feat_node_kf, nk, it1, feat_node_f, nf, it2);
     SgxBowArgs A; memset(&A, 0, sizeof A);
     A.nk = nk; A.nf = nf; A.nnodes = (int)(job.size() / 4); A.nnratio = nnratio; A.check_ori = check_orientation; A.th_low = th_low;
-    SgxStaged b[12]; int rc; const int dummy = 0;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, keys_kf_un, (size_t)nk * 28); PUT(1, desc_kf, (size_t)nk * 32); PUT(2, kf_good_mp, (size_t)nk);
-    PUT(3, keys_f_un, (size_t)nf * 28); PUT(4, desc_f, (size_t)nf * 32);
-    PUT(5, it1.empty() ? &dummy : it1.data(), it1.empty() ? 4 : it1.size() * 4); PUT(6, it2.empty() ? &dummy : it2.data(), it2.empty() ? 4 : it2.size() * 4);
-    PUT(7, job.empty() ? &dummy : job.data(), job.empty() ? 4 : job.size() * 4);
-    PUT(8, nullptr, (size_t)nf * 4); PUT(9, nullptr, 4);
-    if (good_f) { PUT(10, good_f, (size_t)nf); A.good_f = (const uint8_t *)b[10].p; }
-#undef PUT
-    A.keys_k = (const uint8_t *)b[0].p; A.desc_k = (const uint32_t *)b[1].p; A.good_k = (const uint8_t *)b[2].p;
-    A.keys_f = (const uint8_t *)b[3].p; A.desc_f = (const uint32_t *)b[4].p;
-    A.items_k = (const int *)b[5].p; A.items_f = (const int *)b[6].p; A.job = (const int *)b[7].p; A.match_f = (int *)b[8].p; A.nmatches = (int *)b[9].p;
+    SgxStaging st(SGX_STAGE_SHARED);
+    A.keys_k = st.keys(keys_kf_un, nk); A.desc_k = st.desc(desc_kf, nk); A.good_k = st.in(kf_good_mp, nk);
+    A.keys_f = st.keys(keys_f_un, nf); A.desc_f = st.desc(desc_f, nf);
+    A.items_k = st.in(it1.data(), it1.size()); A.items_f = st.in(it2.data(), it2.size()); A.job = st.in(job.data(), job.size());
+    A.match_f = st.out<int>(nf); A.nmatches = st.out<int>(1);
+    if (good_f) A.good_f = st.in(good_f, nf);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_LAUNCH(k_search_bow, dim3(1), dim3(256), (sgx_stream_t)0, A);
     SGX_CHECK_HIP(hipGetLastError());
-    SGX_CHECK_HIP(hipMemcpy(match_f, A.match_f, (size_t)nf * 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(nmatches, A.nmatches, 4, hipMemcpyDeviceToHost));
-    return SGX_OK;
+    st.back(match_f, A.match_f, nf); st.back(nmatches, A.nmatches, 1);
+    return st.rc;
 }
 
 extern "C" int sgx_match_search_by_bow(
@@ -179,37 +210,24 @@ extern "C" int sgx_match_fuse_search(
     if (nk == 0 || nm == 0) return SGX_OK;
     if (!keys_un || !desc || !uright || !m_xw || !m_normal || !m_min_dist || !m_max_dist || !m_desc || !m_skip) return SGX_ERR_INVALID;
     if (!octaves_ok(keys_un, nk, nlevels)) return SGX_ERR_INVALID;
-    // the keyframe's mGrid (Frame::AssignFeaturesToGrid / PosInGrid: round(), Frame.cc:257-272, :409-419) as CSR, cell (ix, iy) -> ix * 48 + iy, insertion (index) order inside a cell
-    const float invW = 64.0f / (cam->max_x - cam->min_x), invH = 48.0f / (cam->max_y - cam->min_y);
-    std::vector<int> cell((size_t)nk, -1), start(64 * 48 + 1, 0), items;
-    for (int i = 0; i < nk; i++) {
-        const int px = (int)round((keys_un[i].x - cam->min_x) * invW), py = (int)round((keys_un[i].y - cam->min_y) * invH);
-        if (px < 0 || px >= 64 || py < 0 || py >= 48) continue;
-        cell[(size_t)i] = px * 48 + py; start[(size_t)cell[(size_t)i] + 1]++;
-    }
-    for (int c = 0; c < 64 * 48; c++) start[(size_t)c + 1] += start[(size_t)c];
-    items.resize((size_t)start[64 * 48] > 0 ? (size_t)start[64 * 48] : 1);
-    { std::vector<int> fill(64 * 48, 0); for (int i = 0; i < nk; i++) if (cell[(size_t)i] >= 0) items[(size_t)start[(size_t)cell[(size_t)i]] + fill[(size_t)cell[(size_t)i]]++] = i; }
     SgxFuseArgs A; memset(&A, 0, sizeof A);
     A.nk = nk; A.nm = nm; A.nlevels = nlevels; A.log_scale_factor = log_scale_factor; A.th = th;
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) A.Rcw[r][c] = Tcw[4 * r + c]; A.tcw[r] = Tcw[4 * r + 3]; }
+    // deliberately the float form, not camera_centre(): Fuse reads pKF->GetCameraCenter() (ORBmatcher.cc:840), a float product on a stored transpose; test_fuse_search_* pins it against the oracle
     for (int r = 0; r < 3; r++) A.Ow[r] = -(A.Rcw[0][r] * A.tcw[0] + A.Rcw[1][r] * A.tcw[1] + A.Rcw[2][r] * A.tcw[2]);
-    A.cam.fx = cam->fx; A.cam.fy = cam->fy; A.cam.cx = cam->cx; A.cam.cy = cam->cy; A.cam.bf = cam->bf; A.cam.minX = cam->min_x; A.cam.maxX = cam->max_x; A.cam.minY = cam->min_y; A.cam.maxY = cam->max_y;
-    for (int i = 0; i < nlevels; i++) { A.scale.s[i] = scale_factors[i]; A.inv_sigma2.s[i] = inv_level_sigma2[i]; }
-    SgxStaged b[14]; int rc;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, keys_un, (size_t)nk * 28); PUT(1, desc, (size_t)nk * 32); PUT(2, uright, (size_t)nk * 4);
-    PUT(3, start.data(), start.size() * 4); PUT(4, items.data(), items.size() * 4);
-    PUT(5, m_xw, (size_t)nm * 12); PUT(6, m_normal, (size_t)nm * 12); PUT(7, m_min_dist, (size_t)nm * 4); PUT(8, m_max_dist, (size_t)nm * 4); PUT(9, m_desc, (size_t)nm * 32); PUT(10, m_skip, (size_t)nm);
-    PUT(11, nullptr, (size_t)nm * 4); PUT(12, nullptr, (size_t)nm * 4);
-#undef PUT
-    A.keys = (const uint8_t *)b[0].p; A.desc = (const uint32_t *)b[1].p; A.uright = (const float *)b[2].p; A.cell_start = (const int *)b[3].p; A.cell_items = (const int *)b[4].p;
-    A.m_xw = (const float *)b[5].p; A.m_normal = (const float *)b[6].p; A.m_min_dist = (const float *)b[7].p; A.m_max_dist = (const float *)b[8].p;
-    A.m_desc = (const uint32_t *)b[9].p; A.m_skip = (const uint8_t *)b[10].p; A.best_idx = (int *)b[11].p; A.best_dist = (int *)b[12].p;
+    A.cam = to_cam(cam); A.scale = to_scales(scale_factors, nlevels); A.inv_sigma2 = to_scales(inv_level_sigma2, nlevels);
+    const SgxKfGrid g = build_kf_grid(nk, keys_un, A.cam);                 // the keyframe's mGrid
+    SgxStaging st(SGX_STAGE_SHARED);
+    A.keys = st.keys(keys_un, nk); A.desc = st.desc(desc, nk); A.uright = st.in(uright, nk);
+    A.cell_start = st.in(g.start.data(), g.start.size()); A.cell_items = st.in(g.items.data(), g.items.size());
+    A.m_xw = st.in(m_xw, (size_t)nm * 3); A.m_normal = st.in(m_normal, (size_t)nm * 3); A.m_min_dist = st.in(m_min_dist, nm); A.m_max_dist = st.in(m_max_dist, nm);
+    A.m_desc = st.desc(m_desc, nm); A.m_skip = st.in(m_skip, nm);
+    A.best_idx = st.out<int>(nm); A.best_dist = st.out<int>(nm);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_LAUNCH(k_fuse_search, dim3((nm + 255) / 256), dim3(256), (sgx_stream_t)0, A);
     SGX_CHECK_HIP(hipGetLastError());
-    SGX_CHECK_HIP(hipMemcpy(best_idx, A.best_idx, (size_t)nm * 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(best_dist, A.best_dist, (size_t)nm * 4, hipMemcpyDeviceToHost));
+    st.back(best_idx, A.best_idx, nm); st.back(best_dist, A.best_dist, nm);
+    if (st.rc != SGX_OK) return st.rc;
     int n = 0; for (int i = 0; i < nm; i++) n += best_idx[i] >= 0;
     *nfused = n;
     return SGX_OK;
@@ -226,80 +244,40 @@ extern "C" int sgx_match_project_keyframe(
     for (int k = 0; k < nc; k++) cur_match[k] = -1;
     if (nc == 0 || nk == 0) return SGX_OK;
     if (!ckeys_un || !cdesc || !c_has_mp || !kf_keys_un || !kf_ok || !m_xw || !m_min_dist || !m_max_dist || !m_desc) return SGX_ERR_INVALID;
-    // CurrentFrame.mGrid (AssignFeaturesToGrid / PosInGrid: round(), Frame.cc:257-272, :409-419) as CSR, cell (ix, iy) -> ix * 48 + iy, index order inside a cell
-    const float invW = 64.0f / (cam->max_x - cam->min_x), invH = 48.0f / (cam->max_y - cam->min_y);
-    std::vector<int> cell((size_t)nc, -1), start(64 * 48 + 1, 0), items;
-    for (int i = 0; i < nc; i++) {
-        const int px = (int)round((ckeys_un[i].x - cam->min_x) * invW), py = (int)round((ckeys_un[i].y - cam->min_y) * invH);
-        if (px < 0 || px >= 64 || py < 0 || py >= 48) continue;
-        cell[(size_t)i] = px * 48 + py; start[(size_t)cell[(size_t)i] + 1]++;
-    }
-    for (int c = 0; c < 64 * 48; c++) start[(size_t)c + 1] += start[(size_t)c];
-    items.resize((size_t)start[64 * 48] > 0 ? (size_t)start[64 * 48] : 1);
-    { std::vector<int> fill(64 * 48, 0); for (int i = 0; i < nc; i++) if (cell[(size_t)i] >= 0) items[(size_t)start[(size_t)cell[(size_t)i]] + fill[(size_t)cell[(size_t)i]]++] = i; }
     SgxKfProjArgs A; memset(&A, 0, sizeof A);
     A.nc = nc; A.nk = nk; A.nlevels = nlevels; A.orb_dist = orb_dist; A.check_ori = check_orientation; A.log_scale_factor = log_scale_factor; A.th = th;
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) A.Rcw[r][c] = cTcw[4 * r + c]; A.tcw[r] = cTcw[4 * r + 3]; }
-    for (int i = 0; i < 3; i++) {                       // Ow = -Rcw.t()*tcw: transpose flag -> generic gemm, double accumulation, alpha = -1
-        double s = 0; for (int k = 0; k < 3; k++) s += (double)A.Rcw[k][i] * (double)A.tcw[k];
-        A.Ow[i] = (float)(s * -1.0);
-    }
-    A.cam.fx = cam->fx; A.cam.fy = cam->fy; A.cam.cx = cam->cx; A.cam.cy = cam->cy; A.cam.bf = cam->bf; A.cam.minX = cam->min_x; A.cam.maxX = cam->max_x; A.cam.minY = cam->min_y; A.cam.maxY = cam->max_y;
-    for (int i = 0; i < nlevels; i++) A.scale.s[i] = scale_factors[i];
-    SgxStaged b[18]; int rc;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, ckeys_un, (size_t)nc * 28); PUT(1, cdesc, (size_t)nc * 32); PUT(2, c_has_mp, (size_t)nc); PUT(3, start.data(), start.size() * 4); PUT(4, items.data(), items.size() * 4);
-    PUT(5, kf_keys_un, (size_t)nk * 28); PUT(6, kf_ok, (size_t)nk); PUT(7, m_xw, (size_t)nk * 12); PUT(8, m_min_dist, (size_t)nk * 4); PUT(9, m_max_dist, (size_t)nk * 4); PUT(10, m_desc, (size_t)nk * 32);
-    PUT(11, nullptr, (size_t)nc * 4); PUT(12, nullptr, (size_t)nc * 4); PUT(13, nullptr, (size_t)nk * 4); PUT(14, nullptr, (size_t)nc * 4); PUT(15, nullptr, 4);
-#undef PUT
-    A.ckeys = (const uint8_t *)b[0].p; A.cdesc = (const uint32_t *)b[1].p; A.c_has_mp = (const uint8_t *)b[2].p; A.cell_start = (const int *)b[3].p; A.cell_items = (const int *)b[4].p;
-    A.kf_keys = (const uint8_t *)b[5].p; A.kf_ok = (const uint8_t *)b[6].p; A.m_xw = (const float *)b[7].p; A.m_min_dist = (const float *)b[8].p; A.m_max_dist = (const float *)b[9].p;
-    A.m_desc = (const uint32_t *)b[10].p; A.lock_a = (int *)b[11].p; A.lock_b = (int *)b[12].p; A.choice = (int *)b[13].p; A.cur_match = (int *)b[14].p; A.nmatches = (int *)b[15].p;
+    camera_centre(&A.Rcw[0][0], 3, A.tcw, 1, A.Ow);
+    A.cam = to_cam(cam); A.scale = to_scales(scale_factors, nlevels);
+    const SgxKfGrid g = build_kf_grid(nc, ckeys_un, A.cam);                // CurrentFrame.mGrid
+    SgxStaging st(SGX_STAGE_SHARED);
+    A.ckeys = st.keys(ckeys_un, nc); A.cdesc = st.desc(cdesc, nc); A.c_has_mp = st.in(c_has_mp, nc);
+    A.cell_start = st.in(g.start.data(), g.start.size()); A.cell_items = st.in(g.items.data(), g.items.size());
+    A.kf_keys = st.keys(kf_keys_un, nk); A.kf_ok = st.in(kf_ok, nk); A.m_xw = st.in(m_xw, (size_t)nk * 3); A.m_min_dist = st.in(m_min_dist, nk); A.m_max_dist = st.in(m_max_dist, nk);
+    A.m_desc = st.desc(m_desc, nk);
+    A.lock_a = st.out<int>(nc); A.lock_b = st.out<int>(nc); A.choice = st.out<int>(nk); A.cur_match = st.out<int>(nc); A.nmatches = st.out<int>(1);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_LAUNCH(k_match_project_kf, dim3(1), dim3(1024), (sgx_stream_t)0, A);
     SGX_CHECK_HIP(hipGetLastError());
-    SGX_CHECK_HIP(hipMemcpy(cur_match, A.cur_match, (size_t)nc * 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(nmatches, A.nmatches, 4, hipMemcpyDeviceToHost));
-    return SGX_OK;
+    st.back(cur_match, A.cur_match, nc); st.back(nmatches, A.nmatches, 1);
+    return st.rc;
 }
 
 // ---- loop-closing matchers that project through a Sim3 -------------------------------------------------------------------------------------------------------------
 
-// KeyFrame::mGrid (KeyFrame.cc:39-47 copies Frame::mGrid, built by AssignFeaturesToGrid / PosInGrid with round(), Frame.cc:257-272, :409-419) as CSR:
-// cell (ix, iy) -> ix * 48 + iy, index order inside a cell
-static void build_kf_grid(int n, const sgx_keypoint *keys, const sgx_camera *cam, std::vector<int> &start, std::vector<int> &items)
-{
-    const float invW = 64.0f / (cam->max_x - cam->min_x), invH = 48.0f / (cam->max_y - cam->min_y);
-    std::vector<int> cell((size_t)n, -1);
-    start.assign(64 * 48 + 1, 0);
-    for (int i = 0; i < n; i++) {
-        const int px = (int)round((keys[i].x - cam->min_x) * invW), py = (int)round((keys[i].y - cam->min_y) * invH);
-        if (px < 0 || px >= 64 || py < 0 || py >= 48) continue;
-        cell[(size_t)i] = px * 48 + py; start[(size_t)cell[(size_t)i] + 1]++;
-    }
-    for (int c = 0; c < 64 * 48; c++) start[(size_t)c + 1] += start[(size_t)c];
-    items.assign((size_t)start[64 * 48] > 0 ? (size_t)start[64 * 48] : 1, 0);
-    std::vector<int> fill(64 * 48, 0);
-    for (int i = 0; i < n; i++) if (cell[(size_t)i] >= 0) items[(size_t)start[(size_t)cell[(size_t)i]] + fill[(size_t)cell[(size_t)i]]++] = i;
-}
-
-// "Decompose Scw" (ORBmatcher.cc:301-306, :990-995).  cv::Mat arithmetic: Mat::dot accumulates in double; Mat / double is a convertTo by the float of 1/scw;
-// -Rcw.t() * tcw is a gemm with a transpose flag (double accumulation, alpha = -1).
+// "Decompose Scw" (ORBmatcher.cc:301-306, :990-995).  cv::Mat arithmetic: Mat::dot accumulates in double; Mat / double is a convertTo by the float of 1/scw
 static void decompose_scw(const float *Scw, float R[3][3], float t[3], float Ow[3])
 {
     double s = 0; for (int c = 0; c < 3; c++) s += (double)Scw[c] * (double)Scw[c];
     const float scw = (float)sqrt(s), inv = (float)(1.0 / (double)scw);
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[r][c] = Scw[4 * r + c] * inv; t[r] = Scw[4 * r + 3] * inv; }
-    for (int i = 0; i < 3; i++) {
-        double a = 0; for (int k = 0; k < 3; k++) a += (double)R[k][i] * (double)t[k];
-        Ow[i] = (float)(a * -1.0);
-    }
+    camera_centre(&R[0][0], 3, t, 1, Ow);
 }
 
 static void sim3_fill_common(SgxSim3ProjArgs &A, const sgx_camera *cam, const float *scale_factors, int nlevels, float log_scale_factor, float th)
 {
     A.nlevels = nlevels; A.log_scale_factor = log_scale_factor; A.th = th;
-    A.cam.fx = cam->fx; A.cam.fy = cam->fy; A.cam.cx = cam->cx; A.cam.cy = cam->cy; A.cam.bf = cam->bf; A.cam.minX = cam->min_x; A.cam.maxX = cam->max_x; A.cam.minY = cam->min_y; A.cam.maxY = cam->max_y;
-    for (int i = 0; i < nlevels; i++) A.scale.s[i] = scale_factors[i];
+    A.cam = to_cam(cam); A.scale = to_scales(scale_factors, nlevels);
 }
 
 extern "C" int sgx_match_fuse_search_sim3(
@@ -313,25 +291,20 @@ extern "C" int sgx_match_fuse_search_sim3(
     for (int i = 0; i < nm; i++) { best_idx[i] = -1; best_dist[i] = 256; }
     if (nk == 0 || nm == 0) return SGX_OK;
     if (!keys_un || !desc || !m_xw || !m_normal || !m_min_dist || !m_max_dist || !m_desc || !m_skip) return SGX_ERR_INVALID;
-    std::vector<int> start, items;
-    build_kf_grid(nk, keys_un, cam, start, items);
     SgxSim3ProjArgs A; memset(&A, 0, sizeof A);
     A.nk = nk; A.nm = nm; A.flags = SGX_S3_NORMAL; A.th_accept = SGX_TH_LOW;
     sim3_fill_common(A, cam, scale_factors, nlevels, log_scale_factor, th);
     decompose_scw(Scw, A.R1, A.t1, A.Ow);
-    SgxStaged b[12]; int rc;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, keys_un, (size_t)nk * 28); PUT(1, desc, (size_t)nk * 32); PUT(2, start.data(), start.size() * 4); PUT(3, items.data(), items.size() * 4);
-    PUT(4, m_xw, (size_t)nm * 12); PUT(5, m_normal, (size_t)nm * 12); PUT(6, m_min_dist, (size_t)nm * 4); PUT(7, m_max_dist, (size_t)nm * 4); PUT(8, m_desc, (size_t)nm * 32); PUT(9, m_skip, (size_t)nm);
-    PUT(10, nullptr, (size_t)nm * 4); PUT(11, nullptr, (size_t)nm * 4);
-#undef PUT
-    A.keys = (const uint8_t *)b[0].p; A.desc = (const uint32_t *)b[1].p; A.cell_start = (const int *)b[2].p; A.cell_items = (const int *)b[3].p;
-    A.m_xw = (const float *)b[4].p; A.m_normal = (const float *)b[5].p; A.m_min_dist = (const float *)b[6].p; A.m_max_dist = (const float *)b[7].p;
-    A.m_desc = (const uint32_t *)b[8].p; A.m_skip = (const uint8_t *)b[9].p; A.best_idx = (int *)b[10].p; A.best_dist = (int *)b[11].p;
+    const SgxKfGrid g = build_kf_grid(nk, keys_un, A.cam);
+    SgxStaging st(SGX_STAGE_SHARED);
+    A.keys = st.keys(keys_un, nk); A.desc = st.desc(desc, nk); A.cell_start = st.in(g.start.data(), g.start.size()); A.cell_items = st.in(g.items.data(), g.items.size());
+    A.m_xw = st.in(m_xw, (size_t)nm * 3); A.m_normal = st.in(m_normal, (size_t)nm * 3); A.m_min_dist = st.in(m_min_dist, nm); A.m_max_dist = st.in(m_max_dist, nm);
+    A.m_desc = st.desc(m_desc, nm); A.m_skip = st.in(m_skip, nm); A.best_idx = st.out<int>(nm); A.best_dist = st.out<int>(nm);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_LAUNCH(k_sim3_search, dim3((nm + 255) / 256), dim3(256), (sgx_stream_t)0, A);
     SGX_CHECK_HIP(hipGetLastError());
-    SGX_CHECK_HIP(hipMemcpy(best_idx, A.best_idx, (size_t)nm * 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(best_dist, A.best_dist, (size_t)nm * 4, hipMemcpyDeviceToHost));
+    st.back(best_idx, A.best_idx, nm); st.back(best_dist, A.best_dist, nm);
+    if (st.rc != SGX_OK) return st.rc;
     int n = 0; for (int i = 0; i < nm; i++) n += best_idx[i] >= 0;
     *nfused = n;
     return SGX_OK;
@@ -348,28 +321,21 @@ extern "C" int sgx_match_project_sim3(
     for (int k = 0; k < nk; k++) matched_out[k] = -1;
     if (nk == 0 || nm == 0) return SGX_OK;
     if (!keys_un || !desc || !matched_in || !m_xw || !m_normal || !m_min_dist || !m_max_dist || !m_desc || !m_skip) return SGX_ERR_INVALID;
-    std::vector<int> start, items;
-    build_kf_grid(nk, keys_un, cam, start, items);
     SgxSim3ProjArgs A; memset(&A, 0, sizeof A);
     A.nk = nk; A.nm = nm; A.flags = SGX_S3_NORMAL | SGX_S3_FLOAT_INVZ; A.th_accept = SGX_TH_LOW;
     sim3_fill_common(A, cam, scale_factors, nlevels, log_scale_factor, (float)th);
     decompose_scw(Scw, A.R1, A.t1, A.Ow);
-    SgxStaged b[17]; int rc;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, keys_un, (size_t)nk * 28); PUT(1, desc, (size_t)nk * 32); PUT(2, start.data(), start.size() * 4); PUT(3, items.data(), items.size() * 4);
-    PUT(4, m_xw, (size_t)nm * 12); PUT(5, m_normal, (size_t)nm * 12); PUT(6, m_min_dist, (size_t)nm * 4); PUT(7, m_max_dist, (size_t)nm * 4); PUT(8, m_desc, (size_t)nm * 32); PUT(9, m_skip, (size_t)nm);
-    PUT(10, nullptr, (size_t)nm * 4); PUT(11, nullptr, (size_t)nm * 4);
-    PUT(12, matched_in, (size_t)nk); PUT(13, nullptr, (size_t)nk * 4); PUT(14, nullptr, (size_t)nk * 4); PUT(15, nullptr, (size_t)nk * 4); PUT(16, nullptr, 4);
-#undef PUT
-    A.keys = (const uint8_t *)b[0].p; A.desc = (const uint32_t *)b[1].p; A.cell_start = (const int *)b[2].p; A.cell_items = (const int *)b[3].p;
-    A.m_xw = (const float *)b[4].p; A.m_normal = (const float *)b[5].p; A.m_min_dist = (const float *)b[6].p; A.m_max_dist = (const float *)b[7].p;
-    A.m_desc = (const uint32_t *)b[8].p; A.m_skip = (const uint8_t *)b[9].p; A.best_idx = (int *)b[10].p; A.best_dist = (int *)b[11].p;
-    A.taken_in = (const uint8_t *)b[12].p; A.lock_a = (int *)b[13].p; A.lock_b = (int *)b[14].p; A.matched_out = (int *)b[15].p; A.nmatches = (int *)b[16].p;
+    const SgxKfGrid g = build_kf_grid(nk, keys_un, A.cam);
+    SgxStaging st(SGX_STAGE_SHARED);
+    A.keys = st.keys(keys_un, nk); A.desc = st.desc(desc, nk); A.cell_start = st.in(g.start.data(), g.start.size()); A.cell_items = st.in(g.items.data(), g.items.size());
+    A.m_xw = st.in(m_xw, (size_t)nm * 3); A.m_normal = st.in(m_normal, (size_t)nm * 3); A.m_min_dist = st.in(m_min_dist, nm); A.m_max_dist = st.in(m_max_dist, nm);
+    A.m_desc = st.desc(m_desc, nm); A.m_skip = st.in(m_skip, nm); A.best_idx = st.out<int>(nm); A.best_dist = st.out<int>(nm);
+    A.taken_in = st.in(matched_in, nk); A.lock_a = st.out<int>(nk); A.lock_b = st.out<int>(nk); A.matched_out = st.out<int>(nk); A.nmatches = st.out<int>(1);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_LAUNCH(k_sim3_search_locked, dim3(1), dim3(1024), (sgx_stream_t)0, A);
     SGX_CHECK_HIP(hipGetLastError());
-    SGX_CHECK_HIP(hipMemcpy(matched_out, A.matched_out, (size_t)nk * 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(nmatches, A.nmatches, 4, hipMemcpyDeviceToHost));
-    return SGX_OK;
+    st.back(matched_out, A.matched_out, nk); st.back(nmatches, A.nmatches, 1);
+    return st.rc;
 }
 
 extern "C" int sgx_match_search_by_sim3(
@@ -394,39 +360,32 @@ extern "C" int sgx_match_search_by_sim3(
     const float inv_s = (float)(1.0 / (double)s12);
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { sR12[r][c] = R12[3 * r + c] * s12; sR21[r][c] = R12[3 * c + r] * inv_s; }
     for (int r = 0; r < 3; r++) { const float t = sR21[r][0] * t12[0] + sR21[r][1] * t12[1] + sR21[r][2] * t12[2]; t21[r] = (float)((double)t * -1.0 + 0.0); }
-    std::vector<int> start1, items1, start2, items2;
-    build_kf_grid(n1, keys1_un, cam, start1, items1); build_kf_grid(n2, keys2_un, cam, start2, items2);
-    SgxStaged b[24]; int rc;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, keys1_un, (size_t)n1 * 28); PUT(1, desc1, (size_t)n1 * 32); PUT(2, start1.data(), start1.size() * 4); PUT(3, items1.data(), items1.size() * 4);
-    PUT(4, m_xw1, (size_t)n1 * 12); PUT(5, m_min_dist1, (size_t)n1 * 4); PUT(6, m_max_dist1, (size_t)n1 * 4); PUT(7, m_desc1, (size_t)n1 * 32); PUT(8, skip1.data(), (size_t)n1);
-    PUT(9, nullptr, (size_t)n1 * 4); PUT(10, nullptr, (size_t)n1 * 4);
-    PUT(11, keys2_un, (size_t)n2 * 28); PUT(12, desc2, (size_t)n2 * 32); PUT(13, start2.data(), start2.size() * 4); PUT(14, items2.data(), items2.size() * 4);
-    PUT(15, m_xw2, (size_t)n2 * 12); PUT(16, m_min_dist2, (size_t)n2 * 4); PUT(17, m_max_dist2, (size_t)n2 * 4); PUT(18, m_desc2, (size_t)n2 * 32); PUT(19, skip2.data(), (size_t)n2);
-    PUT(20, nullptr, (size_t)n2 * 4); PUT(21, nullptr, (size_t)n2 * 4);
-#undef PUT
+    // A: KF1's points into KF2 (:1150-1224); B: KF2's points into KF1 (:1227-1301)
     SgxSim3ProjArgs A; memset(&A, 0, sizeof A);
     A.flags = SGX_S3_TWO_STEP | SGX_S3_CAM_DIST; A.th_accept = SGX_TH_HIGH;
     sim3_fill_common(A, cam, scale_factors, nlevels, log_scale_factor, th);
     SgxSim3ProjArgs B = A;
-    // KF1's points into KF2 (:1150-1224)
-    A.nk = n2; A.nm = n1;
+    A.nk = n2; A.nm = n1; B.nk = n1; B.nm = n2;
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) { A.R1[r][c] = Tcw1[4 * r + c]; A.R2[r][c] = sR21[r][c]; } A.t1[r] = Tcw1[4 * r + 3]; A.t2[r] = t21[r]; }
-    A.keys = (const uint8_t *)b[11].p; A.desc = (const uint32_t *)b[12].p; A.cell_start = (const int *)b[13].p; A.cell_items = (const int *)b[14].p;
-    A.m_xw = (const float *)b[4].p; A.m_min_dist = (const float *)b[5].p; A.m_max_dist = (const float *)b[6].p; A.m_desc = (const uint32_t *)b[7].p; A.m_skip = (const uint8_t *)b[8].p;
-    A.best_idx = (int *)b[9].p; A.best_dist = (int *)b[10].p;
-    SGX_LAUNCH(k_sim3_search, dim3((n1 + 255) / 256), dim3(256), (sgx_stream_t)0, A);
-    // KF2's points into KF1 (:1227-1301)
-    B.nk = n1; B.nm = n2;
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) { B.R1[r][c] = Tcw2[4 * r + c]; B.R2[r][c] = sR12[r][c]; } B.t1[r] = Tcw2[4 * r + 3]; B.t2[r] = t12[r]; }
-    B.keys = (const uint8_t *)b[0].p; B.desc = (const uint32_t *)b[1].p; B.cell_start = (const int *)b[2].p; B.cell_items = (const int *)b[3].p;
-    B.m_xw = (const float *)b[15].p; B.m_min_dist = (const float *)b[16].p; B.m_max_dist = (const float *)b[17].p; B.m_desc = (const uint32_t *)b[18].p; B.m_skip = (const uint8_t *)b[19].p;
-    B.best_idx = (int *)b[20].p; B.best_dist = (int *)b[21].p;
+    const SgxKfGrid g1 = build_kf_grid(n1, keys1_un, A.cam), g2 = build_kf_grid(n2, keys2_un, A.cam);
+    SgxStaging st(SGX_STAGE_SHARED);
+    // KF1: its keypoints and grid are what B searches, its map points are what A projects
+    B.keys = st.keys(keys1_un, n1); B.desc = st.desc(desc1, n1); B.cell_start = st.in(g1.start.data(), g1.start.size()); B.cell_items = st.in(g1.items.data(), g1.items.size());
+    A.m_xw = st.in(m_xw1, (size_t)n1 * 3); A.m_min_dist = st.in(m_min_dist1, n1); A.m_max_dist = st.in(m_max_dist1, n1); A.m_desc = st.desc(m_desc1, n1); A.m_skip = st.in(skip1.data(), n1);
+    A.best_idx = st.out<int>(n1); A.best_dist = st.out<int>(n1);
+    // KF2: the other way round
+    A.keys = st.keys(keys2_un, n2); A.desc = st.desc(desc2, n2); A.cell_start = st.in(g2.start.data(), g2.start.size()); A.cell_items = st.in(g2.items.data(), g2.items.size());
+    B.m_xw = st.in(m_xw2, (size_t)n2 * 3); B.m_min_dist = st.in(m_min_dist2, n2); B.m_max_dist = st.in(m_max_dist2, n2); B.m_desc = st.desc(m_desc2, n2); B.m_skip = st.in(skip2.data(), n2);
+    B.best_idx = st.out<int>(n2); B.best_dist = st.out<int>(n2);
+    if (st.rc != SGX_OK) return st.rc;
+    SGX_LAUNCH(k_sim3_search, dim3((n1 + 255) / 256), dim3(256), (sgx_stream_t)0, A);
+    SGX_CHECK_HIP(hipGetLastError());
     SGX_LAUNCH(k_sim3_search, dim3((n2 + 255) / 256), dim3(256), (sgx_stream_t)0, B);
     SGX_CHECK_HIP(hipGetLastError());
     std::vector<int> m1((size_t)n1), m2((size_t)n2);
-    SGX_CHECK_HIP(hipMemcpy(m1.data(), A.best_idx, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(m2.data(), B.best_idx, (size_t)n2 * 4, hipMemcpyDeviceToHost));
+    st.back(m1.data(), A.best_idx, n1); st.back(m2.data(), B.best_idx, n2);
+    if (st.rc != SGX_OK) return st.rc;
     int n = 0;
     for (int i1 = 0; i1 < n1; i1++) {                                   // check agreement (:1305-1320)
         const int idx2 = m1[(size_t)i1];
@@ -445,26 +404,19 @@ extern "C" int sgx_match_search_for_initialization(
     for (int i = 0; i < n1; i++) matches12[i] = -1;
     if (n1 == 0 || n2 == 0) return SGX_OK;
     if (!keys1_un || !desc1 || !keys2_un || !desc2 || n2 >= (1 << 22)) return SGX_ERR_INVALID;
-    std::vector<int> start, items;
-    build_kf_grid(n2, keys2_un, cam, start, items);              // F2.mGrid (Frame::AssignFeaturesToGrid, same round() cell rule)
     SgxInitSearchArgs A; memset(&A, 0, sizeof A);
     A.n1 = n1; A.n2 = n2; A.window = window_size; A.check_ori = check_orientation; A.nnratio = nnratio;
-    A.cam.fx = cam->fx; A.cam.fy = cam->fy; A.cam.cx = cam->cx; A.cam.cy = cam->cy; A.cam.bf = cam->bf; A.cam.minX = cam->min_x; A.cam.maxX = cam->max_x; A.cam.minY = cam->min_y; A.cam.maxY = cam->max_y;
-    SgxStaged b[12]; int rc;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, keys1_un, (size_t)n1 * 28); PUT(1, desc1, (size_t)n1 * 32); PUT(2, keys2_un, (size_t)n2 * 28); PUT(3, desc2, (size_t)n2 * 32);
-    PUT(4, start.data(), start.size() * 4); PUT(5, items.data(), items.size() * 4); PUT(6, prev_matched, (size_t)n1 * 8);
-    PUT(7, nullptr, (size_t)n1 * 4); PUT(8, nullptr, (size_t)n2 * 4); PUT(9, nullptr, (size_t)n2 * 4); PUT(10, nullptr, 4);
-#undef PUT
-    A.keys1 = (const uint8_t *)b[0].p; A.desc1 = (const uint32_t *)b[1].p; A.keys2 = (const uint8_t *)b[2].p; A.desc2 = (const uint32_t *)b[3].p;
-    A.cell_start = (const int *)b[4].p; A.cell_items = (const int *)b[5].p; A.prev_matched = (float *)b[6].p;
-    A.matches12 = (int *)b[7].p; A.matches21 = (int *)b[8].p; A.dist21 = (int *)b[9].p; A.nmatches = (int *)b[10].p;
+    A.cam = to_cam(cam);
+    const SgxKfGrid g = build_kf_grid(n2, keys2_un, A.cam);              // F2.mGrid (Frame::AssignFeaturesToGrid, same round() cell rule)
+    SgxStaging st(SGX_STAGE_SHARED);
+    A.keys1 = st.keys(keys1_un, n1); A.desc1 = st.desc(desc1, n1); A.keys2 = st.keys(keys2_un, n2); A.desc2 = st.desc(desc2, n2);
+    A.cell_start = st.in(g.start.data(), g.start.size()); A.cell_items = st.in(g.items.data(), g.items.size()); A.prev_matched = st.inout(prev_matched, (size_t)n1 * 2);
+    A.matches12 = st.out<int>(n1); A.matches21 = st.out<int>(n2); A.dist21 = st.out<int>(n2); A.nmatches = st.out<int>(1);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_LAUNCH(k_search_initialization, dim3(1), dim3(256), (sgx_stream_t)0, A);
     SGX_CHECK_HIP(hipGetLastError());
-    SGX_CHECK_HIP(hipMemcpy(matches12, A.matches12, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(prev_matched, A.prev_matched, (size_t)n1 * 8, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(nmatches, A.nmatches, 4, hipMemcpyDeviceToHost));
-    return SGX_OK;
+    st.back(matches12, A.matches12, n1); st.back(prev_matched, A.prev_matched, (size_t)n1 * 2); st.back(nmatches, A.nmatches, 1);
+    return st.rc;
 }
 
 // ---- MapPoint post-steps (MapPoint.cc:242-307, :330-371), batched over points; host pointers, synchronous ------------------------------------------------------------
@@ -476,19 +428,15 @@ extern "C" int sgx_mappoint_update_normal_and_depth(int n, const float *xw, cons
     const int total = obs_start[n];
     if (total < 0 || (total > 0 && !obs_center)) return SGX_ERR_INVALID;
     for (int p = 0; p < n; p++) if (obs_start[p] > obs_start[p + 1] || ref_level[p] < 0 || ref_level[p] >= nlevels) return SGX_ERR_INVALID;
-    SgxScales sc; memset(&sc, 0, sizeof sc); for (int i = 0; i < nlevels; i++) sc.s[i] = scale_factors[i];
-    SgxStaged b[8]; int rc;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, xw, (size_t)n * 12); PUT(1, obs_start, ((size_t)n + 1) * 4); PUT(2, obs_center, (size_t)total * 12); PUT(3, ref_center, (size_t)n * 12); PUT(4, ref_level, (size_t)n * 4);
-    PUT(5, normal, (size_t)n * 12); PUT(6, min_dist, (size_t)n * 4); PUT(7, max_dist, (size_t)n * 4);          // points without observations keep the caller's values
-#undef PUT
-    SGX_LAUNCH(k_mappoint_normal_depth, dim3((n + 255) / 256), dim3(256), (sgx_stream_t)0, n, (const float *)b[0].p, (const int *)b[1].p, (const float *)b[2].p, (const float *)b[3].p,
-               (const int *)b[4].p, sc, nlevels, (float *)b[5].p, (float *)b[6].p, (float *)b[7].p);
+    SgxStaging st(SGX_STAGE_SHARED);
+    const float *d_xw = st.in(xw, (size_t)n * 3); const int *d_start = st.in(obs_start, (size_t)n + 1);
+    const float *d_oc = st.in(obs_center, (size_t)total * 3), *d_rc = st.in(ref_center, (size_t)n * 3); const int *d_rl = st.in(ref_level, n);
+    float *d_normal = st.inout(normal, (size_t)n * 3), *d_min = st.inout(min_dist, n), *d_max = st.inout(max_dist, n);          // points without observations keep the caller's values
+    if (st.rc != SGX_OK) return st.rc;
+    SGX_LAUNCH(k_mappoint_normal_depth, dim3((n + 255) / 256), dim3(256), (sgx_stream_t)0, n, d_xw, d_start, d_oc, d_rc, d_rl, to_scales(scale_factors, nlevels), nlevels, d_normal, d_min, d_max);
     SGX_CHECK_HIP(hipGetLastError());
-    SGX_CHECK_HIP(hipMemcpy(normal, b[5].p, (size_t)n * 12, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(min_dist, b[6].p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(max_dist, b[7].p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return SGX_OK;
+    st.back(normal, d_normal, (size_t)n * 3); st.back(min_dist, d_min, n); st.back(max_dist, d_max, n);
+    return st.rc;
 }
 
 extern "C" int sgx_mappoint_distinctive_descriptors(int n, const int32_t *obs_start, const uint8_t *obs_desc, int32_t *best, uint8_t *desc_out)
@@ -498,11 +446,13 @@ extern "C" int sgx_mappoint_distinctive_descriptors(int n, const int32_t *obs_st
     const int total = obs_start[n];
     if (total < 0 || (total > 0 && !obs_desc)) return SGX_ERR_INVALID;
     for (int p = 0; p < n; p++) if (obs_start[p] > obs_start[p + 1] || obs_start[p + 1] - obs_start[p] > 65535) return SGX_ERR_INVALID;
-    SgxStaged b[3]; int rc;
-    if ((rc = b[0].put(0, obs_start, ((size_t)n + 1) * 4)) != SGX_OK || (rc = b[1].put(1, obs_desc, (size_t)total * 32)) != SGX_OK || (rc = b[2].put(2, nullptr, (size_t)n * 4)) != SGX_OK) return rc;
-    SGX_LAUNCH(k_mappoint_distinctive, dim3(n), dim3(64), (sgx_stream_t)0, n, (const int *)b[0].p, (const uint32_t *)b[1].p, (int *)b[2].p);
+    SgxStaging st(SGX_STAGE_SHARED);
+    const int *d_start = st.in(obs_start, (size_t)n + 1); const uint32_t *d_desc = st.desc(obs_desc, total); int *d_best = st.out<int>(n);
+    if (st.rc != SGX_OK) return st.rc;
+    SGX_LAUNCH(k_mappoint_distinctive, dim3(n), dim3(64), (sgx_stream_t)0, n, d_start, d_desc, d_best);
     SGX_CHECK_HIP(hipGetLastError());
-    SGX_CHECK_HIP(hipMemcpy(best, b[2].p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    st.back(best, d_best, n);
+    if (st.rc != SGX_OK) return st.rc;
     if (desc_out) for (int p = 0; p < n; p++) if (best[p] >= 0) memcpy(desc_out + 32 * (size_t)p, obs_desc + 32 * (size_t)(obs_start[p] + best[p]), 32);      // mDescriptor = vDescriptors[BestIdx].clone()
     return SGX_OK;
 }
@@ -521,24 +471,19 @@ extern "C" int sgx_triangulate_new_map_points(
     for (int q = 0; q < npairs; q++) if (pairs[2 * q] < 0 || pairs[2 * q] >= n1 || pairs[2 * q + 1] < 0 || pairs[2 * q + 1] >= n2) return SGX_ERR_INVALID;
     SgxNewPointArgs A; memset(&A, 0, sizeof A);
     A.npairs = npairs; memcpy(A.Tcw1, Tcw1, 64); memcpy(A.Tcw2, Tcw2, 64);
-    for (int i = 0; i < 3; i++) {                                 // Ow = -Rcw.t() * tcw (KeyFrame::SetPose, KeyFrame.cc:64-66): transpose flag -> double accumulation, alpha = -1
-        double a = 0, b = 0; for (int k = 0; k < 3; k++) { a += (double)Tcw1[4 * k + i] * (double)Tcw1[4 * k + 3]; b += (double)Tcw2[4 * k + i] * (double)Tcw2[4 * k + 3]; }
-        A.Ow1[i] = (float)(a * -1.0); A.Ow2[i] = (float)(b * -1.0);
-    }
+    camera_centre(Tcw1, 4, Tcw1 + 3, 4, A.Ow1); camera_centre(Tcw2, 4, Tcw2 + 3, 4, A.Ow2);            // the two keyframes' camera centres
     A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy; A.mbf = cam->bf; A.ratio_factor = 1.5f * scale_factors[1];       // ratioFactor = 1.5f * mfScaleFactor (:233)
-    for (int i = 0; i < nlevels; i++) { A.scale.s[i] = scale_factors[i]; A.sigma2.s[i] = level_sigma2[i]; }
-    SgxStaged b[12]; int rc;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, pairs, (size_t)npairs * 8); PUT(1, keys1_un, (size_t)n1 * 28); PUT(2, keys1, (size_t)n1 * 28); PUT(3, uright1, (size_t)n1 * 4); PUT(4, depth1, (size_t)n1 * 4);
-    PUT(5, keys2_un, (size_t)n2 * 28); PUT(6, keys2, (size_t)n2 * 28); PUT(7, uright2, (size_t)n2 * 4); PUT(8, depth2, (size_t)n2 * 4);
-    PUT(9, nullptr, (size_t)npairs); PUT(10, nullptr, (size_t)npairs * 12);
-#undef PUT
-    A.pairs = (const int *)b[0].p; A.keys1_un = (const uint8_t *)b[1].p; A.keys1 = (const uint8_t *)b[2].p; A.ur1 = (const float *)b[3].p; A.dp1 = (const float *)b[4].p;
-    A.keys2_un = (const uint8_t *)b[5].p; A.keys2 = (const uint8_t *)b[6].p; A.ur2 = (const float *)b[7].p; A.dp2 = (const float *)b[8].p; A.ok = (uint8_t *)b[9].p; A.x3d = (float *)b[10].p;
+    A.scale = to_scales(scale_factors, nlevels); A.sigma2 = to_scales(level_sigma2, nlevels);
+    SgxStaging st(SGX_STAGE_SHARED);
+    A.pairs = st.in(pairs, (size_t)npairs * 2);
+    A.keys1_un = st.keys(keys1_un, n1); A.keys1 = st.keys(keys1, n1); A.ur1 = st.in(uright1, n1); A.dp1 = st.in(depth1, n1);
+    A.keys2_un = st.keys(keys2_un, n2); A.keys2 = st.keys(keys2, n2); A.ur2 = st.in(uright2, n2); A.dp2 = st.in(depth2, n2);
+    A.ok = st.out<uint8_t>(npairs); A.x3d = st.out<float>((size_t)npairs * 3);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_LAUNCH(k_triangulate_pairs, dim3((npairs + 255) / 256), dim3(256), (sgx_stream_t)0, A);
     SGX_CHECK_HIP(hipGetLastError());
-    SGX_CHECK_HIP(hipMemcpy(ok, A.ok, (size_t)npairs, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(x3d, A.x3d, (size_t)npairs * 12, hipMemcpyDeviceToHost));
+    st.back(ok, A.ok, npairs); st.back(x3d, A.x3d, (size_t)npairs * 3);
+    if (st.rc != SGX_OK) return st.rc;
     int n = 0; for (int q = 0; q < npairs; q++) n += ok[q];
     *nnew = n;
     return SGX_OK;

@@ -22,20 +22,16 @@ extern "C" int sgx_optimize_sim3(int n, const float *p1c, const float *p2c, cons
     SgxSim3Args A; memset(&A, 0, sizeof A);
     A.n = n; A.fix_scale = fix_scale ? 1 : 0; A.th2 = th2;
     for (int i = 0; i < 4; i++) { A.K1[i] = K1[i]; A.K2[i] = K2[i]; }
-    SgxStaged b[12]; int rc;
-#define PUT(k, src, bytes) if ((rc = b[k].put(k, src, bytes)) != SGX_OK) return rc
-    PUT(0, p1c, (size_t)n * 12); PUT(1, p2c, (size_t)n * 12); PUT(2, obs1, (size_t)n * 8); PUT(3, obs2, (size_t)n * 8); PUT(4, info1, (size_t)n * 4); PUT(5, info2, (size_t)n * 4);
-    PUT(6, S12, 64); PUT(7, nullptr, (size_t)n * 32); PUT(8, nullptr, (size_t)n); PUT(9, nullptr, 8); PUT(10, nullptr, 4);
-#undef PUT
-    A.p1c = (const float *)b[0].p; A.p2c = (const float *)b[1].p; A.obs1 = (const float *)b[2].p; A.obs2 = (const float *)b[3].p; A.info1 = (const float *)b[4].p; A.info2 = (const float *)b[5].p;
-    A.S12 = (double *)b[6].p; A.err = (double *)b[7].p; A.inlier = (uint8_t *)b[8].p; A.iters = (int *)b[9].p; A.nin = (int *)b[10].p;
+    SgxStaging st(SGX_STAGE_SHARED);
+    A.p1c = st.in(p1c, (size_t)n * 3); A.p2c = st.in(p2c, (size_t)n * 3); A.obs1 = st.in(obs1, (size_t)n * 2); A.obs2 = st.in(obs2, (size_t)n * 2); A.info1 = st.in(info1, n); A.info2 = st.in(info2, n);
+    A.S12 = st.inout(S12, 8); A.err = st.out<double>((size_t)n * 4); A.inlier = st.out<uint8_t>(n); A.iters = st.out<int>(2); A.nin = st.out<int>(1);
+    if (st.rc != SGX_OK) return st.rc;
     SGX_LAUNCH(k_optimize_sim3, dim3(1), dim3(256), (sgx_stream_t)0, A);
     SGX_CHECK_HIP(hipGetLastError());
     int nin = 0, its[2] = { 0, 0 };
-    SGX_CHECK_HIP(hipMemcpy(&nin, A.nin, 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(its, A.iters, 8, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(inlier, A.inlier, (size_t)n, hipMemcpyDeviceToHost));
-    if (nin > 0 || its[1] > 0) SGX_CHECK_HIP(hipMemcpy(S12, A.S12, 64, hipMemcpyDeviceToHost));     // the "fewer than 10 survivors" exit leaves g2oS12 untouched
+    st.back(&nin, A.nin, 1); st.back(its, A.iters, 2); st.back(inlier, A.inlier, n);
+    if (st.rc == SGX_OK && (nin > 0 || its[1] > 0)) st.back(S12, A.S12, 8);     // the "fewer than 10 survivors" exit leaves g2oS12 untouched
+    if (st.rc != SGX_OK) return st.rc;
     *n_inliers = nin;
     if (iterations) { iterations[0] = its[0]; iterations[1] = its[1]; }
     return SGX_OK;

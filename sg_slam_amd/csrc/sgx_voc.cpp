@@ -125,16 +125,15 @@ extern "C" int sgx_voc_transform(sgx_voc *v, int n, const uint8_t *desc, int lev
     *nbow = 0;
     for (int i = 0; i < n; i++) { feat_node[i] = -1; if (feat_word) feat_word[i] = -1; }
     if (n == 0 || v->empty) return SGX_OK;                        // :1146-1149
-    SgxStaged b[4]; int rc;
-    if ((rc = b[0].put(0, desc, (size_t)n * 32)) != SGX_OK || (rc = b[1].put(1, nullptr, (size_t)n * 4)) != SGX_OK || (rc = b[2].put(2, nullptr, (size_t)n * 8)) != SGX_OK ||
-        (rc = b[3].put(3, nullptr, (size_t)n * 4)) != SGX_OK) return rc;
-    SGX_LAUNCH(k_voc_transform, dim3((n + 255) / 256, 1), dim3(256), (sgx_stream_t)0, v->dev, levelsup, (const uint8_t *)b[0].p, (size_t)0, (const int *)nullptr, n, n,
-               (int *)b[1].p, (double *)b[2].p, (int *)b[3].p);
+    SgxStaging st(SGX_STAGE_SHARED);
+    const uint8_t *d_desc = st.in(desc, (size_t)n * 32);
+    int *d_word = st.out<int>(n); double *d_w = st.out<double>(n); int *d_node = st.out<int>(n);
+    if (st.rc != SGX_OK) return st.rc;
+    SGX_LAUNCH(k_voc_transform, dim3((n + 255) / 256, 1), dim3(256), (sgx_stream_t)0, v->dev, levelsup, d_desc, (size_t)0, (const int *)nullptr, n, n, d_word, d_w, d_node);
     SGX_CHECK_HIP(hipGetLastError());
     std::vector<int32_t> word((size_t)n); std::vector<double> w((size_t)n);
-    SGX_CHECK_HIP(hipMemcpy(word.data(), b[1].p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(w.data(), b[2].p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    SGX_CHECK_HIP(hipMemcpy(feat_node, b[3].p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    st.back(word.data(), d_word, n); st.back(w.data(), d_w, n); st.back(feat_node, d_node, n);
+    if (st.rc != SGX_OK) return st.rc;
     // BowVector: std::map keyed by word id, weights accumulated in feature order (addWeight, BowVector.cpp:33-45) or first-wins (addIfNotExist :49-57); FeatureVector = feat_node
     std::map<int32_t, double> bow;
     const bool tf = v->weighting == 0 || v->weighting == 1;       // TF_IDF, TF (:1159) against IDF, BINARY (:1186)

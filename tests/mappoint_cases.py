@@ -73,3 +73,26 @@ def check_triangulation_step(lib, orc, n_cases=4, exact=True):
             if variant == 1: svd_like += en
     assert tot > 300 and svd_like > 20 and len(branches) >= 3, (tot, svd_like, branches)
     assert mappoint.TriangulateNewMapPoints(np.zeros((0, 2), 'i4'), A, B, CAM, sf, sg, lib=lib)[0] == 0
+
+
+def check_argument_contract(lib):
+    """NULL pointers, nlevels outside the tables, an octave outside them and an empty call for the three MapPoint / new-map-point entries (see match2_cases.check_contract)"""
+    import match2_cases as mc
+    from scenes import CAM
+    from sg_slam_amd.matcher import camera_struct
+    d = lib.dll; a, b = mc.contract_inputs(3), mc.contract_inputs(4); n = 3; out = mc.out
+    st = np.arange(n + 1, dtype='i4'); oc = a['xw'] * 0
+    # neither MapPoint entry initialises an output before its second check: whatever -1 they return, every output is as it came
+    mc.check_contract(d.sgx_mappoint_update_normal_and_depth,
+                      lambda: dict(n=n, xw=a['xw'], st=st, oc=oc, rc=oc, rl=a['keys']['octave'].astype('i4'), sf=a['scale'], nlevels=8, normal=out((n, 3), 'f4'), mind=out(n, 'f4'), maxd=out(n, 'f4')),
+                      dict(normal=(None, None), mind=(None, None), maxd=(None, None)), first=('xw', 'st', 'rc', 'rl', 'sf', 'normal', 'mind', 'maxd'), levels='nlevels', second=('oc',), sides=('n',))
+    mc.check_contract(d.sgx_mappoint_distinctive_descriptors, lambda: dict(n=n, st=st, desc=a['desc'], best=out(n), dout=out((n, 32), np.uint8)),
+                      dict(best=(None, None), dout=(None, None)), first=('st', 'best'), second=('desc',), sides=('n',))
+    assert d.sgx_mappoint_distinctive_descriptors(n, mc._vp(st), mc._vp(a['desc']), mc._vp(out(n)), None) == 0          # the descriptor copy is optional
+    pairs = np.stack([np.arange(n), np.arange(n)], 1).astype('i4')
+    side = lambda p, s: {'n' + p: n, 'ku' + p: s['keys'], 'k' + p: s['keys'], 'ur' + p: s['uright'], 'dp' + p: s['depth'], 'T' + p: s['T']}
+    mc.check_contract(d.sgx_triangulate_new_map_points,
+                      lambda: dict(npairs=n, pairs=pairs, **side('1', a), **side('2', b), cam=camera_struct(CAM), sf=a['scale'], sg=a['sigma2'], nlevels=8, ok=out(n, np.uint8), x3d=out((n, 3), 'f4'),
+                                   nnew=out(1)),
+                      dict(ok=(None, None), x3d=(None, None), nnew=(0, None)), first=('cam', 'sf', 'sg', 'T1', 'T2', 'nnew', 'pairs', 'ok', 'x3d'), levels='nlevels',
+                      second=[x + p for p in '12' for x in ('ku', 'k', 'ur', 'dp')], sides=('npairs',), octave=('ku1', 'ku2'))

@@ -2,6 +2,7 @@
 import numpy as np
 from scenes import CAM
 from sg_slam_amd import synth
+from sg_slam_amd.capi import _vp
 from sg_slam_amd.matcher import ORBmatcher
 
 
@@ -388,3 +389,169 @@ def check_search_for_initialization(lib, orc, n_cases=4):
     assert n == 0 and (mm == -1).all() and (pp == pm0).all()
     far = pm0 + 5000.0                                                           # every window outside the image
     assert m.SearchForInitialization(F1, F2, far, 100, CAM)[0] == 0 == orc.search_for_initialization(F1, F2, far, 100, CAM)[0]
+
+
+# ---- argument contract of the host-pointer entries (host code, the same in the emulator and the device build: exercised on the emulator only) ----------------------------
+
+SENT = 77          # every output starts as this value: an output still equal to it was left alone
+
+
+def contract_inputs(seed, n=3, nlevels=8):
+    """one side of a tiny valid call: n keypoints with valid octaves, descriptors, per-keypoint arrays and map points, plus the per-level tables"""
+    from sg_slam_amd.capi import KP_DTYPE
+    rng = np.random.RandomState(seed)
+    k = np.zeros(n, KP_DTYPE); k['x'] = rng.uniform(50, 590, n); k['y'] = rng.uniform(50, 430, n); k['size'] = 31; k['angle'] = rng.uniform(0, 360, n); k['octave'] = rng.randint(0, nlevels, n)
+    T = np.eye(4, dtype='f4'); T[:3, 3] = rng.normal(0, 0.05, 3)
+    return dict(keys=k, desc=rng.randint(0, 256, (n, 32)).astype(np.uint8), uright=(k['x'] - 8).astype('f4'), depth=np.full(n, 5.0, 'f4'), flag=np.ones(n, np.uint8), zero=np.zeros(n, np.uint8),
+                node=np.array([0, 0, 1], 'i4')[:n], T=T.reshape(16), xw=np.c_[rng.uniform(-1, 1, (n, 2)), rng.uniform(3, 6, n)].astype('f4'), normal=np.tile(np.array([0, 0, -1], 'f4'), (n, 1)),
+                mind=np.full(n, 0.5, 'f4'), maxd=np.full(n, 50.0, 'f4'), scale=(1.2 ** np.arange(nlevels)).astype('f4'), sigma2=(1.44 ** np.arange(nlevels)).astype('f4'),
+                inv_sigma2=(1.44 ** -np.arange(nlevels)).astype('f4'))
+
+
+def out(shape, dtype='i4'):
+    return np.full(shape, SENT, dtype)
+
+
+def check_contract(fn, make, outs, first=(), second=(), levels=None, sides=(), octave=()):
+    """fn(*make().values()) with ctypes.  make(): {argument name: value} in call order, outputs filled with SENT.
+    outs: {output name: (value it is initialised to, or None if the entry never initialises it; name of the count argument that sizes it, or None for one element)}.
+    first: pointers of the entry's first check (NULL -> SGX_ERR_INVALID, every output left alone); levels: name of the nlevels argument (0 and 13 -> the same);
+    second: pointers checked after the outputs are initialised; sides: count arguments that may be 0 (-> SGX_OK, outputs initialised, nothing else written);
+    octave: keypoint arguments checked by octaves_ok."""
+    import ctypes as C
+    from sg_slam_amd.capi import Camera, _vp
+    def call(null=None, **over):
+        a = make(); a.update(over)
+        return fn(*[None if k == null else C.byref(v) if isinstance(v, Camera) else _vp(v) if isinstance(v, np.ndarray) else v for k, v in a.items()]), a
+    def state(a, initialised, what, null=None):
+        for k, (val, cnt) in outs.items():
+            if k == null: continue
+            rows = a[k].reshape(len(a[k]), -1); n = (1 if cnt is None else a[cnt]) if initialised and val is not None else 0
+            assert (rows[:n] == val).all() and (rows[n:] == SENT).all(), (fn.__name__, what, k, a[k])
+    assert call()[0] == 0, fn.__name__
+    for p in first:
+        rc, a = call(null=p); assert rc == -1, (fn.__name__, p, rc); state(a, False, p, p)
+    for v in (0, 13) if levels else ():
+        rc, a = call(**{levels: v}); assert rc == -1, (fn.__name__, levels, v, rc); state(a, False, (levels, v))
+    for p in second:
+        rc, a = call(null=p); assert rc == -1, (fn.__name__, p, rc); state(a, True, p, p)
+    for s in sides:
+        rc, a = call(**{s: 0}); assert rc == 0, (fn.__name__, s, rc); state(a, True, (s, 0))
+    for kname in octave:
+        k = make()[kname].copy(); k['octave'][1] = make()[levels]
+        rc, a = call(**{kname: k}); assert rc == -1, (fn.__name__, kname, 'octave', rc); state(a, True, (kname, 'octave'))
+
+
+def check_argument_contract(lib):
+    """NULL pointers, nlevels outside 1..12, an octave outside the tables and an empty side for the ten matcher entries: the return code, and which outputs are initialised by then"""
+    from sg_slam_amd.matcher import camera_struct
+    d = lib.dll; a, b = contract_inputs(1), contract_inputs(2); cam = camera_struct(CAM); n = 3; lsf = float(np.log(np.float32(1.2)))
+    pts = lambda p, s: {p + 'xw': s['xw'], p + 'normal': s['normal'], p + 'mind': s['mind'], p + 'maxd': s['maxd'], p + 'mdesc': s['desc'], p + 'skip': s['zero']}
+    ptn = ['xw', 'normal', 'mind', 'maxd', 'mdesc', 'skip']
+
+    check_contract(d.sgx_hamming_matrix, lambda: dict(da=a['desc'], na=n, db=b['desc'], nb=n, out=out((n, n), np.uint16)), dict(out=(None, None)),
+                   first=('da', 'db', 'out'), sides=('na', 'nb'))
+
+    check_contract(d.sgx_match_search_for_triangulation,
+                   lambda: dict(n1=n, k1=a['keys'], d1=a['desc'], u1=a['uright'], h1=a['zero'], f1=a['node'], cc=np.zeros(3, 'f4'), n2=n, k2=b['keys'], d2=b['desc'], u2=b['uright'], h2=b['zero'],
+                                f2=b['node'], T2=b['T'], F=np.eye(3, dtype='f4').reshape(9), cam=cam, sf=a['scale'], sg=a['sigma2'], nlevels=8, stereo=0, ori=1, pairs=out((n, 2)), npairs=out(1)),
+                   dict(pairs=(None, None), npairs=(0, None)), first=('npairs', 'F', 'cam', 'sf', 'sg', 'cc', 'T2'), levels='nlevels',
+                   second=('k1', 'd1', 'u1', 'h1', 'f1', 'k2', 'd2', 'u2', 'h2', 'f2', 'pairs'), sides=('n1', 'n2'), octave=('k1', 'k2'))
+
+    check_contract(d.sgx_match_search_by_bow,
+                   lambda: dict(nk=n, kk=a['keys'], dk=a['desc'], gk=a['flag'], fk=a['node'], nf=n, kf=b['keys'], df=b['desc'], ff=b['node'], ratio=0.7, ori=1, match=out(n), nm=out(1)),
+                   dict(match=(-1, 'nf'), nm=(0, None)), first=('nm', 'match'), second=('kk', 'dk', 'gk', 'fk', 'kf', 'df', 'ff'), sides=('nk', 'nf'))
+
+    check_contract(d.sgx_match_search_by_bow_kf,
+                   lambda: dict(n1=n, k1=a['keys'], d1=a['desc'], g1=a['flag'], f1=a['node'], n2=n, k2=b['keys'], d2=b['desc'], g2=b['flag'], f2=b['node'], ratio=0.75, ori=1, match=out(n), nm=out(1)),
+                   dict(match=(-1, 'n1'), nm=(0, None)), first=('nm', 'match'), second=('k1', 'd1', 'g1', 'f1', 'k2', 'd2', 'g2', 'f2'), sides=('n1', 'n2'))
+
+    check_contract(d.sgx_match_fuse_search,
+                   lambda: dict(nk=n, keys=a['keys'], desc=a['desc'], ur=a['uright'], T=a['T'], nm=n, **pts('', b), cam=cam, sf=a['scale'], is2=a['inv_sigma2'], nlevels=8, lsf=lsf, th=3.0,
+                                bi=out(n), bd=out(n), nf=out(1)),
+                   dict(bi=(-1, 'nm'), bd=(256, 'nm'), nf=(0, None)), first=('cam', 'T', 'sf', 'is2', 'nf', 'bi', 'bd'), levels='nlevels',
+                   second=['keys', 'desc', 'ur'] + ptn, sides=('nk', 'nm'), octave=('keys',))
+
+    check_contract(d.sgx_match_project_keyframe,
+                   lambda: dict(nc=n, ck=a['keys'], cd=a['desc'], ch=a['zero'], T=a['T'], nk=n, kk=b['keys'], ok=b['flag'], xw=b['xw'], mind=b['mind'], maxd=b['maxd'], md=b['desc'], cam=cam,
+                                sf=a['scale'], nlevels=8, lsf=lsf, th=10.0, od=100, ori=1, match=out(n), nm=out(1)),
+                   dict(match=(-1, 'nc'), nm=(0, None)), first=('cam', 'T', 'sf', 'nm', 'match'), levels='nlevels', second=('ck', 'cd', 'ch', 'kk', 'ok', 'xw', 'mind', 'maxd', 'md'),
+                   sides=('nc', 'nk'))
+
+    check_contract(d.sgx_match_fuse_search_sim3,
+                   lambda: dict(nk=n, keys=a['keys'], desc=a['desc'], S=a['T'], nm=n, **pts('', b), cam=cam, sf=a['scale'], nlevels=8, lsf=lsf, th=4.0, bi=out(n), bd=out(n), nf=out(1)),
+                   dict(bi=(-1, 'nm'), bd=(256, 'nm'), nf=(0, None)), first=('cam', 'S', 'sf', 'nf', 'bi', 'bd'), levels='nlevels', second=['keys', 'desc'] + ptn, sides=('nk', 'nm'))
+
+    check_contract(d.sgx_match_project_sim3,
+                   lambda: dict(nk=n, keys=a['keys'], desc=a['desc'], taken=a['zero'], S=a['T'], nm=n, **pts('', b), cam=cam, sf=a['scale'], nlevels=8, lsf=lsf, th=10, mo=out(n), nmatch=out(1)),
+                   dict(mo=(-1, 'nk'), nmatch=(0, None)), first=('cam', 'S', 'sf', 'nmatch', 'mo'), levels='nlevels', second=['keys', 'desc', 'taken'] + ptn, sides=('nk', 'nm'))
+
+    side = lambda p, s: {'n' + p: n, 'k' + p: s['keys'], 'd' + p: s['desc'], 'T' + p: s['T'], 'ok' + p: s['flag'], 'xw' + p: s['xw'], 'mind' + p: s['mind'], 'maxd' + p: s['maxd'], 'md' + p: s['desc']}
+    check_contract(d.sgx_match_search_by_sim3,
+                   lambda: dict(**side('1', a), **side('2', b), cam=cam, sf=a['scale'], nlevels=8, lsf=lsf, s12=1.0, R=np.eye(3, dtype='f4').reshape(9), t=np.zeros(3, 'f4'), th=7.5,
+                                m12=np.full(n, -1, 'i4'), nfound=out(1)),
+                   dict(nfound=(0, None)), first=('cam', 'sf', 'nfound', 'R', 't', 'T1', 'T2', 'm12'), levels='nlevels',
+                   second=[x + p for p in '12' for x in ('k', 'd', 'ok', 'xw', 'mind', 'maxd', 'md')], sides=('n1', 'n2'))
+
+    pm = np.full((n, 2), SENT, 'f4')                                       # vbPrevMatched is in / out: an empty side and a refused call leave it as it came
+    check_contract(d.sgx_match_search_for_initialization,
+                   lambda: dict(n1=n, k1=a['keys'], d1=a['desc'], n2=n, k2=b['keys'], d2=b['desc'], pm=pm.copy(), window=100, ratio=0.9, ori=1, cam=cam, m12=out(n), nm=out(1)),
+                   dict(m12=(-1, 'n1'), nm=(0, None), pm=(None, None)), first=('cam', 'nm', 'm12', 'pm'), second=('k1', 'd1', 'k2', 'd2'), sides=('n1', 'n2'))
+
+
+# ---- the staging slots persist from call to call: a smaller call and a call of another entry find the bytes of the call before in them ---------------------------------
+
+def _first(d, n, full):
+    """the keyframe dict d cut to its first n keypoints (every per-keypoint array, nested map points included)"""
+    return {k: _first(v, n, full) if isinstance(v, dict) else v[:n] if isinstance(v, np.ndarray) and k not in ('Tcw', 'cam_center') and len(v) == full else v for k, v in d.items()}
+
+
+def check_interleaved(lib, orc, n_small):
+    """for each of six entries, in one process: the full-size call on a make_keyframes pair, the same call on the pair cut to its first n_small keypoints, then a call of
+    another entry; every result equals the oracle's.  (The emulator's hipMalloc zeroes, the device's does not: only there a reused slot holds what the larger call left.)"""
+    from test_tracker_emu import make_map_points
+    P = orc.orb_params(); sf, sg, is2 = P['scale'], P['sigma2'], P['inv_sigma2']
+    _, kf1, kf2 = make_keyframes(orc, 7, 10, 13)
+    for kf in (kf1, kf2):
+        ur = kf['uright']; z = np.where(ur >= 0, CAM['bf'] / np.maximum(kf['keys']['x'] - ur, 1e-3), -1.0).astype('f4')
+        xw, has = orc.unproject_stereo(kf['keys'], z, kf['Tcw'], CAM)
+        kf['mp'] = make_map_points(kf['keys'], xw, has, kf['desc'], kf['Tcw'], np.asarray(sf, 'f4'))
+        kf['good_mp'] = kf['has_mp']
+    m = ORBmatcher(0.7, True, lib=lib)
+
+    def flat(x):
+        return dict(keys=x['keys'], desc=x['desc'], Tcw=x['Tcw'], mp_ok=(1 - x['mp']['skip']).astype(np.uint8), xw=x['mp']['xw'], min_dist=x['mp']['min_dist'], max_dist=x['mp']['max_dist'],
+                    mp_desc=x['mp']['desc'])
+    def tri(a, b, f):
+        F12 = fundamental_12(a, b)
+        return f.search_for_triangulation(a, b, F12, False, CAM, sf, sg, check_ori=True) if f is orc else f.SearchForTriangulation(a, b, F12, False, CAM, sf, sg)
+    def bow(a, b, f):
+        return f.search_by_bow(a, b, 0.7, True) if f is orc else f.SearchByBoW(a, b)
+    def fuse(a, b, f):
+        kf = dict(keys=a['keys'], desc=a['desc'], uright=a['uright'], Tcw=a['Tcw'])
+        return f.fuse_search(kf, b['mp'], CAM, sf, is2, 3.0) if f is orc else f.FuseSearch(kf, b['mp'], 3.0, CAM, sf, is2)
+    def project_kf(a, b, f):
+        F = dict(keys=b['keys'], desc=b['desc'], has_mp=np.zeros(len(b['keys']), np.uint8), Tcw=b['Tcw'])
+        kf = dict(keys=a['keys'], ok=(1 - a['mp']['skip']).astype(np.uint8), xw=a['mp']['xw'], min_dist=a['mp']['min_dist'], max_dist=a['mp']['max_dist'], desc=a['mp']['desc'])
+        return f.search_by_projection_kf(F, kf, CAM, sf, 10.0, 100, True) if f is orc else f.SearchByProjectionKF(F, kf, 10.0, 100, CAM, sf)
+    def by_sim3(a, b, f):
+        T1 = a['Tcw'].astype('f8'); T2 = b['Tcw'].astype('f8'); R12 = T1[:3, :3] @ T2[:3, :3].T; t12 = (T1[:3, 3] - R12 @ T2[:3, 3]).astype('f4')
+        m0 = np.full(len(a['keys']), -1, 'i4')
+        return f.search_by_sim3(flat(a), flat(b), m0, 1.0, R12, t12, 7.5, CAM, sf) if f is orc else f.SearchBySim3(flat(a), flat(b), m0, 1.0, R12, t12, 7.5, CAM, sf)
+    def init(a, b, f):
+        pm0 = np.stack([a['keys']['x'], a['keys']['y']], 1).astype('f4')
+        return f.search_for_initialization(a, b, pm0, 100, CAM, 0.7, True) if f is orc else f.SearchForInitialization(a, b, pm0, 100, CAM)
+
+    entries = (tri, bow, fuse, project_kf, by_sim3, init)
+    full = len(kf1['keys']); assert len(kf2['keys']) != full                 # _first tells per-keypoint arrays by their length
+    assert n_small % 64 and n_small < min(full, len(kf2['keys'])) // 2
+    pair = {0: (kf1, kf2), 1: (_first(kf1, n_small, full), _first(kf2, n_small, len(kf2['keys'])))}
+    ref = {(e, c): e(*pair[c], orc) for e in entries for c in pair}          # the oracle's answers, once
+    def same(e, c):
+        got = e(*pair[c], m); exp = ref[e, c]
+        assert got[0] == exp[0] and all((np.asarray(g) == np.asarray(x)).all() for g, x in zip(got[1:], exp[1:])), (e.__name__, 'cut' if c else 'full', got[0], exp[0])
+    for i, e in enumerate(entries):
+        same(e, 0); same(e, 1); same(entries[(i + 1) % len(entries)], 1)
+    counts = {e.__name__: (ref[e, 0][0], ref[e, 1][0]) for e in entries}
+    assert all(v[0] > 0 for v in counts.values()) and sum(v[1] > 0 for v in counts.values()) >= 4, counts       # at most two entries may come back empty on the cut pair
+    return counts

@@ -8,3 +8,7 @@ def test_mappoint_post_steps_emu(emu, oracle):
 
 def test_triangulation_step_emu(emu, oracle):
     mpc.check_triangulation_step(emu, oracle, n_cases=2, exact=True)
+
+
+def test_mappoint_argument_contract_emu(emu):
+    mpc.check_argument_contract(emu)

@@ -40,3 +40,11 @@ def test_search_by_sim3_emu(emu, oracle):
 
 def test_search_for_initialization_emu(emu, oracle):
     mc.check_search_for_initialization(emu, oracle, n_cases=2)
+
+
+def test_match2_argument_contract_emu(emu):
+    mc.check_argument_contract(emu)
+
+
+def test_match2_interleaved_emu(emu, oracle):
+    mc.check_interleaved(emu, oracle, n_small=300)          # the same case as test_match2_gpu.py::test_match2_interleaved_gpu

@@ -43,3 +43,7 @@ def test_search_by_sim3_gpu(gpulib, oracle):
 
 def test_search_for_initialization_gpu(gpulib, oracle):
     mc.check_search_for_initialization(gpulib, oracle, n_cases=4)
+
+
+def test_match2_interleaved_gpu(gpulib, oracle):
+    mc.check_interleaved(gpulib, oracle, n_small=300)       # 300: a multiple of neither 64 nor 256, and on the emulator the oracle finds matches for all six entries on the cut pair
