@@ -25,7 +25,7 @@ struct sgx_orb {
     float scale[SGX_MAX_LEVELS], inv_scale[SGX_MAX_LEVELS], sigma2[SGX_MAX_LEVELS], inv_sigma2[SGX_MAX_LEVELS];
     int umax_h[16];
     // device tables
-    SgxCell *d_cells = nullptr;
+    SgxRun *d_runs = nullptr;
     SgxXTab *d_xt[SGX_MAX_LEVELS] = {};
     SgxYTab *d_yt[SGX_MAX_LEVELS] = {};
     // fused pyramid (k_pyramid): concatenated tables, per (tile, level) rects
@@ -127,12 +127,31 @@ extern "C" const char *sgx_status_string(int s)
 extern "C" void sgx_orb_destroy(sgx_orb *h)
 {
     if (!h) return;
-    (void)hipFree(h->d_cells); (void)hipFree(h->d_umax); (void)hipFree(h->d_pattern); (void)hipFree(h->d_pyr); (void)hipFree(h->d_cand);
+    (void)hipFree(h->d_runs); (void)hipFree(h->d_umax); (void)hipFree(h->d_pattern); (void)hipFree(h->d_pyr); (void)hipFree(h->d_cand);
     (void)hipFree(h->d_cand_count); (void)hipFree(h->d_node_scratch); (void)hipFree(h->d_sel); (void)hipFree(h->d_sel_count); (void)hipFree(h->d_status);
     (void)hipFree(h->d_gray1); (void)hipFree(h->d_kps1); (void)hipFree(h->d_desc1); (void)hipFree(h->d_count1);
     for (int l = 0; l < SGX_MAX_LEVELS; l++) { (void)hipFree(h->d_xt[l]); (void)hipFree(h->d_yt[l]); }
     (void)hipFree(h->d_xg_all); (void)hipFree(h->d_yt_all); (void)hipFree(h->d_pyr_rects); (void)hipFree(h->d_blur); (void)hipFree(h->d_blur_tiles);
     delete h;
+}
+
+// one FAST cell (ORBextractor.cc:790-808): tile rect in level coords incl. the 3-px aprons; col = j, ox = j*wCell, oy = i*hCell
+struct SgxCell { short level, x0, y0, cw, ch, ox, oy, col; };
+
+// k_fast_cells LDS carve of a run of ncell cells, tile rw x ch: bytes of the staged tile (the score map is as large), of the quick-test list (the corner list is as large:
+// every interior pixel can pass both tests) and of the output list (strict-'>' NMS inside a cell: no two survivors of a cell are 8-adjacent); returns the total
+#ifndef SGX_FAST_LDS_BUDGET
+#define SGX_FAST_LDS_BUDGET 24576
+#endif
+static int fast_carve(int rw, int ch, int ncell, int wcell, int *tile_b, int *q_b, int *o_b)
+{
+    const int tb = ch * ((15 + rw + 5 + 15) & ~15), qb = ((rw - 6) * (ch - 6) * 2 + 15) & ~15;
+    const int last = rw - 6 - (ncell - 1) * wcell;                     // interior width of the run's last cell
+    const int ob = ((((ncell - 1) * ((wcell + 1) / 2) + (last + 1) / 2) * ((ch - 5) / 2)) * 4 + 15) & ~15;
+    if (tile_b) *tile_b = tb;
+    if (q_b) *q_b = qb;
+    if (o_b) *o_b = ob;
+    return 2 * tb + 2 * qb + ob;
 }
 
 extern "C" int sgx_orb_create(const sgx_orb_config *cfg, sgx_orb **out)
@@ -181,7 +200,7 @@ extern "C" int sgx_orb_create(const sgx_orb_config *cfg, sgx_orb **out)
                 SgxCell c; c.level = (short)l; c.x0 = (short)iniX; c.y0 = (short)iniY;
                 c.cw = (short)((int)maxX - (int)iniX); c.ch = (short)((int)maxY - (int)iniY);
                 c.ox = (short)(j * L.wcell); c.oy = (short)(i * L.hcell);
-                { const int ng = ((c.x0 & 3) + c.cw + 3) >> 2; c.pad = (short)(unsigned short)((65536 + ng - 1) / ng); }      // ceil(2^16 / ng): k_fast_cells divides its task index by ng (ng >= 2, tasks < 4096: exact)
+                c.col = (short)j;
                 if (c.cw >= 7 && c.ch >= 7) {                        // cv::FAST yields nothing on tiles < 7 px
                     cells.push_back(c);
                     L.cand_cap += ((c.cw - 6 + 1) / 2) * ((c.ch - 6 + 1) / 2);   // strict-'>' NMS: no two survivors are 8-adjacent
@@ -200,11 +219,45 @@ extern "C" int sgx_orb_create(const sgx_orb_config *cfg, sgx_orb **out)
         cand_off += L.cand_cap;
     }
     g.cand_pitch = cand_off;
-    {   // k_fast_cells LDS carve for the largest tile of this geometry
-        int mw = 7, mh = 7;
-        for (const SgxCell &cc : cells) { if (cc.cw > mw) mw = cc.cw; if (cc.ch > mh) mh = cc.ch; }
-        const int tile_b = mh * SGX_TILE_STRIDE, q_b = ((mw - 6) * (mh - 6) * 2 + 15) & ~15, o_b = (((mw - 5) / 2) * ((mh - 5) / 2) * 4 + 15) & ~15;
-        g.fast_off_score = tile_b; g.fast_off_qlist = 2 * tile_b; g.fast_off_out = 2 * tile_b + q_b; g.fast_lds_bytes = 2 * tile_b + q_b + o_b;
+    // k_fast_cells works on runs of adjacent cells of one cell row.  Cells per run: as many as keep the LDS carve of a run within SGX_FAST_LDS_BUDGET (6 workgroups of
+    // 4 waves per CU: 24 resident waves, the single-cell kernel had 16; at 640x480 that is 3 cells on levels 1-3 and 2 on the others), at most SGX_FAST_MAXG; a row's cells are spread evenly
+    // over its runs.  Measured per 512 frames by budget (profiles/fast_cell_runs_ab.txt): 0.903 ms at 24 KB, 0.954 at 17 KB, 0.970 at 32 KB, 0.924 at 40 KB (256 threads); 0.961 / 1.082 at 24 KB and 192 / 128 threads.
+    std::vector<SgxRun> runs;
+    {
+        int tile_b = 0, q_b = 0, o_b = 0;
+        for (size_t i = 0; i < cells.size();) {
+            const SgxLevel &L = g.lv[cells[i].level];
+            size_t e = i + 1;                                           // [i, e): the cells of one cell row (adjacent columns)
+            while (e < cells.size() && cells[e].level == cells[i].level && cells[e].y0 == cells[i].y0 && cells[e].col == cells[e - 1].col + 1) e++;
+            const int n = (int)(e - i), ch = cells[i].ch;
+            int G = 1;
+            for (int t = 2; t <= SGX_FAST_MAXG && t <= n; t++) {
+                const int rw = t * L.wcell + 6;
+                if (rw > SGX_FAST_MAXRW) break;
+                if (fast_carve(rw, ch, t, L.wcell, nullptr, nullptr, nullptr) > SGX_FAST_LDS_BUDGET) break;
+                G = t;
+            }
+            const int nr = (n + G - 1) / G;
+            for (int r = 0, k = 0; r < nr; r++) {
+                const int m = n / nr + (r < n % nr ? 1 : 0);
+                const SgxCell &a = cells[i + k], &z = cells[i + k + m - 1];
+                SgxRun u; memset(&u, 0, sizeof u);
+                u.level = a.level; u.x0 = a.x0; u.y0 = a.y0; u.rw = (short)(z.x0 + z.cw - a.x0); u.ch = a.ch; u.ox = a.ox; u.oy = a.oy; u.ncell = (short)m; u.wcell = (short)L.wcell;
+                const int lead = u.x0 & 15;
+                u.ts = (short)((lead + u.rw + 5 + 15) & ~15);           // room for the dword two groups right of the last quick-test task
+                while ((1 << u.sh) < (u.ts >> 4)) u.sh++;
+                u.wc_m16 = (unsigned short)((65536 + L.wcell - 1) / L.wcell);
+                int tb, qb, ob;
+                fast_carve(u.rw, u.ch, m, L.wcell, &tb, &qb, &ob);
+                tile_b = std::max(tile_b, tb); q_b = std::max(q_b, qb); o_b = std::max(o_b, ob);
+                if (u.rw > SGX_FAST_MAXRW || (u.ts >> 2) > SGX_FAST_MAXGROUPS) { sgx_orb_destroy(h); return SGX_ERR_UNSUPPORTED; }
+                runs.push_back(u);
+                k += m;
+            }
+            i = e;
+        }
+        g.fast_off_score = tile_b; g.fast_off_qlist = 2 * tile_b; g.fast_off_clist = 2 * tile_b + q_b; g.fast_off_out = 2 * tile_b + 2 * q_b; g.fast_lds_bytes = 2 * tile_b + 2 * q_b + o_b;
+        g.nruns = (int)runs.size();
     }
     g.pyr_pitch = (off + 255) & ~255;
     std::vector<SgxBlurTile> btiles;
@@ -226,7 +279,7 @@ extern "C" int sgx_orb_create(const sgx_orb_config *cfg, sgx_orb **out)
 
     const int B = cfg->max_batch, nl = g.nlevels;
 #define SGX_ALLOC(p, bytes) do { if (hipMalloc((void **)&(p), (bytes)) != hipSuccess) { sgx_orb_destroy(h); return SGX_ERR_NOMEM; } } while (0)
-    SGX_ALLOC(h->d_cells, cells.size() * sizeof(SgxCell));
+    SGX_ALLOC(h->d_runs, runs.size() * sizeof(SgxRun));
     SGX_ALLOC(h->d_umax, 16 * sizeof(int));
     SGX_ALLOC(h->d_pattern, 1024);
     SGX_ALLOC(h->d_pyr, (size_t)B * g.pyr_pitch + 256);
@@ -243,7 +296,7 @@ extern "C" int sgx_orb_create(const sgx_orb_config *cfg, sgx_orb **out)
     SGX_ALLOC(h->d_kps1, (size_t)kp_cap * 28);
     SGX_ALLOC(h->d_desc1, (size_t)kp_cap * 32);
     SGX_ALLOC(h->d_count1, 4);
-    SGX_CHECK_HIP(hipMemcpyAsync(h->d_cells, cells.data(), cells.size() * sizeof(SgxCell), hipMemcpyHostToDevice, 0));
+    SGX_CHECK_HIP(hipMemcpyAsync(h->d_runs, runs.data(), runs.size() * sizeof(SgxRun), hipMemcpyHostToDevice, 0));
     SGX_CHECK_HIP(hipMemcpyAsync(h->d_umax, h->umax_h, 16 * sizeof(int), hipMemcpyHostToDevice, 0));
     SGX_CHECK_HIP(hipMemcpyAsync(h->d_pattern, sgx_orb_pattern_xy, 1024, hipMemcpyHostToDevice, 0));
     SGX_CHECK_HIP(hipMemsetAsync(h->d_status, 0, 4, 0));
@@ -381,9 +434,9 @@ static int launch_detect(sgx_orb *h, const uint8_t *d_gray, int pitch, int batch
         }
     sgx_prof_end(SGX_K_RESIZE, stream);
     sgx_prof_begin(SGX_K_FAST, stream);
-    static const int fast_threads = sgx_getenv("SGX_TUNE_FAST_THREADS") ? atoi(sgx_getenv("SGX_TUNE_FAST_THREADS")) : 128;      // workgroup size; env = tuning tap (64..SGX_FAST_THREADS)
+    static const int fast_threads = sgx_getenv("SGX_TUNE_FAST_THREADS") ? std::min(SGX_FAST_THREADS, std::max(64, atoi(sgx_getenv("SGX_TUNE_FAST_THREADS")) & ~63)) : SGX_FAST_THREADS;      // workgroup size; env = tuning tap (64..SGX_FAST_THREADS, whole waves)
     static const int e_extra = sgx_getenv("SGX_TUNE_E_EXTRA_LDS") ? atoi(sgx_getenv("SGX_TUNE_E_EXTRA_LDS")) : 0;   // tuning tap: pad the extraction kernels' LDS to cap their occupancy
-    SGX_LAUNCH_DYN(k_fast_cells, dim3(g.ncells * batch), dim3(fast_threads), g.fast_lds_bytes + e_extra, stream, g, h->d_cells, d_gray, pitch, h->d_pyr, batch,
+    SGX_LAUNCH_DYN(k_fast_cells, dim3(g.nruns * batch), dim3(fast_threads), g.fast_lds_bytes + e_extra, stream, g, h->d_runs, d_gray, pitch, h->d_pyr, batch,
                h->d_cand, h->d_cand_count, h->d_status);
     sgx_prof_end(SGX_K_FAST, stream);
     sgx_prof_begin(SGX_K_OCTREE, stream);

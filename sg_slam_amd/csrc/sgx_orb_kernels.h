@@ -16,7 +16,9 @@
 #define SGX_EDGE 19            /* EDGE_THRESHOLD, ORBextractor.cc:75 */
 #define SGX_BORDER 16          /* EDGE_THRESHOLD-3 = minBorderX/Y, ORBextractor.cc:774 */
 #define SGX_TILE_MAX 68        /* max FAST cell tile edge incl. 3-px aprons */
-#define SGX_TILE_STRIDE 72
+#define SGX_FAST_MAXG 8        /* max cells per run of k_fast_cells */
+#define SGX_FAST_MAXRW 496     /* max tile width of a run: byte columns of a staged row stay below 512 (9 bits of a list entry) */
+#define SGX_FAST_MAXGROUPS 136 /* max dword groups per staged row */
 #define SGX_CAND_LDS 8192      /* k_octree keeps up to this many keys of a (frame, level) in LDS; more -> global-memory variant */
 #define SGX_OCT_MAXN 1280      /* max octree list length (per-level quota + 3) */
 #define SGX_OCT_THREADS 512      /* measured: 0.0435 ms per 64 frames at 512 threads vs 0.0475 / 0.056 / 0.071 at 256 / 128 / 64 */
@@ -36,16 +38,18 @@ struct SgxLevel {
 struct SgxOrbGeom {
     int nlevels, W, H;
     int pyr_pitch;             // bytes per frame of pyramid storage (levels 1..)
-    int ncells;                // total valid cells over all levels
+    int ncells, nruns;         // total valid cells over all levels; runs of adjacent cells (one k_fast_cells workgroup each)
     int kp_cap;                // keypoint capacity per frame
-    int fast_off_score, fast_off_qlist, fast_off_out, fast_lds_bytes;   // k_fast_cells dynamic-LDS carve (bytes)
+    int fast_off_score, fast_off_qlist, fast_off_clist, fast_off_out, fast_lds_bytes;   // k_fast_cells dynamic-LDS carve (bytes)
     int cand_pitch;            // candidate entries per frame (all levels)
     int blur_pitch, nblur_tiles;   // bytes per frame of blurred-level storage; tiles of k_blur_levels over all levels
     int ini_th, min_th;
     SgxLevel lv[SGX_MAX_LEVELS];
 };
 
-struct SgxCell { short level, x0, y0, cw, ch, ox, oy, pad; };  // tile rect in level coords; ox=j*wCell, oy=i*hCell; pad = ceil(2^16 / ng), ng = dword groups per tile row (k_fast_cells)
+// a run of ncell horizontally adjacent cells of one cell row: tile rect in level coords (rw = the cells' interiors + the two 3-px aprons); ox = j0*wCell, oy = i*hCell;
+// ts = bytes between staged rows (multiple of 16), 1 << sh = lanes that stage one row, wc_m16 = ceil(2^16 / wcell)
+struct SgxRun { short level, x0, y0, rw, ch, ox, oy, ncell, wcell, ts, sh; unsigned short wc_m16; };
 
 // status bits written by kernels
 #define SGX_ST_CAND_OVERFLOW 1u
@@ -200,12 +204,19 @@ SGX_KERNEL(1024) k_pyramid(SgxOrbGeom g, SgxPyrTabs tb, const uint8_t *gray, int
 
 // ---------------------------------------------------------------------------------------------
 // k_fast_cells: ORBextractor.cc:790-830 for every cell of every level of every frame.
-// One 256-thread workgroup per (cell, frame).  cv::FAST(cell, 20, nms) with fallback
-// cv::FAST(cell, 7, nms) is evaluated from ONE threshold-free score map S = A-1, where
+// One workgroup per (run, frame): a run is up to G horizontally adjacent cells of one cell row (SgxRun, from the host).  The run's
+// pixels are staged once in LDS, so the 6-pixel overlap of neighbouring cells is loaded once, and the quick-test, corner and output lists are pooled over the run: lanes stay
+// full where a single cell leaves most of a wave idle.
+// cv::FAST(cell, 20, nms) with fallback cv::FAST(cell, 7, nms) is evaluated from ONE threshold-free score map S = A-1, where
 // A = max over the 16 nine-pixel arcs of min(v - ring) (bright) / min(ring - v) (dark):
 // a pixel is a corner at threshold t iff S >= t, its OpenCV response is S, NMS is a strict
 // '>' against the 8 neighbours inside the cell interior (everything else scores 0), and the
 // cell keeps {NMS-max, S>=20} unless that set is empty, then {NMS-max, S>=7}.
+// What is per CELL stays per cell although the tile and the score map are the run's:
+//   - the interiors of a run's cells partition tile columns [3, rw-3) at 3 + k*wcell; the NMS of a corner on the first / last column of its cell reads 0 for the three
+//     neighbours across that edge, whatever they scored and in whichever pass; rows outside the interior are never scored (a run is one cell row);
+//   - pass 0 (threshold 20) covers the run; a cell without an NMS survivor of pass 0 is searched again at 7 (pass 1), and only such cells: pass 1 tests, scores and reports
+//     pixels of those cells alone.  A score is threshold-free, so what pass 1 writes over a pass-0 score is the same value.
 // Candidates are appended unordered to the (frame, level) list as packed x | y<<12 | S<<24
 // with x,y relative to the (16,16) border origin (ORBextractor.cc:823-824); k_octree does not
 // depend on their order.
@@ -223,14 +234,6 @@ SGX_DEV uint32_t sgx_pk_min_u16(uint32_t a, uint32_t b)
     const sgx_u16x2 r = __builtin_elementwise_min(__builtin_bit_cast(sgx_u16x2, a), __builtin_bit_cast(sgx_u16x2, b));
     return __builtin_bit_cast(uint32_t, r);
 }
-SGX_DEV uint32_t sgx_pk_max_u16(uint32_t a, uint32_t b)
-{
-    const sgx_u16x2 r = __builtin_elementwise_max(__builtin_bit_cast(sgx_u16x2, a), __builtin_bit_cast(sgx_u16x2, b));
-    return __builtin_bit_cast(uint32_t, r);
-}
-// bytes (0, 2) or (1, 3) of a dword as 2 x u16: one v_perm_b32 (selector byte 0x0c = constant zero) instead of shift + mask
-SGX_DEV uint32_t sgx_even_bytes_u16(uint32_t v) { return __builtin_amdgcn_perm(0u, v, 0x0c020c00u); }
-SGX_DEV uint32_t sgx_odd_bytes_u16(uint32_t v) { return __builtin_amdgcn_perm(0u, v, 0x0c030c01u); }
 #else
 SGX_DEV uint32_t sgx_pk_usubsat_u16(uint32_t a, uint32_t b)
 {
@@ -242,13 +245,6 @@ SGX_DEV uint32_t sgx_pk_min_u16(uint32_t a, uint32_t b)
     const uint32_t al = a & 0xFFFFu, ah = a >> 16, bl = b & 0xFFFFu, bh = b >> 16;
     return (al < bl ? al : bl) | ((ah < bh ? ah : bh) << 16);
 }
-SGX_DEV uint32_t sgx_pk_max_u16(uint32_t a, uint32_t b)
-{
-    const uint32_t al = a & 0xFFFFu, ah = a >> 16, bl = b & 0xFFFFu, bh = b >> 16;
-    return (al > bl ? al : bl) | ((ah > bh ? ah : bh) << 16);
-}
-SGX_DEV uint32_t sgx_even_bytes_u16(uint32_t v) { return v & 0x00FF00FFu; }
-SGX_DEV uint32_t sgx_odd_bytes_u16(uint32_t v) { return (v >> 8) & 0x00FF00FFu; }
 #endif
 
 // ((hi:lo) >> sh) as 32 bits (v_alignbit_b32); with sh = 31 it shifts the sign bit of lo into hi from the right
@@ -270,126 +266,186 @@ SGX_DEV uint32_t sgx_has9(uint32_t m16)
     return (c & (m >> 8)) & 0xFFFFu;
 }
 
-#define SGX_FAST_THREADS 256     /* launch bound; the host launches 128 (2 waves per cell: measured best on MI355X — 0.184 ms per 64 frames vs 0.202 / 0.216 / 0.287 at 192 / 256 / 320) */
-SGX_KERNEL(SGX_FAST_THREADS) k_fast_cells(SgxOrbGeom g, const SgxCell *cells, const uint8_t *gray, int gray_pitch, const uint8_t *pyr,
+struct alignas(16) SgxU4 { uint32_t x, y, z, w; };
+
+#ifndef SGX_EMU
+// number of lanes below this one whose bit is set in a wave mask (v_mbcnt_lo / _hi)
+SGX_DEV int sgx_lane_rank(unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+#endif
+
+// the 16 ring pixels of the pixel at p (row stride ts), clockwise from (0, +3)
+SGX_DEV void sgx_fast_ring(const uint8_t *p, int ts, int (&r)[16])
+{
+    const uint8_t *p1 = p + ts, *p2 = p1 + ts, *p3 = p2 + ts, *m1 = p - ts, *m2 = m1 - ts, *m3 = m2 - ts;
+    r[0] = p3[0];   r[1] = p3[1];   r[2] = p2[2];   r[3] = p1[3];   r[4] = p[3];    r[5] = m1[3];   r[6] = m2[2];   r[7] = m3[1];
+    r[8] = m3[0];   r[9] = m3[-1];  r[10] = m2[-2]; r[11] = m1[-3]; r[12] = p[-3];  r[13] = p1[-3]; r[14] = p2[-2]; r[15] = p3[-1];
+}
+
+// Quick-test task gq = the 4 pixels at tile bytes 4*gq .. 4*gq+3 of a row.  Its flags sit where the packed compares leave them: pixel 0 -> bit 15, 1 -> 14, 2 -> 31, 3 -> 30.
+#define SGX_FAST_FLAG(i) (((i) & 2 ? 0x80000000u : 0x8000u) >> ((i) & 1))
+// the flags of the task's pixels that are interior pixels of a cell selected by cellmask
+SGX_DEV uint32_t sgx_fast_task_pixels(int gq, int lead, int rw, uint32_t wc_m16, uint32_t cellmask)
+{
+    uint32_t pm = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int x = 4 * gq + i - lead;                                        // tile column
+        if (x >= 3 && x < rw - 3 && ((cellmask >> (((uint32_t)(x - 3) * wc_m16) >> 16)) & 1u)) pm |= SGX_FAST_FLAG(i);
+    }
+    return pm;
+}
+
+#ifndef SGX_FAST_THREADS
+#define SGX_FAST_THREADS 256     /* launch bound and the host's default: 4 waves per run (2 or 3 cells at 640x480: the host's SGX_FAST_LDS_BUDGET) */
+#endif
+SGX_KERNEL(SGX_FAST_THREADS) k_fast_cells(SgxOrbGeom g, const SgxRun *runs, const uint8_t *gray, int gray_pitch, const uint8_t *pyr,
                              int batch, uint32_t *cand, int *cand_count, uint32_t *status)
 {
-    // LDS: carved from one dynamic pool sized on the host from the largest tile of this geometry (g.fast_* fields), so that
-    // the common 640x480 case (tiles <= 43x40) runs 8 workgroups per CU instead of the 5 a worst-case static layout allows.
+    // LDS: carved from one dynamic pool sized on the host from the largest run of this geometry (g.fast_* fields); the host picks the cells per run so that the pool
+    // stays within SGX_FAST_LDS_BUDGET: 6 workgroups = 24 waves resident per CU (the single-cell kernel had 16).
     SGX_DYN_LDS(pool);
-    uint32_t *tile_dw = (uint32_t *)pool;                                   // staged rows, 72 B stride; tile column x at byte lead + x
+    uint8_t *tile = (uint8_t *)pool;                                        // staged rows, c.ts bytes apart; tile column x at byte lead + x
     uint8_t *score = (uint8_t *)pool + g.fast_off_score;                    // threshold-free FAST score map, same layout
-    uint16_t *qlist = (uint16_t *)((uint8_t *)pool + g.fast_off_qlist);     // survivors of the quick test; bit 15 = is a corner
+    uint16_t *qlist = (uint16_t *)((uint8_t *)pool + g.fast_off_qlist);     // survivors of the quick test: row << 9 | byte column
+    uint16_t *clist = (uint16_t *)((uint8_t *)pool + g.fast_off_clist);     // those that pass the ring test (corners at the pass's threshold)
     uint32_t *outbuf = (uint32_t *)((uint8_t *)pool + g.fast_off_out);      // NMS survivors (packed candidates)
-    SGX_LDS int n_lo, out_base, n_quick;
-    const uint8_t *tile = (const uint8_t *)tile_dw;
+    SGX_LDS int n_quick, n_corner, n_out, n_glist, out_base;
+    SGX_LDS uint32_t cell_hit;                                              // bit k: cell k of the run has an NMS survivor
+    SGX_LDS uint8_t glist[SGX_FAST_MAXGROUPS];                              // pass 1: the quick-test tasks of a row that touch a cell to search again
 
-    // block -> (cell, frame): frame fastest so that frame f stays on XCD f%8 (block b -> XCD b%8)
+    // block -> (run, frame): frame fastest so that frame f stays on XCD f%8 (block b -> XCD b%8)
     const int bid = (int)blockIdx.x;
-    const int frame = bid % batch, cid = bid / batch;
-    const SgxCell c = cells[cid];
-    const int cw = c.cw, ch = c.ch, level = c.level;
+    const int frame = bid % batch, rid = bid / batch;
+    const SgxRun c = runs[rid];
+    const int rw = c.rw, ch = c.ch, level = c.level, ts = c.ts, ncell = c.ncell, wcell = c.wcell;
+    const uint32_t wc_m16 = c.wc_m16;
     int stride;
     const uint8_t *img = sgx_level_ptr(g, gray, gray_pitch, pyr, frame, level, &stride);
     const int thr_lo = g.min_th, thr_hi = g.ini_th;
-    const int xa = c.x0 & ~3, lead = c.x0 - xa, ndw = (lead + cw + 3) >> 2;
-    const int SD = SGX_TILE_STRIDE / 4;
+    const int x16 = c.x0 & ~15, lead = c.x0 - x16;
+    const int T = (int)blockDim.x;
 
-    // phase A: stage the tile rows as aligned dwords (coalesced global loads, one LDS dword store each); zero the score map
-    SGX_THREADS_BEGIN(tid)
-    if (tid == 0) { n_lo = 0; n_quick = 0; }
-    for (int i = tid; i < ch * SD; i += (int)blockDim.x) {
-        const int r = i / SD, q = i - r * SD;
-        tile_dw[i] = q < ndw ? *(const uint32_t *)(img + (size_t)(c.y0 + r) * stride + xa + 4 * q) : 0u;
+    // phase A: stage the run's rows in 16-byte units (a power-of-two group of lanes per row: no division), zero-filled to the row stride; zero the score map
+    {
+        const int sh = c.sh, units = ts >> 4, n16 = (lead + rw + 15) >> 4;      // the level's rows are readable up to the next multiple of 16 (x0 + rw <= w - 16)
+        const bool a16 = ((((uintptr_t)img) | (uintptr_t)stride) & 15) == 0;   // level 0 is the caller's image: 4-byte alignment is all the entry asks for
+        SGX_THREADS_BEGIN(tid)
+        if (tid == 0) { n_quick = 0; n_corner = 0; n_out = 0; n_glist = 0; cell_hit = 0u; }
+        const int q = tid & ((1 << sh) - 1);
+        if (q < units)
+            for (int r = tid >> sh; r < ch; r += T >> sh) {
+                SgxU4 v = { 0u, 0u, 0u, 0u };
+                if (q < n16) {
+                    const uint8_t *src = img + (size_t)(c.y0 + r) * stride + x16 + 16 * q;
+                    if (a16) v = *(const SgxU4 *)src;
+                    else { const uint32_t *s4 = (const uint32_t *)src; v.x = s4[0]; v.y = s4[1]; v.z = s4[2]; v.w = s4[3]; }
+                }
+                *(SgxU4 *)(tile + r * ts + 16 * q) = v;
+                *(SgxU4 *)(score + r * ts + 16 * q) = SgxU4{ 0u, 0u, 0u, 0u };
+            }
+        SGX_THREADS_END
     }
-    for (int i = tid; i < ch * SD; i += (int)blockDim.x) ((uint32_t *)score)[i] = 0u;       // score map (72-byte rows) as dwords
-    SGX_THREADS_END
     SGX_SYNC();
 
     // Two passes, as the reference: FAST at iniThFAST first; only a cell that yields no corner is searched again at minThFAST (ORBextractor.cc:806-817).  The
     // segment test, the threshold-free score and the 3x3 NMS of a pass see exactly the corners cv::FAST(threshold) sees: a pixel is a corner at threshold t iff its
     // score >= t, and a neighbour that is not a corner at t has a score below t, so it cannot suppress one that is (cv::FAST scores it 0).  Textured cells — the
     // common case — never pay for the low-threshold pass, whose quick test lets several times more pixels through.
-    const int ih = ch - 6, ng = (lead + cw + 3) >> 2;
-    const unsigned ng_m16 = (unsigned)(unsigned short)c.pad;
+    const int ih = ch - 6, tsd = ts >> 2;
+    const int gq_first = (lead + 3) >> 2, ngt = ((lead + rw - 4) >> 2) - gq_first + 1;    // quick-test tasks per row: the dwords that hold an interior pixel
+    uint32_t cellmask = (1u << ncell) - 1u;                                          // the cells this pass searches
     for (int pass = 0; pass < 2; pass++) {
         const int thr = pass == 0 ? thr_hi : thr_lo;
+        if (pass) {         // the tasks of a row that touch a cell of this pass, compacted: lanes stay dense when one cell of the run is searched again
+            SGX_THREADS_BEGIN(tid)
+            if (tid == 0) { n_quick = 0; n_corner = 0; }
+            for (int gi = tid; gi < ngt; gi += T)
+                if (sgx_fast_task_pixels(gq_first + gi, lead, rw, wc_m16, cellmask)) glist[sgx_atomic_add(&n_glist, 1)] = (uint8_t)(gq_first + gi);
+            SGX_THREADS_END
+            SGX_SYNC();
+        }
         // phase B1: necessary condition on every interior pixel.  A 9-pixel arc of the 16-ring contains one pixel of every antipodal
         // pair, so a corner needs (p0|p8) & (p4|p12) all-brighter or all-darker (the high-speed test cv::FAST itself starts with).
-        // A task = 4 horizontally adjacent pixels: the compass pixels come from 7 aligned LDS dwords.  Survivors are compacted.
+        // A task = the 4 pixels of one tile dword: centre, below and above are aligned dwords, left and right two v_alignbyte of the neighbouring dwords.  A thread keeps its
+        // dword column and walks down rows `nb` apart, so what depends on the columns (which pixels are interior pixels of a searched cell) is worked out once per thread.
+        // The compares are plain 32-bit adds on 2 x 16-bit fields (even / odd pixels) with a guard bit: for bytes r, v and threshold t the field r + (0x7FFF - t - v) has bit 15
+        // set iff r > v + t, the field (v + 0x7FFF - t) - r iff r < v - t; every field stays inside [0x7E01, 0x80FE], so no carry or borrow crosses fields.  Simple integer
+        // instructions issue at twice the rate of the packed 16-bit ones this replaces.  Survivors are compacted with one list reservation per wave.
+        const int ngl = pass ? n_glist : ngt, nb = max(1, T / max(1, ngl));
         SGX_THREADS_BEGIN(tid)
-        for (int t = tid; t < ih * ng; t += (int)blockDim.x) {
-            const int yq = (int)(((unsigned)t * ng_m16) >> 16), y = 3 + yq, gq = t - yq * ng;          // t / ng, t % ng with the host's 16-bit reciprocal (exact for t < 4096, ng <= 16)
-            const int x0 = 4 * gq + 3 - lead;                                   // tile column of the first pixel of the group
-            if (x0 + 3 < 3 || x0 >= cw - 3) continue;
-            const uint32_t *rc = tile_dw + y * SD + gq, *rp = rc + 3 * SD, *rm = rc - 3 * SD;
-            const bool has1 = gq + 1 < SD, has2 = gq + 2 < SD;
-            const uint32_t C0 = rc[0], C1 = has1 ? rc[1] : 0u, C2 = has2 ? rc[2] : 0u;
-            const uint32_t P0 = rp[0], P1 = has1 ? rp[1] : 0u, M0 = rm[0], M1 = has1 ? rm[1] : 0u;
-            // the 4 pixels of the task as packed bytes: centre v (tile bytes 3..6 of the group), the compass pixels below / above (same columns of rows
-            // y+3 / y-3) and right / left (bytes 6..9 / 0..3), then as two sets of 2 x u16 (even / odd pixels) for the packed saturating compares:
-            //   brighter  <=>  usubsat(r, v + t) != 0      darker  <=>  usubsat(usubsat(v, t), r) != 0
-            const uint32_t V = sgx_alignbyte(C1, C0, 3), R4 = sgx_alignbyte(C2, C1, 2), R12 = C0, R0 = sgx_alignbyte(P1, P0, 3), R8 = sgx_alignbyte(M1, M0, 3);
-            const uint32_t T2 = (uint32_t)thr * 0x00010001u;
-            uint32_t any[2];
-#if !defined(SGX_FAST_QUICK_V2)      /* the round-3 formulation; V2 (below) is the round-4 attempt kept for the record: 17 fewer instructions per task, 5 % SLOWER (A/B, tools/ab_run.sh) */
+        for (int cb = tid; cb < ngl * nb; cb += T) {
+            const int band = (int)((unsigned)cb / (unsigned)ngl), gi = cb - band * ngl;
+            const int gq = pass ? (int)glist[gi] : gq_first + gi;
+            const uint32_t pm = sgx_fast_task_pixels(gq, lead, rw, wc_m16, cellmask);
+            const uint32_t KD = 0x7FFF7FFFu - (uint32_t)thr * 0x00010001u;
+            const uint32_t *rc = (const uint32_t *)tile + (3 + band) * tsd + gq;
+            for (int y = 3 + band; y < 3 + ih; y += nb, rc += nb * tsd) {
+                const uint32_t C0 = rc[-1], C1 = rc[0], C2 = rc[1], P = rc[3 * tsd], M = rc[-3 * tsd];        // dword gq - 1 of the first task feeds apron pixels only; the row stride leaves room for gq + 1
+                const uint32_t R4 = sgx_alignbyte(C2, C1, 3), R12 = sgx_alignbyte(C1, C0, 1);              // the pixels 3 to the right / left
+                uint32_t any[2];
     #pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) {
-                const int sh = 8 * s2;
-                const uint32_t v = (V >> sh) & 0x00FF00FFu, r0 = (R0 >> sh) & 0x00FF00FFu, r8 = (R8 >> sh) & 0x00FF00FFu, r4 = (R4 >> sh) & 0x00FF00FFu, r12 = (R12 >> sh) & 0x00FF00FFu;
-                const uint32_t hi = v + T2, lo = sgx_pk_usubsat_u16(v, T2);
-                const uint32_t br = sgx_pk_min_u16(sgx_pk_usubsat_u16(r0, hi) | sgx_pk_usubsat_u16(r8, hi), sgx_pk_usubsat_u16(r4, hi) | sgx_pk_usubsat_u16(r12, hi));
-                const uint32_t dk = sgx_pk_min_u16(sgx_pk_usubsat_u16(lo, r0) | sgx_pk_usubsat_u16(lo, r8), sgx_pk_usubsat_u16(lo, r4) | sgx_pk_usubsat_u16(lo, r12));
-                any[s2] = br | dk;
-            }
-#else
-    #pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) {
-                // round-4 attempt: (p0 | p8) & (p4 | p12) brighter  <=>  min(max(r0, r8), max(r4, r12)) > v + t, darker  <=>  max(min(r0, r8), min(r4, r12)) < v - t: two packed
-                // max / min pairs and ONE saturating subtraction per polarity instead of four each; the 2 x u16 operands come out of the byte quads with one v_perm_b32.
-                // Measured 1.158 against 1.106 ms per 512 frames: it trades 2-cycle logic / shift instructions for 4-cycle v_perm_b32 / v_pk_max_u16 (r2_ubench_valu_issue.txt)
-                const uint32_t v = s2 ? sgx_odd_bytes_u16(V) : sgx_even_bytes_u16(V), r0 = s2 ? sgx_odd_bytes_u16(R0) : sgx_even_bytes_u16(R0), r8 = s2 ? sgx_odd_bytes_u16(R8) : sgx_even_bytes_u16(R8),
-                               r4 = s2 ? sgx_odd_bytes_u16(R4) : sgx_even_bytes_u16(R4), r12 = s2 ? sgx_odd_bytes_u16(R12) : sgx_even_bytes_u16(R12);
-                const uint32_t hi = v + T2, lo = sgx_pk_usubsat_u16(v, T2);
-                const uint32_t br = sgx_pk_usubsat_u16(sgx_pk_min_u16(sgx_pk_max_u16(r0, r8), sgx_pk_max_u16(r4, r12)), hi);
-                const uint32_t dk = sgx_pk_usubsat_u16(lo, sgx_pk_max_u16(sgx_pk_min_u16(r0, r8), sgx_pk_min_u16(r4, r12)));
-                any[s2] = br | dk;
-            }
-#endif
-            if ((any[0] | any[1]) == 0u) continue;                                   // three tasks in four hold no survivor
-    #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int x = x0 + i;
-                const uint32_t f = (any[i & 1] >> (16 * (i >> 1))) & 0xFFFFu;          // pixel i = half (i>>1) of set (i&1)
-                if (x >= 3 && x < cw - 3 && f) {
-                    const int slot = sgx_atomic_add(&n_quick, 1);
-                    qlist[slot] = (uint16_t)(y * SGX_TILE_STRIDE + lead + x);
+                for (int s2 = 0; s2 < 2; s2++) {
+                    const int sh = 8 * s2;
+                    const uint32_t v = (C1 >> sh) & 0x00FF00FFu, r0 = (P >> sh) & 0x00FF00FFu, r8 = (M >> sh) & 0x00FF00FFu, r4 = (R4 >> sh) & 0x00FF00FFu, r12 = (R12 >> sh) & 0x00FF00FFu;
+                    const uint32_t kb = KD - v, kd = KD + v;
+                    const uint32_t br = ((r0 + kb) | (r8 + kb)) & ((r4 + kb) | (r12 + kb));          // (p0 | p8) & (p4 | p12) brighter
+                    const uint32_t dk = ((kd - r0) | (kd - r8)) & ((kd - r4) | (kd - r12));          // ... darker
+                    any[s2] = br | dk;
                 }
+                const uint32_t f = pm & ((any[0] & 0x80008000u) | ((any[1] & 0x80008000u) >> 1));
+                const uint32_t pos0 = ((uint32_t)y << 9) | (uint32_t)(4 * gq);
+#ifndef SGX_EMU
+                // This arm exists in the device build only and the emulator's twin below is a different code path: the @gpu cases of tests/test_fast_cell_runs.py and
+                // tests/test_orb_gpu.py are its only coverage.
+                // one list reservation per wave and row step: the survivors are laid out pixel plane by pixel plane, a lane's slot within a plane is its rank among the
+                // lanes that hold one (three row steps in four hold no survivor in most lanes; a wave without any skips the reservation)
+                const unsigned long long b0 = __builtin_amdgcn_ballot_w64((f & SGX_FAST_FLAG(0)) != 0u), b1 = __builtin_amdgcn_ballot_w64((f & SGX_FAST_FLAG(1)) != 0u),
+                                         b2 = __builtin_amdgcn_ballot_w64((f & SGX_FAST_FLAG(2)) != 0u), b3 = __builtin_amdgcn_ballot_w64((f & SGX_FAST_FLAG(3)) != 0u);
+                if ((b0 | b1 | b2 | b3) == 0ull) continue;
+                const int c0 = __builtin_popcountll(b0), c1 = c0 + __builtin_popcountll(b1), c2 = c1 + __builtin_popcountll(b2), c3 = c2 + __builtin_popcountll(b3);
+                int base = 0;
+                if (sgx_lane_rank(__builtin_amdgcn_ballot_w64(true)) == 0) base = sgx_atomic_add(&n_quick, c3);     // the first active lane reserves for the wave
+                base = __builtin_amdgcn_readfirstlane(base);
+                if (f & SGX_FAST_FLAG(0)) qlist[base + sgx_lane_rank(b0)] = (uint16_t)pos0;
+                if (f & SGX_FAST_FLAG(1)) qlist[base + c0 + sgx_lane_rank(b1)] = (uint16_t)(pos0 + 1);
+                if (f & SGX_FAST_FLAG(2)) qlist[base + c1 + sgx_lane_rank(b2)] = (uint16_t)(pos0 + 2);
+                if (f & SGX_FAST_FLAG(3)) qlist[base + c2 + sgx_lane_rank(b3)] = (uint16_t)(pos0 + 3);
+#else
+                if (f == 0u) continue;                                                  // scalar twin: one reservation per task
+                int slot = sgx_atomic_add(&n_quick, __builtin_popcount(f));
+                for (int i = 0; i < 4; i++)
+                    if (f & SGX_FAST_FLAG(i)) qlist[slot++] = (uint16_t)(pos0 + i);
+#endif
             }
         }
         SGX_THREADS_END
         SGX_SYNC();
 
-        // phase B2: full segment test (>= 9 contiguous ring pixels brighter than v+t or darker than v-t) on the survivors.
+        // phase B2: full segment test (>= 9 contiguous ring pixels brighter than v+t or darker than v-t) on the run's pooled survivors; the corners are compacted.
         // The two 16-bit ring masks are shifted in from sign bits with v_alignbit (2 VALU per ring pixel and polarity).
         SGX_THREADS_BEGIN(tid)
-        for (int t = tid; t < n_quick; t += (int)blockDim.x) {
+        for (int t = tid; t < n_quick; t += T) {
             const int pos = qlist[t];
-            const uint8_t *p = tile + pos;
+            const uint8_t *p = tile + (pos >> 9) * ts + (pos & 511);
             const int v = p[0], lo = v - thr, hi = v + thr;
-            int r[16];                                                    // the 16 ring pixels, clockwise from (0, +3) — loaded once for the mask test and the score
-            r[0] = p[3 * SGX_TILE_STRIDE];       r[1] = p[3 * SGX_TILE_STRIDE + 1];  r[2] = p[2 * SGX_TILE_STRIDE + 2];
-            r[3] = p[SGX_TILE_STRIDE + 3];       r[4] = p[3];                        r[5] = p[-SGX_TILE_STRIDE + 3];
-            r[6] = p[-2 * SGX_TILE_STRIDE + 2];  r[7] = p[-3 * SGX_TILE_STRIDE + 1]; r[8] = p[-3 * SGX_TILE_STRIDE];
-            r[9] = p[-3 * SGX_TILE_STRIDE - 1];  r[10] = p[-2 * SGX_TILE_STRIDE - 2]; r[11] = p[-SGX_TILE_STRIDE - 3];
-            r[12] = p[-3];                       r[13] = p[SGX_TILE_STRIDE - 3];     r[14] = p[2 * SGX_TILE_STRIDE - 2];
-            r[15] = p[3 * SGX_TILE_STRIDE - 1];
+            int r[16];
+            sgx_fast_ring(p, ts, r);
             uint32_t mb = 0, md = 0;
     #pragma unroll
             for (int k = 0; k < 16; k++) { mb = sgx_alignbit(mb, (uint32_t)(hi - r[k]), 31); md = sgx_alignbit(md, (uint32_t)(r[k] - lo), 31); }
-            if (!(sgx_has9(mb & 0xFFFFu) | sgx_has9(md & 0xFFFFu))) continue;
-            qlist[t] = (uint16_t)(pos | 0x8000);                          // pos < 68*72 < 2^15
-            // threshold-free score of the corner, in the same pass (phase C of the first version cost one more barrier and one more walk of the list)
+            if (sgx_has9(mb & 0xFFFFu) | sgx_has9(md & 0xFFFFu)) clist[sgx_atomic_add(&n_corner, 1)] = (uint16_t)pos;
+        }
+        SGX_THREADS_END
+        SGX_SYNC();
+
+        // phase C: threshold-free score, over the corners alone (one in five of the quick test's survivors): every lane of the pass works
+        SGX_THREADS_BEGIN(tid)
+        for (int t = tid; t < n_corner; t += T) {
+            const int pos = clist[t], off = (pos >> 9) * ts + (pos & 511);
+            const uint8_t *p = tile + off;
+            const int v = p[0];
+            int r[16];
+            sgx_fast_ring(p, ts, r);
             int d[16];
     #pragma unroll
             for (int k = 0; k < 16; k++) d[k] = v - r[k];
@@ -405,37 +461,37 @@ SGX_KERNEL(SGX_FAST_THREADS) k_fast_cells(SgxOrbGeom g, const SgxCell *cells, co
                 const int mx9 = max(max(mx4[k], mx4[(k + 4) & 15]), d[(k + 8) & 15]);
                 A = max(A, mn9); Bm = min(Bm, mx9);
             }
-            const int s = max(A, -Bm) - 1;
-            score[pos] = (uint8_t)s;
+            score[off] = (uint8_t)(max(A, -Bm) - 1);
         }
         SGX_THREADS_END
         SGX_SYNC();
 
-        // phase D: NMS (strict > over the 8 neighbours; apron and non-corners are 0), count survivors
+        // phase D: NMS (strict > over the 8 neighbours inside the corner's own cell; apron, non-corners and everything across a cell edge are 0)
         SGX_THREADS_BEGIN(tid)
-        for (int i = tid; i < n_quick; i += (int)blockDim.x) {
-            if (!(qlist[i] & 0x8000)) continue;
-            const int pos = qlist[i] & 0x7FFF;
-            const uint8_t *s = score + pos;
+        for (int i = tid; i < n_corner; i += T) {
+            const int pos = clist[i], y = pos >> 9, x = (pos & 511) - lead;
+            const int k = (int)(((uint32_t)(x - 3) * wc_m16) >> 16);                      // (x - 3) / wcell: the host's 16-bit reciprocal is exact for x < 512
+            const int xl = 3 + k * wcell, xr = min(xl + wcell, rw - 3) - 1;             // first and last interior column of cell k
+            const uint8_t *s = score + y * ts + lead + x, *su = s - ts, *sd = s + ts;
             const int v = s[0];
-            const bool mx = v > s[-1] && v > s[1] && v > s[-SGX_TILE_STRIDE - 1] && v > s[-SGX_TILE_STRIDE] && v > s[-SGX_TILE_STRIDE + 1] &&
-                            v > s[SGX_TILE_STRIDE - 1] && v > s[SGX_TILE_STRIDE] && v > s[SGX_TILE_STRIDE + 1];
-            if (mx && v >= thr) {
-                const int slot = sgx_atomic_add(&n_lo, 1);
-                const int y = pos / SGX_TILE_STRIDE, x = pos - y * SGX_TILE_STRIDE - lead;
-                outbuf[slot] = (uint32_t)(x + c.ox) | ((uint32_t)(y + c.oy) << 12) | ((uint32_t)v << 24);
+            int nmax = max((int)su[0], (int)sd[0]);
+            if (x > xl) nmax = max(nmax, max(max((int)su[-1], (int)s[-1]), (int)sd[-1]));
+            if (x < xr) nmax = max(nmax, max(max((int)su[1], (int)s[1]), (int)sd[1]));
+            if (v > nmax && v >= thr) {
+                sgx_atomic_or(&cell_hit, 1u << k);
+                outbuf[sgx_atomic_add(&n_out, 1)] = (uint32_t)(x + c.ox) | ((uint32_t)(y + c.oy) << 12) | ((uint32_t)v << 24);
             }
         }
         SGX_THREADS_END
         SGX_SYNC();
 
-        if (n_lo > 0 || thr_hi == thr_lo) break;                      // uniform: n_lo is final after the barrier above
-        SGX_THREADS_BEGIN(tid) if (tid == 0) n_quick = 0; SGX_THREADS_END
-        SGX_SYNC();
+        if (pass || thr_hi == thr_lo) break;
+        cellmask &= ~cell_hit;                                          // uniform: cell_hit is final after the barrier above
+        if (cellmask == 0u) break;
     }
 
-    // phase E: reserve space in the (frame, level) list, emit the NMS survivors of the pass that found corners
-    const int n_emit = n_lo;
+    // phase E: reserve space in the (frame, level) list (one atomic per run), emit the NMS survivors
+    const int n_emit = n_out;
     SGX_THREADS_BEGIN(tid)
     if (tid == 0 && n_emit > 0) out_base = sgx_atomic_add(&cand_count[frame * g.nlevels + level], n_emit);
     SGX_THREADS_END
@@ -444,7 +500,7 @@ SGX_KERNEL(SGX_FAST_THREADS) k_fast_cells(SgxOrbGeom g, const SgxCell *cells, co
         uint32_t *dst = cand + (size_t)frame * g.cand_pitch + g.lv[level].cand_off;
         const int dcap = g.lv[level].cand_cap;
         SGX_THREADS_BEGIN(tid)
-        for (int i = tid; i < n_emit; i += (int)blockDim.x) {
+        for (int i = tid; i < n_emit; i += T) {
             const int slot = out_base + i;
             if (slot < dcap) dst[slot] = outbuf[i];
             else sgx_atomic_or(status, SGX_ST_CAND_OVERFLOW);
