@@ -654,10 +654,13 @@ int sgx_flow_levels(const sgx_flow *h);          /* pyramid levels actually used
 /* d_gray: batch frames of height rows x pitch bytes (pitch and pointer multiples of 4).  When the handle holds a previous batch of the same size:
  * d_prev_xy[f*cap + i] = (x, y) of keypoint i of frame f in the previous frame (nextPts), d_status (optional) = State; *have_prev (host, optional) = 1.
  * First call after create / reset: only the pyramid is built, *have_prev = 0 (the reference skips the whole mask step, Frame.cc:155-163).
+ * Tracking needs width and height of at least 22 (win_size + 1: the tracker reflects a window index once, which covers a 21-pixel window only on such a side): a call that
+ * would track on a smaller handle returns SGX_ERR_UNSUPPORTED and changes nothing.  Pyramid-only calls (the first after create / reset) work at any size from 2 x 2.
  * Asynchronous on `stream`. */
 int sgx_flow_lk_batch_dev(sgx_flow *h, const uint8_t *d_gray, int pitch, int batch, const sgx_keypoint *d_keys, const int32_t *d_n, int cap,
                           float *d_prev_xy, uint8_t *d_status, int32_t *have_prev, void *stream);
-/* cv::calcOpticalFlowPyrLK(gray_from, gray_to, pts, next_pts, status, ...) on one host image pair (n points, 2 floats each).  Synchronous; resets the streaming state. */
+/* cv::calcOpticalFlowPyrLK(gray_from, gray_to, pts, next_pts, status, ...) on one host image pair (n points, 2 floats each).  Synchronous; resets the streaming state.
+ * SGX_ERR_UNSUPPORTED when the handle's width or height is below 22 (see sgx_flow_lk_batch_dev); OpenCV itself accepts such images, the reference never passes one. */
 int sgx_flow_lk(sgx_flow *h, const uint8_t *gray_from, const uint8_t *gray_to, int stride, const float *pts, int n, float *next_pts, uint8_t *status);
 /* Frame.cc:454-472 for `batch` frames: pair selection against the PREVIOUS frame's person boxes (d_pre_have_dynamic = bPreFrameHavePotentialDynamicObj,
  * d_pre_boxes / d_pre_nboxes = vPreFramePotentialDynamicBorder in the layout sgx_det_detect_batch_dev writes; all three may be NULL) and

@@ -91,6 +91,11 @@ static int build_pyramid(sgx_flow *h, int slot, const uint8_t *d_gray, int pitch
     return SGX_OK;
 }
 
+// The tracker stages its windows with ONE fold of REFLECT_101 (sgx_reflect1).  A window reads indices -21 .. len + 20 of a side of length len, which one fold covers
+// only for len >= SGX_LK_WIN + 1.  Levels 1 .. are that large by construction; level 0 is the caller's: smaller images get a pyramid (any size) but are not tracked.  On the
+// device a 5 x 40 pair came out different from the oracle in 4 of 64 points (tests/lk_track_cases.py, case 2).  The emulator build refuses too: one contract for both.
+static bool trackable(const sgx_flow *h) { return h->cfg.width > SGX_LK_WIN && h->cfg.height > SGX_LK_WIN; }
+
 static int track(sgx_flow *h, int cur_slot, int prev_slot, int batch, const sgx_keypoint *d_keys, const int32_t *d_n, int cap, float *d_prev_xy, uint8_t *d_status, sgx_stream_t st)
 {
     SgxLkArgs A;
@@ -122,6 +127,7 @@ extern "C" int sgx_flow_lk_batch_dev(sgx_flow *h, const uint8_t *d_gray, int pit
     const int cur = h->cur, prev = cur ^ 1;
     const bool tracked = h->prev_batch == batch;
     if (tracked && (!d_keys || !d_n || !d_prev_xy || cap < 1)) return SGX_ERR_INVALID;
+    if (tracked && !trackable(h)) return SGX_ERR_UNSUPPORTED;          // before the pyramid: a refused call changes nothing
     int rc = build_pyramid(h, cur, d_gray, pitch, batch, st);
     if (rc != SGX_OK) return rc;
     if (tracked) { rc = track(h, cur, prev, batch, d_keys, d_n, cap, d_prev_xy, d_status, st); if (rc != SGX_OK) return rc; }
@@ -134,6 +140,7 @@ extern "C" int sgx_flow_lk_batch_dev(sgx_flow *h, const uint8_t *d_gray, int pit
 extern "C" int sgx_flow_lk(sgx_flow *h, const uint8_t *gray_from, const uint8_t *gray_to, int stride, const float *pts, int n, float *next_pts, uint8_t *status)
 {
     if (!h || !gray_from || !gray_to || stride < h->cfg.width || n < 0 || (n > 0 && (!pts || !next_pts))) return SGX_ERR_INVALID;
+    if (!trackable(h)) return SGX_ERR_UNSUPPORTED;
     if (n == 0) return SGX_OK;
     const int W = h->cfg.width, H = h->cfg.height, P = (W + 3) & ~3;
     std::vector<uint8_t> pack((size_t)P * H * 2, 0);

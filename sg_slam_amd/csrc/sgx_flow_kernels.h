@@ -328,7 +328,9 @@ SGX_DEV float sgx_wave_sum_f32(int v)
     return fmaf((float)hi, 65536.0f, (float)lo);       /* |hi| <= 2^21, lo < 2^22: both conversions and the product are exact, the fused add rounds the exact integer once */
 }
 SGX_DEV int sgx_mul24(int a, int b) { return __mul24(a, b); }          /* both operands fit 24 bits at every call site */
-/* REFLECT_101 for indices at most one image length outside, clamped (the clamp only ever acts on tile bytes no window uses) */
+/* REFLECT_101 by one fold, then clamped: exact for -(2 len - 2) <= p <= 2 len - 2.  A window uses indices -21 .. len + 20, so the clamp acts only on tile bytes no window uses
+ * as long as len >= 22.  Every level above 0 is that large by construction and the host refuses to track a smaller level 0 (sgx_flow.cpp: trackable); without that refusal a
+ * 5 x 40 image tracked differently from the oracle on the device, while 21 x 21, 20 x 33, 12 x 9 and 42 x 19 happened to agree (tests/lk_track_cases.py) */
 SGX_DEV int sgx_reflect1(int p, int len) { p = p < 0 ? -p : p; p = p >= len ? 2 * len - 2 - p : p; return min(max(p, 0), len - 1); }
 
 typedef short sgx_i16x2 __attribute__((ext_vector_type(2)));

@@ -35,7 +35,9 @@ def check_pyramid(lib, orc):
         img[h // 4:h // 2, w // 4:w // 2] = 200
         fl = OpticalFlowLK(width=w, height=h, lib=lib)
         pts = np.array([[w / 2, h / 2]], 'f4')
-        fl(img, img, pts)                                   # builds slot 0 (from-image) and slot 1
+        got, st = fl(img, img, pts)                         # builds slot 0 (from-image) and slot 1
+        ref, rst = orc.lk_pyr(img, img, pts)
+        assert (st == rst).all() and (got.view(np.uint32) == ref.view(np.uint32)).all(), f'image tracked into itself differs from the oracle ({w}x{h})'
         ref = img
         for l in range(fl.levels):
             got = fl.debug_level(0, 0, l)

@@ -63,9 +63,11 @@ def test_collective_entry_needs_no_rccl_at_load_time():
 
 
 def test_tap_builds_export_the_taps():
-    for so in (os.path.join(ROOT, 'tests', 'taps', 'libsgx_taps.so'), os.path.join(ROOT, 'tests', 'emu', 'libsgx_emu.so')):
-        if not os.path.exists(so):
-            pytest.skip(so + ' not built')
+    import subprocess
+    for target, so in (('taps', os.path.join(ROOT, 'tests', 'taps', 'libsgx_taps.so')), ('emu', os.path.join(ROOT, 'tests', 'emu', 'libsgx_emu.so'))):
+        if not os.path.exists(so):      # normally built by __graft_entry__.build(); a missing library is built here, never skipped over
+            subprocess.check_call(['make', '-s', '-j16', '-C', os.path.join(ROOT, 'sg_slam_amd', 'csrc'), target])
+        assert os.path.exists(so), so + ' not built (make -C sg_slam_amd/csrc ' + target + ')'
         dll = ctypes.CDLL(so)
         for s in _declared() + _declared('sgx_debug.h'):
             assert hasattr(dll, s), (so, s)
