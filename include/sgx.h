@@ -423,7 +423,8 @@ int sgx_objdb_get(const sgx_objdb *db, int index, sgx_semantic_object *out);  /*
 /* ---- ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (src/sg-slam/include/ORBVocabulary.h:31-32) ----------------------------------------------
  * The bag-of-words transform behind Frame::ComputeBoW (src/sg-slam/src/Frame.cc:422-429) and KeyFrame::ComputeBoW (src/sg-slam/src/KeyFrame.cc:60-69):
  *     mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4)          src/sg-slam/Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1139-1206
- * The per-feature tree descent (:1231-1273, FORB::distance FORB.cpp:81-101) runs on the device; BowVector / FeatureVector assembly and scoring are host work.
+ * The per-feature tree descent (:1231-1273, FORB::distance FORB.cpp:81-101) runs on the device; BowVector / FeatureVector assembly and scoring are host work in
+ * sgx_voc_transform / sgx_voc_score and device work in sgx_voc_bow_batch_dev and the sgx_kfdb_* entries.
  *
  * sgx_voc_load: loadFromTextFile (:1351-1438) for a path ending in ".txt", loadFromBinaryFile (:1467-1510) otherwise — System::System's rule (System.cc:69-73).
  * sgx_voc_create: the same tree from flat arrays: node 0 is the root, parent[i] < i for i >= 1, desc32 = nnodes x 32 bytes, is_leaf[i] gives node i the next word id. */
@@ -441,9 +442,81 @@ int sgx_voc_transform(sgx_voc *v, int n, const uint8_t *desc, int levelsup, int3
 /* the per-feature part for B frames resident on the device (frame b: d_n[b] descriptors at d_desc + b * desc_pitch; outputs with row pitch cap); asynchronous on `stream` */
 int sgx_voc_transform_batch_dev(sgx_voc *v, const uint8_t *d_desc, size_t desc_pitch, const int32_t *d_n, int batch, int cap, int levelsup,
                                 int32_t *d_word_id, double *d_weight, int32_t *d_feat_node, void *stream);
+/* The BowVector half of transform() (:1159-1204; BowVector.cpp:33-86) for the B frames of sgx_voc_transform_batch_dev, on the device: d_word_id / d_weight are that
+ * entry's outputs (row pitch cap, d_n[b] features in row b).  Row b of d_bow_ids / d_bow_weights (pitch cap) receives the BowVector, d_nbow[b] its size: word ids
+ * ascending, weights of a repeated word accumulated in feature order (TF_IDF, TF) or the first one kept (IDF, BINARY), stopped words (!(w > 0), :1170) dropped, then the
+ * / nd step of :1177-1183 or normalize() with the L1 / L2 norm summed in ascending word order: bit for bit what sgx_voc_transform returns for the same descriptors.
+ * Rows and counts are the query layout of sgx_kfdb_detect_batch_dev.  cap <= 8192 (SGX_ERR_UNSUPPORTED beyond).  Asynchronous on `stream`. */
+int sgx_voc_bow_batch_dev(sgx_voc *v, const int32_t *d_n, int batch, int cap, const int32_t *d_word_id, const double *d_weight,
+                          int32_t *d_bow_ids, double *d_bow_weights, int32_t *d_nbow, void *stream);
 /* double TemplatedVocabulary::score(const BowVector&, const BowVector&) (:1210-1215) for the L1 scoring the ORB vocabulary files select (L1Scoring::score,
  * src/sg-slam/Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-67; callers KeyFrameDatabase.cc:133,249, LoopClosing.cc:134); SGX_ERR_UNSUPPORTED for the other scoring types */
 int sgx_voc_score(const sgx_voc *v, int n1, const int32_t *ids1, const double *w1, int n2, const int32_t *ids2, const double *w2, double *score);
+
+/* ---- KeyFrameDatabase (src/sg-slam/src/KeyFrameDatabase.cc) -------------------------------------------------------------------------------------------------------
+ * DetectRelocalizationCandidates (:199-309; caller Tracking::Relocalization, Tracking.cc:1467) and DetectLoopCandidates (:76-197; caller LoopClosing::DetectLoop,
+ * LoopClosing.cc:141) on the device.  The handle keeps every keyframe's BowVector (the forward file), its id, its add() sequence number, its best-covisibility list and
+ * its mRelocScore on the device.  The reference's inverted file is not built: a query intersects every keyframe's vector with the query's.  What the inverted file
+ * decides beyond the set of keyframes found is their order in lKFsSharingWords (the query's words ascending, within a word that word's list in add() order), and that is
+ * reproduced exactly: a keyframe's place is (its first common word, its add() sequence number) ascending; the candidates come back in that order.  Kept as written:
+ * minCommonWords = (int)(maxCommonWords * 0.8f), the gate words > minCommonWords, si = (float) of L1Scoring's double sum in ascending word order
+ * (ScoringObject.cpp:23-67), loop keeps si >= minScore, accScore a float sum in neighbour order, pBestKF moves on a strictly greater score, bestAccScore starts at
+ * minScore (loop) or 0 (relocalisation), retention accScore > 0.75f * bestAccScore, the first occurrence of a pBestKF stands, the early empty returns.
+ * Loop: a connected keyframe is never listed, so maxCommonWords is taken over the unconnected ones, and a neighbour counts only if it was listed and passed the word
+ * gate (:93-102, :159).  Relocalisation: a neighbour counts if it shares any word (:273) and adds its mRelocScore whether or not THIS query scored it (:276): a neighbour
+ * that shares a word but failed the gate contributes what an earlier query left in it.  mRelocScore is therefore persistent state of the handle, and query q of a batch
+ * sees what queries 0 .. q-1 left: a batch of Q equals Q single calls bit for bit.
+ * Defined where the reference is not:
+ *   - mRelocScore of a keyframe no query has scored is 0 (the reference's constructor leaves it uninitialised, KeyFrame.cc:35); add() gives a keyframe a fresh one.
+ *   - a query has no id: it behaves as one whose mnId is fresh and nonzero (mnRelocQuery(0) / mnLoopQuery(0) make id 0 special in the reference; nothing queries with it).
+ *   - weights must be finite, a BowVector's ids strictly ascending and below the vocabulary's size, keyframe ids >= 0: anything else is SGX_ERR_INVALID.
+ *   - an empty query or an empty database gives no candidates and a zero report.
+ *   - a query longer than max_query_words is SGX_ERR_INVALID (single entries) or, in a batch, status = SGX_ERR_INVALID in its report, no candidates, no state change.
+ *
+ * sgx_kfdb_create: nwords and the scoring type are copied from the vocabulary (the pointer is not kept); SGX_ERR_UNSUPPORTED unless the scoring is L1, as sgx_voc_score.
+ *   Capacity is fixed: max_keyframes keyframes, max_bow_entries BowVector entries over all of them, queries of at most max_query_words words (0 = 2048, 24 KB of LDS;
+ *   at most 4096), batches of at most max_queries.  The workspace is 37 bytes x max_queries x max_keyframes.
+ * sgx_kfdb_add / erase / clear (:40-73), set_covisibility: host pointers, synchronous; none may run while a batch of this handle is in flight.  add of an id that is
+ *   present, erase or set_covisibility of one that is absent: SGX_ERR_INVALID; a full database: SGX_ERR_NOMEM.  erase gives the keyframe's slot and entries back.  clear
+ *   also forgets every mRelocScore.  set_covisibility: what pKFi->GetBestCovisibilityKeyFrames(10) returns for that keyframe (:151, :265), in its order, n <= 10; the
+ *   caller refreshes it when its covisibility graph changes.  A neighbour id that is not in the database when a query runs contributes nothing.
+ * sgx_kfdb_slots: kf_ids[max_keyframes] = the keyframe id held by every slot (-1 = free), *n_slots = slots in use from 0: the order of words_dev / score_dev. */
+typedef struct sgx_kfdb sgx_kfdb;
+typedef struct sgx_kfdb_report {
+    int32_t n_sharing;                      /* lKFsSharingWords.size() */
+    int32_t max_common_words, min_common_words, n_scores;
+    int32_t n_score_and_match;              /* lScoreAndMatch.size() */
+    float best_acc_score, min_score_to_retain;
+    int32_t n_candidates;
+    int32_t status;                         /* SGX_OK, or SGX_ERR_INVALID for a query of a batch that is longer than max_query_words */
+} sgx_kfdb_report;                          /* fields past an early return stay 0 */
+enum { SGX_KFDB_RELOCALIZATION = 0, SGX_KFDB_LOOP_CLOSING = 1 };
+int sgx_kfdb_create(const sgx_voc *voc, int max_keyframes, int max_bow_entries, int max_query_words, int max_queries, sgx_kfdb **out);
+void sgx_kfdb_destroy(sgx_kfdb *db);
+int sgx_kfdb_size(const sgx_kfdb *db);                                                                        /* keyframes in the database */
+int sgx_kfdb_add(sgx_kfdb *db, int32_t kf_id, int nbow, const int32_t *ids, const double *weights);           /* ids / weights as sgx_voc_transform returns them */
+int sgx_kfdb_erase(sgx_kfdb *db, int32_t kf_id);
+int sgx_kfdb_clear(sgx_kfdb *db);
+int sgx_kfdb_set_covisibility(sgx_kfdb *db, int32_t kf_id, int n, const int32_t *neighbour_ids);
+int sgx_kfdb_slots(const sgx_kfdb *db, int32_t *kf_ids, int32_t *n_slots);
+/* One query from host memory, synchronous, a batch of one.  cand (capacity sgx_kfdb_size) = vpRelocCandidates / vpLoopCandidates as keyframe ids, *n_cand their number;
+ * report may be NULL.  connected_ids = pKF->GetConnectedKeyFrames() (:78), min_score = minScore. */
+int sgx_kfdb_detect_relocalization_candidates(sgx_kfdb *db, int nbow, const int32_t *ids, const double *weights, int32_t *cand, int32_t *n_cand, sgx_kfdb_report *report);
+int sgx_kfdb_detect_loop_candidates(sgx_kfdb *db, int nbow, const int32_t *ids, const double *weights, int n_connected, const int32_t *connected_ids, float min_score,
+                                    int32_t *cand, int32_t *n_cand, sgx_kfdb_report *report);
+/* LoopClosing::DetectLoop's reference score (LoopClosing.cc:126-138): starts from the float 1 and takes the float-cast L1 score of the query against each listed
+ * keyframe that is in the database; the caller lists only keyframes that are not isBad().  Host pointers, synchronous; leaves mRelocScore alone. */
+int sgx_kfdb_min_score(sgx_kfdb *db, int nbow, const int32_t *ids, const double *weights, int n, const int32_t *kf_ids, float *min_score);
+/* Q queries (mode: SGX_KFDB_RELOCALIZATION or SGX_KFDB_LOOP_CLOSING) as one launch sequence, asynchronous on `stream`; every pointer is device memory.  Query q = the
+ * first counts_dev[q] entries of row q of ids_dev / weights_dev (row pitch `pitch` elements, counts_dev[q] <= pitch): the layout sgx_voc_bow_batch_dev writes.  Loop only: the connected
+ * keyframes of query q are conn_ids_dev[conn_offsets_dev[q] .. conn_offsets_dev[q + 1]) (Q + 1 offsets; ids that are not in the database are ignored), its minScore
+ * min_score_dev[q]; all three may be NULL for relocalisation.  cand_dev = Q rows of max_keyframes ids, n_cand_dev / report_dev one per query.  words_dev / score_dev
+ * (optional, Q x max_keyframes, by slot: sgx_kfdb_slots) = what the reference leaves in the keyframes' public members after query q: mnRelocWords / mnLoopWords (0 for a
+ * keyframe the query did not touch; 1 for a connected keyframe of a loop query, whose counter :95 resets at every word) and mRelocScore, or for a loop query mLoopScore
+ * where this query wrote it and 0 elsewhere.  A handle serves one call at a time: calls of one handle must be ordered by their streams. */
+int sgx_kfdb_detect_batch_dev(sgx_kfdb *db, int mode, int Q, const int32_t *ids_dev, const double *weights_dev, int pitch, const int32_t *counts_dev,
+                              const int32_t *conn_offsets_dev, const int32_t *conn_ids_dev, const float *min_score_dev,
+                              int32_t *cand_dev, int32_t *n_cand_dev, sgx_kfdb_report *report_dev, int32_t *words_dev, float *score_dev, void *stream);
 
 /* The colour conversion at the top of Tracking::GrabImageRGBD (src/sg-slam/src/Tracking.cc:214-227): cvtColor(CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) on
  * 8-bit images, OpenCV's fixed point (R*4899 + G*9617 + B*1868 + 8192) >> 14.  blue_first = !mbRGB.  Pitches in bytes, multiples of 4; pointers 4-byte aligned. */

@@ -78,6 +78,15 @@ class InitReport(C.Structure):
                 ('parallax', C.c_float * 8), ('H21', C.c_float * 9), ('F21', C.c_float * 9)]
 
 
+class KfdbReport(C.Structure):
+    _fields_ = [('n_sharing', C.c_int32), ('max_common_words', C.c_int32), ('min_common_words', C.c_int32), ('n_scores', C.c_int32), ('n_score_and_match', C.c_int32),
+                ('best_acc_score', C.c_float), ('min_score_to_retain', C.c_float), ('n_candidates', C.c_int32), ('status', C.c_int32)]
+
+
+KFDB_REPORT_DTYPE = np.dtype([('n_sharing', 'i4'), ('max_common_words', 'i4'), ('min_common_words', 'i4'), ('n_scores', 'i4'), ('n_score_and_match', 'i4'),
+                              ('best_acc_score', 'f4'), ('min_score_to_retain', 'f4'), ('n_candidates', 'i4'), ('status', 'i4')])   # sgx_kfdb_report, 36 B
+
+
 class OrbConfig(C.Structure):
     _fields_ = [('nfeatures', C.c_int32), ('scale_factor', C.c_float), ('nlevels', C.c_int32),
                 ('ini_th_fast', C.c_int32), ('min_th_fast', C.c_int32), ('width', C.c_int32),
@@ -111,6 +120,8 @@ SYMBOLS = [
     'sgx_obj3d_create', 'sgx_obj3d_destroy', 'sgx_obj3d_detect_batch_dev', 'sgx_obj3d_detect', 'sgx_objdb_create', 'sgx_objdb_destroy', 'sgx_objdb_add', 'sgx_objdb_size',
     'sgx_objdb_get', 'sgx_initializer_create', 'sgx_initializer_initialize', 'sgx_initializer_destroy', 'sgx_init_batch_create', 'sgx_init_batch_run_dev',
     'sgx_init_batch_destroy', 'sgx_orb_detect_batch_dev', 'sgx_orb_describe_batch_dev', 'sgx_frame_compact_keys_src_batch_dev',
+    'sgx_voc_bow_batch_dev', 'sgx_kfdb_create', 'sgx_kfdb_destroy', 'sgx_kfdb_size', 'sgx_kfdb_add', 'sgx_kfdb_erase', 'sgx_kfdb_clear', 'sgx_kfdb_set_covisibility',
+    'sgx_kfdb_slots', 'sgx_kfdb_detect_relocalization_candidates', 'sgx_kfdb_detect_loop_candidates', 'sgx_kfdb_min_score', 'sgx_kfdb_detect_batch_dev',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -268,6 +279,19 @@ class SgxLib:
         d.sgx_voc_transform.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
         d.sgx_voc_transform_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
         d.sgx_voc_score.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+        d.sgx_voc_bow_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int] + [vp] * 6
+        d.sgx_kfdb_create.argtypes = [vp] + [C.c_int] * 4 + [vp]
+        d.sgx_kfdb_destroy.argtypes = [vp]; d.sgx_kfdb_destroy.restype = None
+        d.sgx_kfdb_size.argtypes = [vp]
+        d.sgx_kfdb_add.argtypes = [vp, C.c_int32, C.c_int, vp, vp]
+        d.sgx_kfdb_erase.argtypes = [vp, C.c_int32]
+        d.sgx_kfdb_clear.argtypes = [vp]
+        d.sgx_kfdb_set_covisibility.argtypes = [vp, C.c_int32, C.c_int, vp]
+        d.sgx_kfdb_slots.argtypes = [vp, vp, vp]
+        d.sgx_kfdb_detect_relocalization_candidates.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(KfdbReport)]
+        d.sgx_kfdb_detect_loop_candidates.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_float, vp, vp, C.POINTER(KfdbReport)]
+        d.sgx_kfdb_min_score.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
+        d.sgx_kfdb_detect_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int] + [vp] * 10
         d.sgx_match_search_by_bow_kf.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 4 + [C.c_float, C.c_int, vp, vp]
         d.sgx_match_fuse_search.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 6 + [C.POINTER(Camera), vp, vp, C.c_int, C.c_float, C.c_float, vp, vp, vp]
         d.sgx_hamming_matrix_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]

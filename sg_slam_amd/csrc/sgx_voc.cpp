@@ -1,5 +1,5 @@
 // sgx_voc.cpp — ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>) behind the C ABI: loaders, the per-feature descent on the device (sgx_voc_kernels.h),
-// BowVector / FeatureVector assembly and L1 scoring on the host.  Reference: src/sg-slam/Thirdparty/DBoW2/DBoW2/{TemplatedVocabulary.h, BowVector.cpp, FeatureVector.cpp,
+// BowVector / FeatureVector assembly and L1 scoring on the host, the BowVector assembly also on the device for frames that stay there (sgx_voc_bow_batch_dev).  Reference: src/sg-slam/Thirdparty/DBoW2/DBoW2/{TemplatedVocabulary.h, BowVector.cpp, FeatureVector.cpp,
 // ScoringObject.cpp, FORB.cpp}; callers Frame::ComputeBoW (Frame.cc:422-429), KeyFrame::ComputeBoW (KeyFrame.cc:60-69), System::System (System.cc:65-80).
 #include "sgx_voc_kernels.h"
 #include "sgx_stage.h"
@@ -117,6 +117,22 @@ static bool must_normalize(int scoring, bool *l2)
 {   // ScoringObject.h:73-92: every scoring class is declared with mustNormalize = true (KLScoring too: __SCORING_CLASS(KLScoring, true, L1)) except DotProductScoring
     *l2 = scoring == 1;
     return scoring != 5;
+}
+
+// the BowVector half of transform() for B frames whose per-feature arrays sgx_voc_transform_batch_dev left on the device: what the host code of sgx_voc_transform
+// below does with its std::map, one workgroup per frame
+extern "C" int sgx_voc_bow_batch_dev(sgx_voc *v, const int32_t *d_n, int batch, int cap, const int32_t *d_word_id, const double *d_weight,
+                                     int32_t *d_bow_ids, double *d_bow_weights, int32_t *d_nbow, void *stream)
+{
+    if (!v || batch < 0 || cap < 0 || (batch > 0 && (!d_n || !d_nbow)) || (batch > 0 && cap > 0 && (!d_word_id || !d_weight || !d_bow_ids || !d_bow_weights))) return SGX_ERR_INVALID;
+    if (cap > 8192) return SGX_ERR_UNSUPPORTED;                   // a frame's words and head flags sit in LDS: 5 bytes a feature
+    if (batch == 0) return SGX_OK;
+    bool l2; const bool must = must_normalize(v->scoring, &l2);
+    const int tf = v->weighting == 0 || v->weighting == 1;
+    SGX_LAUNCH_DYN(k_voc_bow, dim3((unsigned)batch), dim3(256), (size_t)cap * 5, (sgx_stream_t)stream, cap, tf, must ? 1 : 0, l2 ? 1 : 0, d_n, d_word_id, d_weight,
+                   d_bow_ids, d_bow_weights, d_nbow);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
 }
 
 extern "C" int sgx_voc_transform(sgx_voc *v, int n, const uint8_t *desc, int levelsup, int32_t *bow_ids, double *bow_weights, int32_t *nbow, int32_t *feat_node, int32_t *feat_word)

@@ -7,6 +7,7 @@
 // a frame's 1 000 features touch 60 k of them.  B frames per launch (grid.y), ragged counts.
 #pragma once
 #include "sgx_match_common.h"
+#include <limits.h>
 
 struct SgxVocDev {
     int L, nnodes;
@@ -47,5 +48,65 @@ SGX_KERNEL(256) k_voc_transform(SgxVocDev V, int levelsup, const uint8_t *desc, 
         const size_t o = (size_t)b * cap + i;
         word_id[o] = V.word_id[final_id]; weight[o] = w; feat_node[o] = w > 0 ? nid : -1;
     }
+    SGX_THREADS_END
+}
+
+// ---- the BowVector of one frame from its per-feature (word, weight) arrays: what the std::map of TemplatedVocabulary::transform ends up holding --------------------------
+// One workgroup per frame.  The words sit in LDS (stopped ones, !(w > 0), as INT_MAX: :1170); a feature is the head of its word if no earlier feature has the word; a
+// head's place in the map is the number of heads with a smaller word (pairwise, stable by construction), its weight the sum over its word's features in feature order
+// (addWeight, BowVector.cpp:33-45) or the first one's alone (addIfNotExist :49-57 for IDF / BINARY).  Then the /nd step of :1177-1183 or BowVector::normalize (:61-86) with
+// the norm summed by one lane in ascending word order.
+SGX_KERNEL(256) k_voc_bow(int cap, int tf, int must, int l2, const int *n_arr, const int *word_id, const double *weight, int *bow_ids, double *bow_w, int *bow_n)
+{
+    SGX_DYN_LDS(lds);
+    SGX_LDS int s_m;
+    SGX_LDS double s_norm;
+    const int b = (int)blockIdx.x;
+    int n = n_arr[b]; if (n > cap) n = cap; if (n < 0) n = 0;
+    int *wl = (int *)lds; unsigned char *head = lds + (size_t)cap * 4;
+    const size_t r0 = (size_t)b * cap;
+    SGX_THREADS_BEGIN(tid)
+    if (tid == 0) s_m = 0;
+    for (int i = tid; i < n; i += 256) wl[i] = weight[r0 + i] > 0 ? word_id[r0 + i] : INT_MAX;
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    for (int i = tid; i < n; i += 256) {
+        const int w = wl[i]; bool h = w != INT_MAX;
+        for (int j = 0; h && j < i; j++) h = wl[j] != w;
+        head[i] = h ? 1 : 0;
+    }
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    int heads = 0;
+    for (int i = tid; i < n; i += 256) {
+        if (!head[i]) continue;
+        const int w = wl[i]; int rank = 0; double v = weight[r0 + i];
+        for (int j = 0; j < n; j++) {
+            rank += head[j] && wl[j] < w;
+            if (tf && j > i && wl[j] == w) v += weight[r0 + j];
+        }
+        bow_ids[r0 + rank] = w; bow_w[r0 + rank] = v; heads++;
+    }
+    if (heads) sgx_atomic_add(&s_m, heads);
+    SGX_THREADS_END
+    SGX_SYNC();
+    const int m = s_m;
+    SGX_THREADS_BEGIN(tid)
+    if (tid == 0) {
+        bow_n[b] = m;
+        double norm = 0.0;
+        if (must) {
+            if (!l2) for (int i = 0; i < m; i++) norm += fabs(bow_w[r0 + i]);
+            else { for (int i = 0; i < m; i++) norm += bow_w[r0 + i] * bow_w[r0 + i]; norm = sqrt(norm); }
+        } else if (tf) norm = (double)m;
+        s_norm = norm;
+    }
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    const double norm = s_norm;
+    if (norm > 0.0) for (int i = tid; i < m; i += 256) bow_w[r0 + i] /= norm;
     SGX_THREADS_END
 }

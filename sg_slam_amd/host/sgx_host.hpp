@@ -418,6 +418,54 @@ private:
     sgx_voc *h_ = nullptr;
 };
 
+// KeyFrameDatabase (src/sg-slam/include/KeyFrameDatabase.h:41-68) over sgx_kfdb_*: the database on the device.  Where the reference passes KeyFrame* / Frame*, this mirror
+// takes what it reads of them: the keyframe's mnId and mBowVec, the query's mBowVec and, for a loop query, pKF->GetConnectedKeyFrames() as ids.  Candidates come back as
+// mnIds in the reference's order.  The covisibility the accumulation reads (pKFi->GetBestCovisibilityKeyFrames(10), KeyFrameDatabase.cc:151, :265) lives in the caller's
+// graph: setBestCovisibilityKeyFrames hands it over whenever the graph changes (KeyFrame::UpdateBestCovisibles, KeyFrame.cc:139-173).
+class KeyFrameDatabase {
+public:
+    typedef ORBVocabulary::BowVector BowVector;
+    KeyFrameDatabase(const ORBVocabulary &voc, int maxKeyFrames = 4096, int maxBowEntries = 0, int maxQueryWords = 0, int maxQueries = 64) : cap_(maxKeyFrames)
+    { check(sgx_kfdb_create(voc.handle(), maxKeyFrames, maxBowEntries > 0 ? maxBowEntries : 1024 * maxKeyFrames, maxQueryWords, maxQueries, &h_), "sgx_kfdb_create"); }
+    ~KeyFrameDatabase() { if (h_) sgx_kfdb_destroy(h_); }
+    KeyFrameDatabase(const KeyFrameDatabase &) = delete; KeyFrameDatabase &operator=(const KeyFrameDatabase &) = delete;
+    void add(int32_t mnId, const BowVector &mBowVec)                           // void add(KeyFrame *pKF) (:40-46)
+    { std::vector<int32_t> i; std::vector<double> w; split(mBowVec, i, w); check(sgx_kfdb_add(h_, mnId, (int)i.size(), i.data(), w.data()), "sgx_kfdb_add"); }
+    void erase(int32_t mnId) { check(sgx_kfdb_erase(h_, mnId), "sgx_kfdb_erase"); }      // void erase(KeyFrame *pKF) (:48-67)
+    void clear() { check(sgx_kfdb_clear(h_), "sgx_kfdb_clear"); }                          // (:69-73)
+    int size() const { return sgx_kfdb_size(h_); }
+    void setBestCovisibilityKeyFrames(int32_t mnId, const std::vector<int32_t> &vpNeighs)
+    { check(sgx_kfdb_set_covisibility(h_, mnId, (int)vpNeighs.size(), vpNeighs.data()), "sgx_kfdb_set_covisibility"); }
+    // std::vector<KeyFrame*> DetectLoopCandidates(KeyFrame *pKF, float minScore) (:76-197)
+    std::vector<int32_t> DetectLoopCandidates(const BowVector &mBowVec, const std::vector<int32_t> &spConnectedKeyFrames, float minScore, sgx_kfdb_report *report = nullptr)
+    {
+        std::vector<int32_t> i; std::vector<double> w; split(mBowVec, i, w);
+        std::vector<int32_t> cand((size_t)cap_); int32_t n = 0;
+        check(sgx_kfdb_detect_loop_candidates(h_, (int)i.size(), i.data(), w.data(), (int)spConnectedKeyFrames.size(), spConnectedKeyFrames.data(), minScore, cand.data(), &n, report),
+              "sgx_kfdb_detect_loop_candidates");
+        cand.resize((size_t)n); return cand;
+    }
+    // std::vector<KeyFrame*> DetectRelocalizationCandidates(Frame *F) (:199-309)
+    std::vector<int32_t> DetectRelocalizationCandidates(const BowVector &mBowVec, sgx_kfdb_report *report = nullptr)
+    {
+        std::vector<int32_t> i; std::vector<double> w; split(mBowVec, i, w);
+        std::vector<int32_t> cand((size_t)cap_); int32_t n = 0;
+        check(sgx_kfdb_detect_relocalization_candidates(h_, (int)i.size(), i.data(), w.data(), cand.data(), &n, report), "sgx_kfdb_detect_relocalization_candidates");
+        cand.resize((size_t)n); return cand;
+    }
+    // the minScore of LoopClosing::DetectLoop (LoopClosing.cc:126-138) over the covisible keyframes that are not isBad()
+    float MinScore(const BowVector &mBowVec, const std::vector<int32_t> &vpConnectedKeyFrames)
+    {
+        std::vector<int32_t> i; std::vector<double> w; split(mBowVec, i, w); float m = 1.0f;
+        check(sgx_kfdb_min_score(h_, (int)i.size(), i.data(), w.data(), (int)vpConnectedKeyFrames.size(), vpConnectedKeyFrames.data(), &m), "sgx_kfdb_min_score");
+        return m;
+    }
+    sgx_kfdb *handle() const { return h_; }
+private:
+    static void split(const BowVector &v, std::vector<int32_t> &i, std::vector<double> &w) { for (auto &e : v) { i.push_back(e.first); w.push_back(e.second); } }
+    sgx_kfdb *h_ = nullptr; int cap_;
+};
+
 // the two OpenCV calls of Frame::RmDynamicPointWithSemanticAndGeometry (Frame.cc:445, :469-472)
 class OpticalFlowLK {                                                // cv::calcOpticalFlowPyrLK(cur, prev, pts, nextPts, status, err, Size(21,21), 3, TermCriteria(ITER|EPS, 30, 0.01))
 public:

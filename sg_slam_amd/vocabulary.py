@@ -65,6 +65,12 @@ class ORBVocabulary:
         self.lib.check(self.lib.dll.sgx_voc_transform_batch_dev(self.h, _vp(d_desc), desc_pitch, _vp(d_n), batch, cap, int(levelsup), _vp(d_word), _vp(d_weight), _vp(d_feat_node),
                                                                  _vp(stream) if stream is not None else None), 'sgx_voc_transform_batch_dev')
 
+    def bow_batch_dev(self, d_n, batch, cap, d_word, d_weight, d_bow_ids, d_bow_weights, d_nbow, stream=None):
+        """the BowVectors of the B frames of transform_batch_dev on the device: rows of pitch cap in d_bow_ids / d_bow_weights and a count per row in d_nbow (the query
+        layout of KeyFrameDatabase.detect_batch_dev), bit for bit what transform() returns"""
+        self.lib.check(self.lib.dll.sgx_voc_bow_batch_dev(self.h, _vp(d_n), batch, cap, _vp(d_word), _vp(d_weight), _vp(d_bow_ids), _vp(d_bow_weights), _vp(d_nbow),
+                                                           _vp(stream) if stream is not None else None), 'sgx_voc_bow_batch_dev')
+
     def close(self):
         if self.h: self.lib.dll.sgx_voc_destroy(self.h); self.h = C.c_void_p()
 
