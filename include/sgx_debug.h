@@ -57,6 +57,11 @@ int sgx_det_debug_run_step(sgx_det *h, const uint8_t *d_img, int pitch, int batc
 /* run the octree-distribution kernel alone on packed candidates (x | y<<12 | score<<24, coordinates
  * relative to the (16,16) border origin) for `level`; returns the selected packed entries in list order */
 int sgx_orb_debug_run_octree(sgx_orb *h, int level, const uint32_t *packed, int n, uint32_t *out_sel, int cap, int *nsel);
+/* test tap: what sgx_orb_create decided (sgx_orb_plan.h), one section per call; the tables are read back from the handle's device copies.  section: 0 SgxOrbGeom,
+ * 1 SgxRun list, 2 SgxBlurTile list, 3 the levels' SgxXTab tables (levels 1.. in order), 4 the levels' SgxYTab tables as k_resize sees them, 5 SgxXGroup list,
+ * 6 the concatenated SgxYTab table of the fused pyramid, 7 SgxPyrRect list, 8 { SgxPyrTabs, pyr_tiles, pyr_lds, oct_maxlim, 0, packed umax (64 bits) }.
+ * *bytes = the section's size; dst == NULL asks for the size only, cap < *bytes is SGX_ERR_OVERFLOW.  Synchronises. */
+int sgx_orb_debug_read_plan(const sgx_orb *h, int section, void *dst, size_t cap, size_t *bytes);
 /* test / A-B tap: 1 = the NEXT sgx_tracker_create of this thread builds a tracker that orients and describes every raw keypoint before the dynamic mask (one-shot
  * extraction, descriptor rows moved by the erase step) instead of the survivors after it; 0 = the product order; -1 = default (SGX_TRK_DESCRIBE_EARLY set, or the product
  * order).  Bit-identical results either way. */
