@@ -767,6 +767,8 @@ typedef struct sgx_tracker_config {
     int32_t pipelined;                                                                      /* 1: own HIP streams; 0: everything on the caller's stream (tests) */
 } sgx_tracker_config;
 typedef struct sgx_tracker sgx_tracker;
+/* *out is NULL after any failed call.  The status is the one that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed fill, copy, stream or event;
+ * whatever had been acquired is released.  sgx_tracker_destroy waits for the tracker's work and releases everything the tracker acquired. */
 int sgx_tracker_create(const sgx_tracker_config *cfg, sgx_det *detector /* NULL: no Detector2D::detect; not owned */, sgx_tracker **out);
 void sgx_tracker_destroy(sgx_tracker *t);
 int sgx_tracker_keypoint_capacity(const sgx_tracker *t);
@@ -776,16 +778,22 @@ int sgx_tracker_set_initial_pose(sgx_tracker *t, const float *Tcw /* streams x 1
  * change (Frame.cc:656-660 / :707-713 skip everything).  Otherwise the grid / frustum bounds become those of sgx_frame_image_bounds (copied to *out_cam when it
  * is not NULL; with dist[0] == 0 *out_cam receives the unchanged camera), every frame's keypoints are undistorted beside ComputeStereoFromRGBD, and the
  * undistorted keypoints (mvKeysUn) feed the matchers, both PoseOptimization calls, the unprojection and the map points; ORB, LK, RANSAC, the dynamic mask
- * and the erase step keep the raw ones. */
+ * and the erase step keep the raw ones.  All or nothing: a call that fails leaves the tracker exactly as it was (no distortion, or the previous coefficients) and may be
+ * repeated. */
 int sgx_tracker_set_distortion(sgx_tracker *t, const float *dist, int ndist, sgx_camera *out_cam);
 /* one frame of every stream from device memory: d_gray streams x height x gray_pitch u8, d_depth streams x height x width raw u16, d_bgr (optional, detector
  * input) streams x height x bgr_pitch interleaved 3-channel u8.  Asynchronous — a step only ENQUEUES work.  The inputs of a step may be rewritten
  * (a) by work enqueued on `caller_stream` after the THIRD following sgx_tracker_step_dev call (that call orders caller_stream behind the step's readers), or
- * (b) from the host after sgx_tracker_wait_inputs(t, steps_back) or sgx_tracker_sync returned. */
+ * (b) from the host after sgx_tracker_wait_inputs(t, steps_back) or sgx_tracker_sync returned.
+ * A refused argument (SGX_ERR_INVALID) enqueues nothing and changes nothing.  A step that fails once enqueueing has begun POISONS the tracker: the frame was issued in part,
+ * so sgx_tracker_step_dev, sgx_tracker_step_host and sgx_tracker_pack_records_dev return that first status from then on without enqueueing anything;
+ * sgx_tracker_sync, _read, _wait_inputs and _destroy keep working. */
 int sgx_tracker_step_dev(sgx_tracker *t, const uint8_t *d_gray, int gray_pitch, const uint16_t *d_depth, const uint8_t *d_bgr, int bgr_pitch, void *caller_stream);
 /* host input (cv::imread's BGR image + the 16-bit depth map, rgbd_tum.cc:114-115): fill the pinned staging buffers of slot 0 / 1, then step; the tracker uploads
  * them on its own stream and converts to gray on the device (Tracking.cc:214-227; rgb_order = Camera.RGB).  The upload is asynchronous: before REFILLING a slot call
- * sgx_tracker_host_buffers(slot) again — it returns once the slot's pending upload has left the pinned buffers — or sgx_tracker_sync. */
+ * sgx_tracker_host_buffers(slot) again — it returns once the slot's pending upload has left the pinned buffers — or sgx_tracker_sync.
+ * The first sgx_tracker_host_buffers call sets the staging up, all or nothing: a call that fails has released what it acquired, sgx_tracker_step_host goes on refusing
+ * with SGX_ERR_INVALID, and the next call starts from scratch.  A failed sgx_tracker_step_host poisons the tracker as a failed sgx_tracker_step_dev does. */
 int sgx_tracker_host_buffers(sgx_tracker *t, int slot, uint8_t **bgr, int *bgr_pitch, uint16_t **depth);
 int sgx_tracker_step_host(sgx_tracker *t, int slot, int rgb_order);
 /* blocks the host until the device has read the input images of the step issued `steps_back` (0..2) calls ago */

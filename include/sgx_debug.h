@@ -69,6 +69,17 @@ int sgx_tracker_debug_set_describe_early(int on);
 /* test tap: person rectangles for the following steps of a tracker created WITHOUT a detector (host arrays: streams x max_boxes x (x, y, w, h), streams counts, streams
  * have-dynamic flags), in place of the empty set it would mask with.  Synchronises. */
 int sgx_tracker_debug_set_boxes(sgx_tracker *t, const float *boxes, const int32_t *nboxes, const int32_t *have_dynamic);
+/* test tap: reads and clears the tracker's log of everything that orders its streams since it was created, three int32 per entry: (op, stream, event).  op: 0 event
+ * record, 1 stream waits for event, 2 host waits for event, 3 host waits for stream, 4 device synchronisation, 5 mark — a fixed point of the step's schedule on `stream`,
+ * whose id stands in the event field: 1 before the detector forward, 2 ORB detect / extract, 3 the dynamic mask, 4 the stereo / undistort kernel, 5 the motion model,
+ * 6 unproject, 7 the two upload copies, 8 the gray conversion, 9 the pack kernel.  Streams and events are numbered in order of their first appearance in the tracker's
+ * log (caller streams included); the host is stream -1, and an entry without an event has -1 there.  *n = the number of int32 values; dst == NULL asks for the size only
+ * and keeps the log, cap < *n is SGX_ERR_OVERFLOW.  The emulator gives the numbers of the device build: its streams and events are distinct tokens there. */
+int sgx_tracker_debug_sync_trace(sgx_tracker *t, int32_t *dst, int cap, int *n);
+/* test tap, PER CALLING THREAD: the n-th acquisition or checked call made by the sgx_tracker_* entries of this thread from now on fails as if the runtime had refused it —
+ * a device or pinned allocation with SGX_ERR_NOMEM, a stream or event creation or a checked launch / copy / synchronisation with SGX_ERR_DEVICE.  n <= 0 turns it off.
+ * Returns the status that the previous arming delivered, SGX_OK when it never fired. */
+int sgx_tracker_debug_fail_after(int n);
 
 #ifdef __cplusplus
 }

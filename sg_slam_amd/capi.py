@@ -130,7 +130,7 @@ TAP_SYMBOLS = [
     'sgx_det_debug_detection_output', 'sgx_det_debug_continued', 'sgx_debug_flow_affine_batch_dev', 'sgx_det_debug_set_fusion', 'sgx_det_debug_set_legacy_kernels',
     'sgx_det_debug_set_block_fusion', 'sgx_det_debug_set_irb', 'sgx_det_debug_set_gemm', 'sgx_det_debug_time_ops', 'sgx_det_debug_run_step', 'sgx_flow_debug_read_level',
     'sgx_flow_debug_level_size', 'sgx_flow_debug_read_slot', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas', 'sgx_obj3d_debug_read',
-    'sgx_tracker_debug_set_describe_early', 'sgx_tracker_debug_set_boxes',
+    'sgx_tracker_debug_set_describe_early', 'sgx_tracker_debug_set_boxes', 'sgx_tracker_debug_sync_trace', 'sgx_tracker_debug_fail_after',
 ]
 
 
@@ -328,6 +328,10 @@ class SgxLib:
             d.sgx_flow_debug_read_slot.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int32)]
             d.sgx_tracker_debug_set_describe_early.argtypes = [C.c_int]
             d.sgx_tracker_debug_set_boxes.argtypes = [vp, vp, vp, vp]
+            if hasattr(d, 'sgx_tracker_debug_sync_trace'):      # as sgx_orb_debug_read_plan: a tap library built before these two existed still loads
+                d.sgx_tracker_debug_sync_trace.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
+            if hasattr(d, 'sgx_tracker_debug_fail_after'):
+                d.sgx_tracker_debug_fail_after.argtypes = [C.c_int]
 
     def tap(self, name):
         """a test / tuning tap entry (include/sgx_debug.h); the product library has none"""
