@@ -275,7 +275,8 @@ int sgx_mappoint_distinctive_descriptors(int n, const int32_t *obs_start, const 
  * values (3 x n_iterations; only the first 3 x *iterations_run are consumed — a caller sharing the global stream passes one iteration per call), or NULL: the solver then
  * uses its own replica of glibc's rand() seeded with rand_seed at creation (srand(rand_seed)).
  * Outputs: *found = a model was returned (T12 = 4x4 row-major mBestT12, inliers[n] over the n pairs — the caller maps them through mvnIndices1 — *n_inliers);
- * *no_more = bNoMore.  get_estimate = GetEstimatedRotation / Translation / Scale of the best model so far, and the effective mRansacMaxIts. */
+ * *no_more = bNoMore.  get_estimate = GetEstimatedRotation / Translation / Scale of the best model so far, and the effective mRansacMaxIts.
+ * A failed create clears *out and returns the status that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed copy. */
 typedef struct sgx_sim3_solver sgx_sim3_solver;
 int sgx_sim3_solver_create(int n, const float *x3dc1, const float *x3dc2, const float *max_err1, const float *max_err2, const float *K1, const float *K2, int fix_scale,
                            unsigned rand_seed, sgx_sim3_solver **out);
@@ -300,7 +301,8 @@ void sgx_sim3_solver_destroy(sgx_sim3_solver *s);
  * values, 4 x the call's hypothesis count (max(n_iterations, max_iterations - iterations), get_estimate), of which the first 4 x *iterations_run are consumed; or NULL:
  * the solver's replica of glibc's rand(), srand(rand_seed) at creation, draws of hypotheses that did not run are handed back.
  * Outputs: *found = a model was returned (Tcw 4 x 4 row-major float, inliers[n] over the n correspondences, *n_inliers); *no_more = bNoMore.  get_estimate: mBestTcw,
- * the effective mRansacMaxIts and mRansacMinInliers, mnIterations and mnBestInliers.  Synchronous, host pointers. */
+ * the effective mRansacMaxIts and mRansacMinInliers, mnIterations and mnBestInliers.  Synchronous, host pointers.
+ * A failed create clears *out and returns the status that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed copy. */
 typedef struct sgx_pnp_solver sgx_pnp_solver;
 int sgx_pnp_solver_create(int n, const float *p2d, const float *sigma2, const float *p3dw, const float *cam4, unsigned rand_seed, sgx_pnp_solver **out);
 int sgx_pnp_solver_set_ransac_parameters(sgx_pnp_solver *s, double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2);
@@ -313,7 +315,9 @@ void sgx_pnp_solver_destroy(sgx_pnp_solver *s);
  * cam (host, B x 4) = fx, fy, cx, cy; ransac (host, B x 6) = SetRansacParameters(probability, minInliers, maxIterations, minSet, epsilon, th2) of each solver;
  * rand_seeds (host, B) seeds each solver's rand() replica (NULL: 0).  iterate_dev = iterate(n_iterations) of every solver on `stream`: rand_draws_dev (device, optional)
  * = solver b's raw rand() values at b * draw_stride, 4 per hypothesis as above; result_dev (B x 4 int32) = found, bNoMore, nInliers, iterations run; tcw_dev (B x 16);
- * inliers_dev (offsets[B] bytes).  Asynchronous on `stream`. */
+ * inliers_dev (offsets[B] bytes).  Asynchronous on `stream`.
+ * A failed create clears *out and returns the status that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed copy.  A failed set_dev leaves the batch not set: iterate_dev answers SGX_ERR_INVALID until a
+ * set_dev succeeds. */
 typedef struct sgx_pnp_batch sgx_pnp_batch;
 int sgx_pnp_batch_create(int max_solvers, int max_correspondences, sgx_pnp_batch **out);
 int sgx_pnp_batch_set_dev(sgx_pnp_batch *t, int B, const int32_t *offsets, const float *p2d_dev, const float *sigma2_dev, const float *p3dw_dev, const float *cam,
@@ -339,7 +343,9 @@ void sgx_pnp_batch_destroy(sgx_pnp_batch *t);
  * Defined where the reference is undefined: fewer than 8 matches -> *ok = 0 and no random number is consumed; no hypothesis of the chosen model scored above 0 (the
  * reference decomposes an empty matrix) -> *ok = 0; a hypothesis whose score is NaN never wins; matches12[i] >= n2 counts as unmatched.
  * Random numbers: the reference draws 8 x iterations values from the process-global rand() after SeedRandOnce(0).  rand_draws = those raw rand() values, or NULL: the
- * object's replica of glibc's rand(), srand(rand_seed) at creation, continuing across calls (seed 0 = a process's first Initialize).  Synchronous, host pointers. */
+ * object's replica of glibc's rand(), srand(rand_seed) at creation, continuing across calls (seed 0 = a process's first Initialize).  Synchronous, host pointers.
+ * A failed create clears *out and returns the status that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed copy.  An initialize that fails while it makes room for a larger frame 2 leaves the
+ * initializer as it was: usable at its old size, the replica unmoved. */
 typedef struct sgx_initializer sgx_initializer;
 typedef struct sgx_init_report {
     float SH, SF, RH; int32_t model /* 0 H, 1 F */, n_matches, n_inliers_h, n_inliers_f, n_hyp /* 8, 4 or 0 */, best_hyp;
@@ -354,7 +360,7 @@ void sgx_initializer_destroy(sgx_initializer *s);
  * keys in keys1_dev / keys2_dev; matches12_dev, p3d_dev, triangulated_dev and inliers_dev follow offsets1; cam (host, B x 4), sigma (host, B); rand_seeds (host, B)
  * re-seeds the pairs' rand() replicas before this run (NULL: they continue; all start as srand(0)); rand_draws_dev (device, optional) = pair b's 8 x iterations raw
  * rand() values at b * draw_stride.  Outputs on the device: R21_dev (B x 9), t21_dev (B x 3), ok_dev (B), report_dev (B; its parallax[] stays 0: the host
- * evaluates acos).  Asynchronous on `stream`. */
+ * evaluates acos).  Asynchronous on `stream`. A failed create clears *out and returns the status that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed copy. */
 typedef struct sgx_init_batch sgx_init_batch;
 int sgx_init_batch_create(int max_pairs, int max_keys, int max_matches, int iterations, sgx_init_batch **out);
 int sgx_init_batch_run_dev(sgx_init_batch *t, int B, const int32_t *offsets1, const sgx_keypoint *keys1_dev, const int32_t *matches12_dev, const int32_t *offsets2,
@@ -398,7 +404,8 @@ typedef struct sgx_obj3d sgx_obj3d;
 /* width x height images, at most max_images images and max_jobs jobs per batch, at most max_crop_points cells per crop; 0 = the largest crop there is:
  * Detector2D only clamps its boxes to the image (Detector2D.cc:63-71), so a box can be the whole image and its crop the central 60 % of it, 384 x 288 = 110 592 cells
  * of a 640 x 480 image.  The workspace is 32 bytes per cell and job, plus 64 bytes per job for every max_crop_points / max(cluster_min_size, 1) cells: the surviving
- * clusters are ranked pairwise by one workgroup, so a cluster_min_size of a few points on a large crop costs (cells / min_size)^2 reads there. */
+ * clusters are ranked pairwise by one workgroup, so a cluster_min_size of a few points on a large crop costs (cells / min_size)^2 reads there.
+ * A failed create clears *out and returns the status that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed copy. */
 int sgx_obj3d_create(int width, int height, int max_images, int max_jobs, int max_crop_points, const sgx_obj3d_params *params, sgx_obj3d **out);
 void sgx_obj3d_destroy(sgx_obj3d *h);
 /* n_jobs jobs over n_images depth images (device, float metres as mImDep, n_images x height x pitch floats), cam4 = fx, fy, cx, cy (host), twc_dev = n_images x 16
@@ -427,7 +434,8 @@ int sgx_objdb_get(const sgx_objdb *db, int index, sgx_semantic_object *out);  /*
  * sgx_voc_transform / sgx_voc_score and device work in sgx_voc_bow_batch_dev and the sgx_kfdb_* entries.
  *
  * sgx_voc_load: loadFromTextFile (:1351-1438) for a path ending in ".txt", loadFromBinaryFile (:1467-1510) otherwise — System::System's rule (System.cc:69-73).
- * sgx_voc_create: the same tree from flat arrays: node 0 is the root, parent[i] < i for i >= 1, desc32 = nnodes x 32 bytes, is_leaf[i] gives node i the next word id. */
+ * sgx_voc_create: the same tree from flat arrays: node 0 is the root, parent[i] < i for i >= 1, desc32 = nnodes x 32 bytes, is_leaf[i] gives node i the next word id.
+ * A failed create clears *out and returns the status that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed copy. */
 typedef struct sgx_voc sgx_voc;
 int sgx_voc_load(const char *path, sgx_voc **out);
 int sgx_voc_create(int k, int L, int scoring, int weighting, int nnodes, const int32_t *parent, const uint8_t *desc32, const double *weight, const uint8_t *is_leaf, sgx_voc **out);
@@ -476,6 +484,7 @@ int sgx_voc_score(const sgx_voc *v, int n1, const int32_t *ids1, const double *w
  * sgx_kfdb_create: nwords and the scoring type are copied from the vocabulary (the pointer is not kept); SGX_ERR_UNSUPPORTED unless the scoring is L1, as sgx_voc_score.
  *   Capacity is fixed: max_keyframes keyframes, max_bow_entries BowVector entries over all of them, queries of at most max_query_words words (0 = 2048, 24 KB of LDS;
  *   at most 4096), batches of at most max_queries.  The workspace is 37 bytes x max_queries x max_keyframes.
+ *   A failed create clears *out and returns the status that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed copy.
  * sgx_kfdb_add / erase / clear (:40-73), set_covisibility: host pointers, synchronous; none may run while a batch of this handle is in flight.  add of an id that is
  *   present, erase or set_covisibility of one that is absent: SGX_ERR_INVALID; a full database: SGX_ERR_NOMEM.  erase gives the keyframe's slot and entries back.  clear
  *   also forgets every mRelocScore.  set_covisibility: what pKFi->GetBestCovisibilityKeyFrames(10) returns for that keyframe (:151, :265), in its order, n <= 10; the

@@ -80,6 +80,11 @@ int sgx_tracker_debug_sync_trace(sgx_tracker *t, int32_t *dst, int cap, int *n);
  * a device or pinned allocation with SGX_ERR_NOMEM, a stream or event creation or a checked launch / copy / synchronisation with SGX_ERR_DEVICE.  n <= 0 turns it off.
  * Returns the status that the previous arming delivered, SGX_OK when it never fired. */
 int sgx_tracker_debug_fail_after(int n);
+/* test tap, PER CALLING THREAD: the same for the handles whose device buffers one owner holds (sg_slam_amd/csrc/sgx_devmem.h: the ORB extractor, the detector, the
+ * vocabulary, the keyframe database, PnP, Initializer, Sim3Solver and Detector3D handles).  The n-th acquisition from now on fails as if the runtime had refused it — an
+ * allocation with SGX_ERR_NOMEM, the copy of a table or input uploaded at creation with SGX_ERR_DEVICE.  n <= 0 turns it off.  Returns the status that the previous
+ * arming delivered, SGX_OK when it never fired. */
+int sgx_debug_devmem_fail_after(int n);
 
 #ifdef __cplusplus
 }

@@ -131,6 +131,7 @@ TAP_SYMBOLS = [
     'sgx_det_debug_set_block_fusion', 'sgx_det_debug_set_irb', 'sgx_det_debug_set_gemm', 'sgx_det_debug_time_ops', 'sgx_det_debug_run_step', 'sgx_flow_debug_read_level',
     'sgx_flow_debug_level_size', 'sgx_flow_debug_read_slot', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas', 'sgx_obj3d_debug_read',
     'sgx_tracker_debug_set_describe_early', 'sgx_tracker_debug_set_boxes', 'sgx_tracker_debug_sync_trace', 'sgx_tracker_debug_fail_after',
+    'sgx_debug_devmem_fail_after',
 ]
 
 
@@ -332,6 +333,8 @@ class SgxLib:
                 d.sgx_tracker_debug_sync_trace.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
             if hasattr(d, 'sgx_tracker_debug_fail_after'):
                 d.sgx_tracker_debug_fail_after.argtypes = [C.c_int]
+            if hasattr(d, 'sgx_debug_devmem_fail_after'):
+                d.sgx_debug_devmem_fail_after.argtypes = [C.c_int]
 
     def tap(self, name):
         """a test / tuning tap entry (include/sgx_debug.h); the product library has none"""

@@ -7,6 +7,7 @@
 #include "sgx_det_bf16.h"
 #include "sgx_det_hrb.h"
 #include "sgx_prof.h"
+#include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #ifdef SGX_DEBUG_TAPS
 #include "../../include/sgx_debug.h"      // test / tuning taps: compiled into tests/taps/libsgx_taps.so and the emulator only
@@ -90,7 +91,7 @@ struct sgx_det {
     std::map<std::string, int> blob_id;
     std::vector<Blob> blobs;
     std::vector<Op> ops;
-    std::vector<void *> dev;
+    SgxDevMem mem;                      // every device allocation of the handle; destroyed after the graphs below
     std::vector<float> priors;          // 2 x (num_priors*4): boxes, variances (PriorBox is input-independent: host constant)
     int num_priors = 0, num_class = 21, nms_top_k = 300, keep_top_k = 100; float nms_th = 0.45f, conf_th = 0.01f, dvar[4] = {0.1f, 0.1f, 0.2f, 0.2f};
     int loc_blob = -1, conf_blob = -1;
@@ -111,12 +112,7 @@ struct sgx_det {
         for (hipEvent_t e : fork_events) (void)hipEventDestroy(e);
         for (hipStream_t q : fork_streams) (void)hipStreamDestroy(q);
 #endif
-        for (void *p : dev) (void)hipFree(p);
     }
-    template <class Tp> int alloc(Tp **p, size_t n) { void *q = nullptr; if (hipMalloc(&q, (n ? n : 1) * sizeof(Tp)) != hipSuccess) return SGX_ERR_NOMEM; dev.push_back(q); *p = (Tp *)q; return SGX_OK; }
-    // a host array as a device allocation of the handle
-    template <class Tp, class Pp> int upload(Pp *dst, const Tp *src, size_t n) { Tp *d = nullptr; if (alloc(&d, n)) return SGX_ERR_NOMEM; *dst = (Pp)d; return hipMemcpy(d, src, n * sizeof(Tp), hipMemcpyHostToDevice) == hipSuccess ? SGX_OK : SGX_ERR_DEVICE; }
-    template <class Tp, class Pp> int upload(Pp *dst, const std::vector<Tp> &v) { return upload(dst, v.data(), v.size()); }
     int resolve(int id) const { while (blobs[id].alias >= 0) id = blobs[id].alias; return id; }
     bool is_output(int id) const { return id == loc_blob || id == conf_blob; }
 };
@@ -250,8 +246,8 @@ int upload_se_interleaved(sgx_det *h, const Op &d, const Op &e, const float **wq
     std::vector<float> p1((size_t)Cq * Co), p2((size_t)Co * Cq);
     for (int j = 0; j < Cq; j++) for (int k = 0; k < Co; k++) p1[((size_t)(j >> 1) * Co + k) * 2 + (j & 1)] = d.hw[(size_t)j * Co + k];
     for (int co = 0; co < Co; co++) for (int j = 0; j < Cq; j++) p2[((size_t)j * (Co / 2) + (co >> 1)) * 2 + (co & 1)] = e.hw[(size_t)co * Cq + j];
-    const int rc = h->upload(wq1p, p1);
-    return rc ? rc : h->upload(wq2p, p2);
+    const int rc = h->mem.upload(wq1p, p1);
+    return rc ? rc : h->mem.upload(wq2p, p2);
 }
 
 int Loader::conv(const Layer &L, int in0, const Blob &A)
@@ -265,8 +261,8 @@ int Loader::conv(const Layer &L, int in0, const Blob &A)
     op.hw.resize(wsize); memcpy(op.hw.data(), bp + bo, (size_t)wsize * 4); bo += (size_t)wsize * 4;
     op.hb.assign(outc, 0.f);
     if (L.geti(5, 0)) { memcpy(op.hb.data(), bp + bo, (size_t)outc * 4); bo += (size_t)outc * 4; }
-    int rc = h->upload(&op.wt, op.hw); if (rc) return rc;
-    if ((rc = h->upload(&op.bias, op.hb))) return rc;
+    int rc = h->mem.upload(&op.wt, op.hw); if (rc) return rc;
+    if ((rc = h->mem.upload(&op.bias, op.hb))) return rc;
     // host-transposed copies for the tuned kernels: pointwise [k][oc]; stem [(c,i,j)][16]
     const bool pw = (k == 1 && group == 1 && stride == 1 && pad == 0), stem = (group == 1 && k > 1 && outc <= 16);
     if (pw || stem) {
@@ -274,15 +270,17 @@ int Loader::conv(const Layer &L, int in0, const Blob &A)
         op.ldw = ldo;
         std::vector<float> wT((size_t)(pw ? ((kk + 31) / 32) * 32 : kk) * ldo, 0.f);
         for (int o = 0; o < outc; o++) for (int q = 0; q < kk; q++) wT[(size_t)q * ldo + o] = op.hw[(size_t)o * kk + q];
-        if ((rc = h->upload(&op.wtT, wT))) return rc;
+        if ((rc = h->mem.upload(&op.wtT, wT))) return rc;
         if (pw && h->sw.gemm == 1) {                           // bf16x3 plan: the same weights as three bf16 terms in the matrix-core operand layout
             std::vector<unsigned short> ws((size_t)((kk + 15) / 16) * 6 * ldo * 8);
             sgx_split_weights_bf16x3(op.hw.data(), outc, kk, ldo, ws.data());
-            if ((rc = h->upload(&op.wS, ws))) return rc;
+            unsigned short *dS = nullptr;
+            if ((rc = h->mem.upload(&dS, ws))) return rc;
+            op.wS = dS;
         }
     }
 #ifdef SGX_DEBUG_TAPS      // k_conv_dw3 (round-6 experiment, slower than k_conv_dw2) exists in the tap build only
-    if (group == inc && group != 1 && (outc & 1) == 0 && inc == outc && (rc = h->upload(&op.wtP, pair_interleave(op.hw, outc, k * k)))) return rc;
+    if (group == inc && group != 1 && (outc & 1) == 0 && inc == outc && (rc = h->mem.upload(&op.wtP, pair_interleave(op.hw, outc, k * k)))) return rc;
 #endif
     op.inc = inc; op.outc = outc; op.H = A.h; op.W = A.w; op.k = k; op.stride = stride; op.pad = pad; op.depthwise = group != 1;
     op.Ho = (A.h + 2 * pad - k) / stride + 1; op.Wo = (A.w + 2 * pad - k) / stride + 1;
@@ -321,7 +319,7 @@ int Loader::run()
 {
     const int B = h->max_batch, T = h->T;
     for (const Layer &L : h->layers) {
-        if (L.type == "Input") { Blob &b = h->blobs[blob(L.outs[0])]; b.c = 3; b.h = T; b.w = T; b.n = (size_t)3 * T * T; if (h->alloc(&b.d, b.n * B)) return SGX_ERR_NOMEM; continue; }
+        if (L.type == "Input") { Blob &b = h->blobs[blob(L.outs[0])]; b.c = 3; b.h = T; b.w = T; b.n = (size_t)3 * T * T; if (h->mem.alloc(&b.d, b.n * B)) return SGX_ERR_NOMEM; continue; }
         if (L.type == "MemoryData") {
             const int n = L.geti(0, 0) * std::max(L.geti(1, 1), 1) * std::max(L.geti(2, 1), 1);
             if (n != 1 || bo + 4 > bin_bytes) return SGX_ERR_UNSUPPORTED;
@@ -533,7 +531,7 @@ int Planner::fuse_blocks()
             SgxFusedBlk fb = make_fused_blk(a, bq, c, ca, cb);
             fb.v2 = v2; fb.w2t = c.wtT; fb.ldw2 = c.ldw;
             sgx_fb2_tile(v2, &fb.TOH, &fb.TOW);
-            const int rc = h->upload(&fb.wd2, pair_interleave(bq.hw, fb.Cmid, bq.k * bq.k)); if (rc) return rc;
+            const int rc = h->mem.upload(&fb.wd2, pair_interleave(bq.hw, fb.Cmid, bq.k * bq.k)); if (rc) return rc;
             // round 6, bf16x3 plan: the same block with both pointwise convolutions on the bf16 matrix pipes (k_hrb, sgx_det_hrb.h); SGX_DET_HRB=0 (tap) keeps k_fused_block2
             if (sw.hrb && h->sw.gemm == 1 && a.wS && c.wS && sgx_hrb_variant(fb.Cin, fb.Cmid, fb.Cout, fb.K, fb.stride, 0, cc.t1 >= 0, fb.lo1, fb.lo2, sw.hrb_pick, &fb.TOH, &fb.TOW, &fb.hrb_occ)) {
                 fb.hrb = 1; fb.w1S = a.wS; fb.ld1S = a.ldw; fb.w2S = c.wS; fb.ld2S = c.ldw;
@@ -635,7 +633,7 @@ int Planner::fuse_block2_se(const IrbMatch &m, bool *taken)
     if (v2) sgx_fb2_tile(v2, &fb.TOH, &fb.TOW);
     fb.Cq = d.outc; fb.qlo = m.cd.lo; fb.qhi = m.cd.hi; fb.gc1 = m.ce.c1; fb.glo = m.ce.lo; fb.ghi = m.ce.hi; fb.gc2 = m.ce.c2;
     fb.wq1 = d.wt; fb.bq1 = d.bias; fb.wq2 = e.wt; fb.bq2 = e.bias;
-    int rc = h->upload(&fb.wd2, pair_interleave(bq.hw, fb.Cmid, bq.k * bq.k)); if (rc) return rc;
+    int rc = h->mem.upload(&fb.wd2, pair_interleave(bq.hw, fb.Cmid, bq.k * bq.k)); if (rc) return rc;
     if ((rc = upload_se_interleaved(h, d, e, &fb.wq1p, &fb.wq2p))) return rc;
     if (hrb_ok) {
         fb.hrb = 1; fb.TOH = h_toh; fb.TOW = h_tow; fb.hrb_occ = h_occ;
@@ -741,7 +739,7 @@ int Planner::fuse_irb()
             if (!ok3 && a3 && h->sw.gemm == 1 && ai >= 0 && ops[ai].wS) { ib.gemm = 2; ib.w1S = ops[ai].wS; }
             if (ib.gemm == 2 && a3 >= 2 && (a3 == 2 || bq.outc == a3)) {      // experiment: pre-split input (SGX_DET_IRB_A3=2: every block; = Cexp: that block only)
                 ib.ldS = ((bq.H * bq.W + 31) / 32) * 32;
-                unsigned *sh = nullptr; if (h->alloc(&sh, (size_t)B * ((ops[ai].inc + 15) / 16) * 6 * ib.ldS * 4)) return SGX_ERR_NOMEM;      // 16 bytes per entry
+                unsigned *sh = nullptr; if (h->mem.alloc(&sh, (size_t)B * ((ops[ai].inc + 15) / 16) * 6 * ib.ldS * 4)) return SGX_ERR_NOMEM;      // 16 bytes per entry
                 ib.inS = sh;
             } else if (ib.gemm == 2 && a3 > 2 && bq.outc != a3) ib.gemm = 0;
             if (ok3) { ib.w2S = c.wS; ib.w1S = ai >= 0 ? ops[ai].wS : nullptr; ib.wq1S = di >= 0 ? ops[di].wS : nullptr; ib.wq2S = di >= 0 ? ops[ei].wS : nullptr; }
@@ -750,7 +748,7 @@ int Planner::fuse_irb()
             const int kk = bq.k * bq.k, kkp = SGX_IRB_KKP(bq.k), rows = ((bq.outc + 31) / 32) * 32;
             std::vector<float> wp((size_t)rows * kkp, 0.f);
             for (int ch = 0; ch < bq.outc; ch++) { for (int t = 0; t < kk; t++) wp[(size_t)ch * kkp + t] = bq.hw[(size_t)ch * kk + t]; wp[(size_t)ch * kkp + kk] = bq.hb[ch]; }
-            if ((rc = h->upload(&ib.wdp, wp))) return rc;
+            if ((rc = h->mem.upload(&ib.wdp, wp))) return rc;
         }
         Op f; f.kind = OP_IRB; f.in0 = ai >= 0 ? ops[ai].in0 : bq.in0; f.out = m.out_blob; f.irb = ib; f.res_blob = m.res_blob;
         f.name = (ai >= 0 ? ops[ai].name + "+" : std::string()) + bq.name + "+" + c.name + (di >= 0 ? "+" + ops[di].name + "+" + ops[ei].name : std::string());
@@ -879,16 +877,15 @@ static int finalise(sgx_det *h)
     const int B = h->max_batch, T = h->T;
     for (Op &o : h->ops) {
         std::vector<float>().swap(o.hw); std::vector<float>().swap(o.hb);
-        Blob &ob = h->blobs[o.out]; if (!ob.d && ob.n) { if (h->alloc(&ob.d, ob.n * B)) return SGX_ERR_NOMEM; }
-        if (o.irb_out2_blob >= 0) { Blob &o2 = h->blobs[o.irb_out2_blob]; if (!o2.d && o2.n) { if (h->alloc(&o2.d, o2.n * B)) return SGX_ERR_NOMEM; } }
+        Blob &ob = h->blobs[o.out]; if (!ob.d && ob.n) { if (h->mem.alloc(&ob.d, ob.n * B)) return SGX_ERR_NOMEM; }
+        if (o.irb_out2_blob >= 0) { Blob &o2 = h->blobs[o.irb_out2_blob]; if (!o2.d && o2.n) { if (h->mem.alloc(&o2.d, o2.n * B)) return SGX_ERR_NOMEM; } }
     }
     {   // pre-processing fused into the stem (k_stem_pre) when the stem is the only reader of the network input and takes the k_conv_stem2 path (see run_op)
         const int in_id = h->blob_id.at("input");
         int readers = 0; for (const Op &o : h->ops) readers += (o.in0 == in_id) + (o.in1 == in_id);
         if (h->sw.prefuse && h->sw.fuse && !h->sw.legacy && !h->ops.empty() && readers == 1 && stem2_ok(h, h->ops[0]) && h->ops[0].in0 == in_id) {
             Blob &ib = h->blobs[in_id];
-            auto it = std::find(h->dev.begin(), h->dev.end(), (void *)ib.d);
-            if (it != h->dev.end()) { (void)hipFree(ib.d); h->dev.erase(it); ib.d = nullptr; h->pre_fused = 1; }
+            if (ib.d) { h->mem.release(ib.d); ib.d = nullptr; h->pre_fused = 1; }
         }
     }
     // every block kernel the plan launches exists and may use its LDS: nothing is left to find out inside a forward (or inside its stream capture)
@@ -896,9 +893,9 @@ static int finalise(sgx_det *h)
     if ((size_t)h->num_priors * 4 != h->blobs[h->loc_blob].n || (size_t)h->num_priors * h->num_class != h->blobs[h->conf_blob].n) return SGX_ERR_INVALID;
     if (h->num_priors > SGX_DO_SORT || h->nms_top_k > SGX_DO_TOPK || (h->num_class - 1) * h->nms_top_k > SGX_DO_MERGE || h->num_class - 1 > 63 || h->num_class < 2 ||
         h->keep_top_k > SGX_DET_MAX) return SGX_ERR_UNSUPPORTED;
-    int rc = h->upload(&h->d_priors, h->priors.data(), (size_t)h->num_priors * 4); if (rc) return rc;
-    if (h->alloc(&h->d_cls_rows, (size_t)B * (h->num_class - 1) * SGX_DO_TOPK * 6) || h->alloc(&h->d_cls_count, (size_t)B * (h->num_class - 1)) || h->alloc(&h->d_results, (size_t)B)) return SGX_ERR_NOMEM;
-    if (h->alloc(&h->d_cls_ncut, (size_t)B * (h->num_class - 1)) || h->alloc(&h->d_cls_next, (size_t)B * (h->num_class - 1)) || h->alloc(&h->d_cls_cont, (size_t)B * (h->num_class - 1)) || h->alloc(&h->d_sstar, (size_t)B)) return SGX_ERR_NOMEM;
+    int rc = h->mem.upload(&h->d_priors, h->priors.data(), (size_t)h->num_priors * 4); if (rc) return rc;
+    if (h->mem.alloc(&h->d_cls_rows, (size_t)B * (h->num_class - 1) * SGX_DO_TOPK * 6) || h->mem.alloc(&h->d_cls_count, (size_t)B * (h->num_class - 1)) || h->mem.alloc(&h->d_results, (size_t)B)) return SGX_ERR_NOMEM;
+    if (h->mem.alloc(&h->d_cls_ncut, (size_t)B * (h->num_class - 1)) || h->mem.alloc(&h->d_cls_next, (size_t)B * (h->num_class - 1)) || h->mem.alloc(&h->d_cls_cont, (size_t)B * (h->num_class - 1)) || h->mem.alloc(&h->d_sstar, (size_t)B)) return SGX_ERR_NOMEM;
 #ifndef SGX_EMU      // A/B switch of the XCD-aware work order (sgx_xcd_order); on by default
     SGX_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(sgx_det_xcd_order), &h->sw.xcd, sizeof(int)));
 #else
@@ -906,8 +903,8 @@ static int finalise(sgx_det *h)
 #endif
     SGX_CHECK_HIP(hipMemset(h->d_results, 0, sizeof(sgx_det_result) * (size_t)B));      // entries past the counts are never written: keep them defined
     std::vector<SgxDetTab> xt, yt; build_tab(h->W, T, xt); build_tab(h->H, T, yt);
-    if ((rc = h->upload(&h->d_xt, xt)) || (rc = h->upload(&h->d_yt, yt))) return rc;
-    return h->alloc(&h->d_img, (size_t)B * h->H * ((3 * h->W + 3) & ~3) + 4);
+    if ((rc = h->mem.upload(&h->d_xt, xt)) || (rc = h->mem.upload(&h->d_yt, yt))) return rc;
+    return h->mem.alloc(&h->d_img, (size_t)B * h->H * ((3 * h->W + 3) & ~3) + 4);
 }
 
 extern "C" int sgx_det_create(const char *param_text, const void *bin, size_t bin_bytes, int width, int height, int max_batch,

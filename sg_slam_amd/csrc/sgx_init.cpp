@@ -3,6 +3,7 @@
 // The single initializer (sgx_initializer_*) is a batch of one fed from host memory.
 #include "sgx_init_kernels.h"
 #include "sgx_prof.h"
+#include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #include <math.h>
 #include <stdio.h>
@@ -11,16 +12,6 @@
 
 static_assert(sizeof(SgxInitReport) == sizeof(sgx_init_report), "SgxInitReport mirrors sgx_init_report");
 static_assert(sizeof(sgx_keypoint) == 28, "the kernels read a key as 7 words");
-
-// glibc random_r TYPE_3 (r[i] = r[i - 3] + r[i - 31]), the generator behind rand(): srand(seed) on the host, the draws on the device
-static void init_gsrand(unsigned seed, int32_t *g)
-{
-    int32_t word = seed ? (int32_t)seed : 1; g[0] = word;
-    for (int i = 1; i < 31; i++) { const long hi = word / 127773, lo = word % 127773; long w = 16807 * lo - 2836 * hi; if (w < 0) w += 2147483647; word = (int32_t)w; g[i] = word; }
-    int f = 3, b = 0;
-    for (int i = 0; i < 310; i++) { g[f] = (int32_t)((uint32_t)g[f] + (uint32_t)g[b]); f = (f + 1) % 31; b = (b + 1) % 31; }
-    g[31] = f; g[32] = b; g[33] = 0; g[34] = 0; g[35] = 0;
-}
 
 // parallax of CheckRT (:901) from the selected cosine, on the host: the one libm call of the path
 static float init_parallax(float c) { return (float)(acos((double)c) * 180 / 3.1415926535897932384626433832795); }
@@ -43,36 +34,27 @@ struct sgx_init_batch {
     int *off1 = nullptr, *off2 = nullptr, *nmatch = nullptr, *mi = nullptr, *ninl = nullptr, *dec = nullptr, *rng = nullptr, *draws = nullptr;
     float *cam = nullptr, *sigma = nullptr, *mxy = nullptr, *norm = nullptr, *hyp = nullptr, *scores = nullptr, *best = nullptr, *rt = nullptr, *cosp = nullptr, *pts = nullptr;
     uint8_t *inl = nullptr, *good = nullptr;
-    ~sgx_init_batch()
-    {
-        for (void *p : { (void *)off1, (void *)off2, (void *)nmatch, (void *)mi, (void *)ninl, (void *)dec, (void *)rng, (void *)draws, (void *)cam, (void *)sigma, (void *)mxy,
-                         (void *)norm, (void *)hyp, (void *)scores, (void *)best, (void *)rt, (void *)cosp, (void *)pts, (void *)inl, (void *)good })
-            if (p) (void)hipFree(p);
-    }
+    SgxDevMem mem;
 };
 
 extern "C" int sgx_init_batch_create(int max_pairs, int max_keys, int max_matches, int iterations, sgx_init_batch **out)
 {
+    if (out) *out = nullptr;
     if (!out || max_pairs < 1 || max_keys < 0 || max_matches < 0 || iterations < 1) return SGX_ERR_INVALID;
     sgx_init_batch *t = new sgx_init_batch;
     t->maxB = max_pairs; t->maxK = max_keys; t->maxM = max_matches; t->iterations = iterations;
     t->cap = iterations < SGX_INIT_MAXIT ? iterations : SGX_INIT_MAXIT;
     t->cos_gt = init_cos_threshold(true); t->cos_ge = init_cos_threshold(false);
     const size_t B = (size_t)max_pairs, M = (size_t)(max_matches > 0 ? max_matches : 1), c = (size_t)t->cap;
-    bool ok = hipMalloc((void **)&t->off1, 4 * (B + 1)) == hipSuccess && hipMalloc((void **)&t->off2, 4 * (B + 1)) == hipSuccess &&
-              hipMalloc((void **)&t->nmatch, 4 * B) == hipSuccess && hipMalloc((void **)&t->mi, 8 * M) == hipSuccess && hipMalloc((void **)&t->ninl, 8 * B) == hipSuccess &&
-              hipMalloc((void **)&t->dec, 8 * B) == hipSuccess && hipMalloc((void **)&t->rng, 4 * SGX_INIT_RNG * B) == hipSuccess &&
-              hipMalloc((void **)&t->draws, 32 * (size_t)iterations * B) == hipSuccess && hipMalloc((void **)&t->cam, 16 * B) == hipSuccess &&
-              hipMalloc((void **)&t->sigma, 4 * B) == hipSuccess && hipMalloc((void **)&t->mxy, 16 * M) == hipSuccess && hipMalloc((void **)&t->norm, 32 * B) == hipSuccess &&
-              hipMalloc((void **)&t->hyp, 4 * SGX_INIT_HYP * 2 * c * B) == hipSuccess && hipMalloc((void **)&t->scores, 4 * 2 * c * B) == hipSuccess &&
-              hipMalloc((void **)&t->best, 80 * B) == hipSuccess && hipMalloc((void **)&t->rt, 384 * B) == hipSuccess && hipMalloc((void **)&t->cosp, 32 * M) == hipSuccess &&
-              hipMalloc((void **)&t->pts, 96 * M) == hipSuccess && hipMalloc((void **)&t->inl, 2 * M) == hipSuccess && hipMalloc((void **)&t->good, 8 * M) == hipSuccess;
-    if (ok) {                                                    // every replica starts as srand(0)
-        t->rng_h.resize(SGX_INIT_RNG * B);
-        for (size_t b = 0; b < B; b++) init_gsrand(0u, t->rng_h.data() + SGX_INIT_RNG * b);
-        ok = hipMemcpy(t->rng, t->rng_h.data(), 4 * t->rng_h.size(), hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (!ok) { delete t; return SGX_ERR_NOMEM; }
+    t->rng_h.resize(SGX_GRAND_WORDS * B);                        // every replica starts as srand(0)
+    for (size_t b = 0; b < B; b++) sgx_gsrand(0u, t->rng_h.data() + SGX_GRAND_WORDS * b);
+    SgxDevMem &m = t->mem;
+    int rc;
+    if ((rc = m.alloc(&t->off1, B + 1)) || (rc = m.alloc(&t->off2, B + 1)) || (rc = m.alloc(&t->nmatch, B)) || (rc = m.alloc(&t->mi, 2 * M)) || (rc = m.alloc(&t->ninl, 2 * B)) ||
+        (rc = m.alloc(&t->dec, 2 * B)) || (rc = m.upload(&t->rng, t->rng_h)) || (rc = m.alloc(&t->draws, 8 * (size_t)iterations * B)) || (rc = m.alloc(&t->cam, 4 * B)) ||
+        (rc = m.alloc(&t->sigma, B)) || (rc = m.alloc(&t->mxy, 4 * M)) || (rc = m.alloc(&t->norm, 8 * B)) || (rc = m.alloc(&t->hyp, SGX_INIT_HYP * 2 * c * B)) ||
+        (rc = m.alloc(&t->scores, 2 * c * B)) || (rc = m.alloc(&t->best, 20 * B)) || (rc = m.alloc(&t->rt, 96 * B)) || (rc = m.alloc(&t->cosp, 8 * M)) ||
+        (rc = m.alloc(&t->pts, 24 * M)) || (rc = m.alloc(&t->inl, 2 * M)) || (rc = m.alloc(&t->good, 8 * M))) { delete t; return rc; }
     *out = t;
     return SGX_OK;
 }
@@ -103,8 +85,8 @@ extern "C" int sgx_init_batch_run_dev(sgx_init_batch *t, int B, const int32_t *o
     SGX_CHECK_HIP(hipMemcpyAsync(t->cam, t->cam_h.data(), 16 * (size_t)B, hipMemcpyHostToDevice, s));
     SGX_CHECK_HIP(hipMemcpyAsync(t->sigma, t->sigma_h.data(), 4 * (size_t)B, hipMemcpyHostToDevice, s));
     if (rand_seeds) {
-        for (int b = 0; b < B; b++) init_gsrand(rand_seeds[b], t->rng_h.data() + SGX_INIT_RNG * (size_t)b);
-        SGX_CHECK_HIP(hipMemcpyAsync(t->rng, t->rng_h.data(), 4 * SGX_INIT_RNG * (size_t)B, hipMemcpyHostToDevice, s));
+        for (int b = 0; b < B; b++) sgx_gsrand(rand_seeds[b], t->rng_h.data() + SGX_GRAND_WORDS * (size_t)b);
+        SGX_CHECK_HIP(hipMemcpyAsync(t->rng, t->rng_h.data(), 4 * SGX_GRAND_WORDS * (size_t)B, hipMemcpyHostToDevice, s));
     }
     SgxInitArgs A; memset(&A, 0, sizeof A);
     A.B = B; A.iterations = t->iterations; A.cap = t->cap; A.ntot = n1; A.off1 = t->off1; A.off2 = t->off2; A.keys1 = (const float *)keys1_dev; A.keys2 = (const float *)keys2_dev;
@@ -150,27 +132,23 @@ struct sgx_initializer {
     float cam[4] = { 0, 0, 0, 0 }, sigma = 1.f;
     sgx_keypoint *k1 = nullptr, *k2 = nullptr; int32_t *m12 = nullptr, *dd = nullptr, *ok = nullptr;
     float *R = nullptr, *tt = nullptr, *p3d = nullptr; uint8_t *tri = nullptr, *inl = nullptr; sgx_init_report *rep = nullptr;
-    ~sgx_initializer()
-    {
-        delete t;
-        for (void *p : { (void *)k1, (void *)k2, (void *)m12, (void *)dd, (void *)ok, (void *)R, (void *)tt, (void *)p3d, (void *)tri, (void *)inl, (void *)rep }) if (p) (void)hipFree(p);
-    }
+    SgxDevMem mem;
+    ~sgx_initializer() { delete t; }
 };
 
 extern "C" int sgx_initializer_create(int n1, const sgx_keypoint *keys1_un, const float *cam4, float sigma, int iterations, unsigned rand_seed, sgx_initializer **out)
 {
+    if (out) *out = nullptr;
     if (!out || n1 < 0 || !cam4 || iterations < 1 || (n1 > 0 && !keys1_un)) return SGX_ERR_INVALID;
     sgx_initializer *s = new sgx_initializer;
     s->n1 = n1; s->iterations = iterations; s->sigma = sigma;
     for (int i = 0; i < 4; i++) s->cam[i] = cam4[i];
     const size_t m = (size_t)(n1 > 0 ? n1 : 1);
-    bool ok = hipMalloc((void **)&s->k1, 28 * m) == hipSuccess && hipMalloc((void **)&s->m12, 4 * m) == hipSuccess && hipMalloc((void **)&s->dd, 32 * (size_t)iterations) == hipSuccess &&
-              hipMalloc((void **)&s->ok, 4) == hipSuccess && hipMalloc((void **)&s->R, 36) == hipSuccess && hipMalloc((void **)&s->tt, 12) == hipSuccess &&
-              hipMalloc((void **)&s->p3d, 12 * m) == hipSuccess && hipMalloc((void **)&s->tri, m) == hipSuccess && hipMalloc((void **)&s->inl, m) == hipSuccess &&
-              hipMalloc((void **)&s->rep, sizeof(sgx_init_report)) == hipSuccess;
-    if (ok && n1 > 0) ok = hipMemcpy(s->k1, keys1_un, 28 * (size_t)n1, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { delete s; return SGX_ERR_NOMEM; }
-    s->seed = rand_seed;                                         // the batch of one is sized at the first Initialize (n2 is not known before)
+    SgxDevMem &d = s->mem;
+    int rc;
+    if ((rc = d.upload(&s->k1, keys1_un, (size_t)n1)) || (rc = d.alloc(&s->m12, m)) || (rc = d.alloc(&s->dd, 8 * (size_t)iterations)) || (rc = d.alloc(&s->ok, 1)) || (rc = d.alloc(&s->R, 9)) ||
+        (rc = d.alloc(&s->tt, 3)) || (rc = d.alloc(&s->p3d, 3 * m)) || (rc = d.alloc(&s->tri, m)) || (rc = d.alloc(&s->inl, m)) || (rc = d.alloc(&s->rep, 1))) { delete s; return rc; }
+    s->seed = rand_seed;                                        // the batch of one is sized at the first Initialize (n2 is not known before)
     *out = s;
     return SGX_OK;
 }
@@ -182,16 +160,22 @@ extern "C" int sgx_initializer_initialize(sgx_initializer *s, int n2, const sgx_
 {
     if (!s || n2 < 0 || (n2 > 0 && !keys2_un) || !R21 || !t21 || !ok || (s->n1 > 0 && (!matches12 || !p3d || !triangulated || !inliers))) return SGX_ERR_INVALID;
     const int most = s->n1 > n2 ? s->n1 : n2;
-    if (!s->t || s->t->maxK < most) {                            // (re)size for this frame 2, carrying the replica's state over
-        sgx_init_batch *nt = nullptr;
-        const int r = sgx_init_batch_create(1, most, s->n1, s->iterations, &nt);
-        if (r != SGX_OK) return r;
-        if (s->t) SGX_CHECK_HIP(hipMemcpy(nt->rng, s->t->rng, 4 * SGX_INIT_RNG, hipMemcpyDeviceToDevice));
-        else { int32_t g[SGX_INIT_RNG]; init_gsrand(s->seed, g); SGX_CHECK_HIP(hipMemcpy(nt->rng, g, sizeof g, hipMemcpyHostToDevice)); }
+    if (!s->t || s->t->maxK < most) {
+        // (re)size for this frame 2 as a transaction: the new batch and the new k2 are built and the replica's state carried over before anything of the handle
+        // changes, so a failure leaves the initializer as it was (usable at its old size, the replica unmoved)
+        sgx_init_batch *nt = nullptr; sgx_keypoint *nk2 = nullptr;
+        const auto carry_replica = [&]() -> int {
+            if (s->t) SGX_CHECK_HIP(hipMemcpy(nt->rng, s->t->rng, 4 * SGX_GRAND_WORDS, hipMemcpyDeviceToDevice));
+            else { int32_t g[SGX_GRAND_WORDS]; sgx_gsrand(s->seed, g); SGX_CHECK_HIP(hipMemcpy(nt->rng, g, sizeof g, hipMemcpyHostToDevice)); }
+            return SGX_OK;
+        };
+        int r;
+        if ((r = sgx_init_batch_create(1, most, s->n1, s->iterations, &nt)) || (r = s->mem.alloc(&nk2, (size_t)most)) || (r = carry_replica())) {
+            delete nt; s->mem.release(nk2);
+            return r;
+        }
         delete s->t; s->t = nt;
-        if (s->k2) (void)hipFree(s->k2);
-        s->k2 = nullptr;
-        if (hipMalloc((void **)&s->k2, 28 * (size_t)(most > 0 ? most : 1)) != hipSuccess) return SGX_ERR_NOMEM;
+        s->mem.release(s->k2); s->k2 = nk2;
     }
     if (n2 > 0) SGX_CHECK_HIP(hipMemcpy(s->k2, keys2_un, 28 * (size_t)n2, hipMemcpyHostToDevice));
     if (s->n1 > 0) SGX_CHECK_HIP(hipMemcpy(s->m12, matches12, 4 * (size_t)s->n1, hipMemcpyHostToDevice));

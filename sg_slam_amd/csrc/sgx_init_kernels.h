@@ -25,12 +25,12 @@
 // k_init_finish = one workgroup per pair (counts, the min(50, nGood - 1)-th smallest cosine by rank, the selection rule, the outputs).
 #pragma once
 #include "sgx_rt.h"
+#include "sgx_grand.h"
 #include <math.h>
 #include <float.h>
 
 #define SGX_INIT_MAXIT 256           /* hypotheses per (pair, model) and launch */
 #define SGX_INIT_HYP 18              /* floats per hypothesis: H21 9 | H12 9, or F21 9 | unused */
-#define SGX_INIT_RNG 36              /* ints per glibc rand() replica: r[31], f, b, pad */
 #define SGX_INIT_TILE 512            /* matches staged per LDS tile of k_init_score */
 
 struct SgxInitReport {               // = sgx_init_report (include/sgx.h)
@@ -261,15 +261,6 @@ SGX_DEV bool sgx_init_check_f(const float *f, float u1, float v1, float u2, floa
 SGX_DEV float sgx_init_inv_sigma2(float sigma) { return (float)(1.0 / (double)(sigma * sigma)); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------- kernels
-SGX_DEV int32_t sgx_init_grand(int32_t *g)                       // glibc random_r TYPE_3, the generator behind rand()
-{
-    int f = g[31], b = g[32];
-    g[f] = (int32_t)((uint32_t)g[f] + (uint32_t)g[b]);
-    const int32_t o = (int32_t)(((uint32_t)g[f]) >> 1);
-    g[31] = (f + 1) % 31; g[32] = (b + 1) % 31;
-    return o;
-}
-
 // one lane per pair: mvMatches12 (:51-63) in index order and, without caller draws, the 8 x iterations values its rand() replica hands out (none when N < 8)
 SGX_KERNEL(64) k_init_setup(SgxInitArgs A, int32_t *rng, int32_t *own_draws)
 {
@@ -290,7 +281,7 @@ SGX_KERNEL(64) k_init_setup(SgxInitArgs A, int32_t *rng, int32_t *own_draws)
         }
         A.nmatch[b] = N;
         for (int q = 0; q < 2; q++) { A.best[10 * (2 * b + q)] = 0.f; A.ninl[2 * b + q] = 0; }       // score = 0.0 (:137, :188)
-        if (own_draws && N >= 8) { int32_t *g = rng + SGX_INIT_RNG * b; for (int i = 0; i < 8 * A.iterations; i++) own_draws[(size_t)b * 8 * A.iterations + i] = sgx_init_grand(g); }
+        if (own_draws && N >= 8) { int32_t *g = rng + SGX_GRAND_WORDS * b; for (int i = 0; i < 8 * A.iterations; i++) own_draws[(size_t)b * 8 * A.iterations + i] = sgx_grand(g); }
     }
     SGX_THREADS_END
 }

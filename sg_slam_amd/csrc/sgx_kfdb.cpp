@@ -2,6 +2,7 @@
 // (:40-73) as host bookkeeping over it, and the two queries (:76-197, :199-309) as the launch sequence of sgx_kfdb_kernels.h; sgx_voc_bow_batch_dev, the BowVector a query
 // is made of, sits in sgx_voc.cpp beside the transform it completes.
 #include "sgx_kfdb_kernels.h"
+#include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #ifdef SGX_DEBUG_TAPS
 #include "../../include/sgx_debug.h"      // test / tuning taps: compiled into tests/taps/libsgx_taps.so and the emulator only
@@ -36,18 +37,12 @@ struct sgx_kfdb {
     // staging of the single-query entries
     int *s_ids = nullptr, *s_cnt = nullptr, *s_conn_off = nullptr, *s_conn = nullptr, *s_cand = nullptr, *s_ncand = nullptr, *s_slots = nullptr;
     double *s_w = nullptr; float *s_min = nullptr; SgxKfdbReport *s_report = nullptr;
-    std::vector<void *> allocs;
-    ~sgx_kfdb() { for (void *p : allocs) (void)hipFree(p); }
-    template <class T> bool alloc(T **p, size_t n)
-    {
-        void *v = nullptr;
-        if (hipMalloc(&v, (n ? n : 1) * sizeof(T)) != hipSuccess) return false;
-        allocs.push_back(v); *p = (T *)v; return true;
-    }
+    SgxDevMem mem;
 };
 
 extern "C" int sgx_kfdb_create(const sgx_voc *voc, int max_keyframes, int max_bow_entries, int max_query_words, int max_queries, sgx_kfdb **out)
 {
+    if (out) *out = nullptr;
     if (!out || !voc || max_keyframes < 1 || max_bow_entries < 1 || max_query_words < 0 || max_queries < 1) return SGX_ERR_INVALID;
     int32_t scoring = 0, nwords = 0;
     if (sgx_voc_info(voc, nullptr, nullptr, &scoring, nullptr, nullptr, &nwords) != SGX_OK) return SGX_ERR_INVALID;
@@ -58,13 +53,15 @@ extern "C" int sgx_kfdb_create(const sgx_voc *voc, int max_keyframes, int max_bo
     h->nwords = nwords; h->max_kf = max_keyframes; h->max_ent = max_bow_entries; h->max_qw = max_query_words; h->max_q = max_queries;
     const size_t N = (size_t)max_keyframes, QN = N * (size_t)max_queries;
     h->slot.resize(N); h->kf_id.assign(N, -1); h->off.assign(N, 0); h->cnt.assign(N, 0); h->seq.assign(N, 0);
-    const bool ok = h->alloc(&h->d_ent_id, (size_t)max_bow_entries) && h->alloc(&h->d_ent_w, (size_t)max_bow_entries) && h->alloc(&h->d_off, N) && h->alloc(&h->d_cnt, N) &&
-        h->alloc(&h->d_seq, N) && h->alloc(&h->d_kf_id, N) && h->alloc(&h->d_covis, N * SGX_KFDB_COVIS) && h->alloc(&h->d_sorted_id, N) && h->alloc(&h->d_sorted_slot, N) &&
-        h->alloc(&h->d_reloc, N) && h->alloc(&h->d_conn, QN) && h->alloc(&h->d_words, QN) && h->alloc(&h->d_first, QN) && h->alloc(&h->d_order, QN) && h->alloc(&h->d_best, QN) &&
-        h->alloc(&h->d_firstrank, QN) && h->alloc(&h->d_score, QN) && h->alloc(&h->d_acc, QN) && h->alloc(&h->d_key, QN) &&
-        h->alloc(&h->s_ids, (size_t)max_query_words) && h->alloc(&h->s_w, (size_t)max_query_words) && h->alloc(&h->s_cnt, 1) && h->alloc(&h->s_conn_off, 2) &&
-        h->alloc(&h->s_conn, N) && h->alloc(&h->s_cand, N) && h->alloc(&h->s_ncand, 1) && h->alloc(&h->s_slots, N) && h->alloc(&h->s_min, 1) && h->alloc(&h->s_report, 1);
-    if (!ok) { delete h; return SGX_ERR_NOMEM; }
+    SgxDevMem &m = h->mem;
+    int rc;
+    if ((rc = m.alloc(&h->d_ent_id, (size_t)max_bow_entries)) || (rc = m.alloc(&h->d_ent_w, (size_t)max_bow_entries)) || (rc = m.alloc(&h->d_off, N)) || (rc = m.alloc(&h->d_cnt, N)) ||
+        (rc = m.alloc(&h->d_seq, N)) || (rc = m.alloc(&h->d_kf_id, N)) || (rc = m.alloc(&h->d_covis, N * SGX_KFDB_COVIS)) || (rc = m.alloc(&h->d_sorted_id, N)) ||
+        (rc = m.alloc(&h->d_sorted_slot, N)) || (rc = m.alloc(&h->d_reloc, N)) || (rc = m.alloc(&h->d_conn, QN)) || (rc = m.alloc(&h->d_words, QN)) || (rc = m.alloc(&h->d_first, QN)) ||
+        (rc = m.alloc(&h->d_order, QN)) || (rc = m.alloc(&h->d_best, QN)) || (rc = m.alloc(&h->d_firstrank, QN)) || (rc = m.alloc(&h->d_score, QN)) || (rc = m.alloc(&h->d_acc, QN)) ||
+        (rc = m.alloc(&h->d_key, QN)) || (rc = m.alloc(&h->s_ids, (size_t)max_query_words)) || (rc = m.alloc(&h->s_w, (size_t)max_query_words)) || (rc = m.alloc(&h->s_cnt, 1)) ||
+        (rc = m.alloc(&h->s_conn_off, 2)) || (rc = m.alloc(&h->s_conn, N)) || (rc = m.alloc(&h->s_cand, N)) || (rc = m.alloc(&h->s_ncand, 1)) || (rc = m.alloc(&h->s_slots, N)) ||
+        (rc = m.alloc(&h->s_min, 1)) || (rc = m.alloc(&h->s_report, 1))) { delete h; return rc; }
     if (hipMemset(h->d_reloc, 0, N * sizeof(float)) != hipSuccess) { delete h; return SGX_ERR_DEVICE; }
     for (int s = max_keyframes - 1; s >= 0; s--) h->free_slots.push_back(s);
     *out = h;

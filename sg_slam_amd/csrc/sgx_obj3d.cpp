@@ -2,6 +2,7 @@
 // per-job workspace; detect_batch_dev validates the jobs, stages their records and enqueues the kernels of sgx_obj3d_kernels.h on the caller's stream; the single
 // detect is a batch of one fed from host memory.  ObjectDatabase::addObject is host code.
 #include "sgx_obj3d_kernels.h"
+#include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #include <math.h>
 #include <stdio.h>
@@ -24,23 +25,40 @@ struct sgx_obj3d {
     float *wx = nullptr, *wy = nullptr, *wz = nullptr, *dist = nullptr, *scen = nullptr;
     int *state = nullptr, *parent = nullptr, *label = nullptr, *csize = nullptr, *ji = nullptr, *sroot = nullptr, *ssize = nullptr, *smm = nullptr, *sorder = nullptr;
     double *jd = nullptr;
-    float *one_depth = nullptr; double *one_twc = nullptr; SgxObjResult *one_result = nullptr;      // the synchronous entry's staging (allocated on first use)
+    float *one_depth = nullptr; double *one_twc = nullptr; SgxObjResult *one_result = nullptr;      // the synchronous entry's staging
+    SgxDevMem mem;
+#ifndef SGX_EMU
     ~sgx_obj3d()
     {
-        for (void *q : { (void *)jobs, (void *)wx, (void *)wy, (void *)wz, (void *)dist, (void *)scen, (void *)state, (void *)parent, (void *)label, (void *)csize, (void *)ji,
-                         (void *)sroot, (void *)ssize, (void *)smm, (void *)sorder, (void *)jd, (void *)one_depth, (void *)one_twc, (void *)one_result })
-            if (q) (void)hipFree(q);
-#ifndef SGX_EMU
         if (pinned) (void)hipHostFree(pinned);
         if (staged) (void)hipEventDestroy(staged);
-#endif
     }
+#endif
 };
 
 static bool obj_finite(double v) { return v == v && v - v == 0; }
 
+// the per-job workspace, the synchronous entry's staging, the pinned job records and their event
+static int obj_allocate(sgx_obj3d *h)
+{
+    const size_t J = (size_t)h->max_jobs, P = J * (size_t)h->cap, S = J * (size_t)h->slot_cap;
+    SgxDevMem &m = h->mem;
+    int rc;
+    if ((rc = m.alloc(&h->jobs, J)) || (rc = m.alloc(&h->wx, P)) || (rc = m.alloc(&h->wy, P)) || (rc = m.alloc(&h->wz, P)) || (rc = m.alloc(&h->dist, P)) ||
+        (rc = m.alloc(&h->state, P)) || (rc = m.alloc(&h->parent, P)) || (rc = m.alloc(&h->label, P)) || (rc = m.alloc(&h->csize, P)) || (rc = m.alloc(&h->ji, SGX_OBJ_JI * J)) ||
+        (rc = m.alloc(&h->jd, SGX_OBJ_JD * J)) || (rc = m.alloc(&h->sroot, S)) || (rc = m.alloc(&h->ssize, S)) || (rc = m.alloc(&h->smm, SGX_OBJ_MM * S)) ||
+        (rc = m.alloc(&h->sorder, S)) || (rc = m.alloc(&h->scen, 3 * S)) ||
+        (rc = m.alloc(&h->one_depth, (size_t)h->width * h->height)) || (rc = m.alloc(&h->one_twc, 16)) || (rc = m.alloc(&h->one_result, 1))) return rc;
+#ifndef SGX_EMU
+    if (hipHostMalloc((void **)&h->pinned, sizeof(SgxObjJob) * J, hipHostMallocDefault) != hipSuccess) return SGX_ERR_NOMEM;
+    if (hipEventCreateWithFlags(&h->staged, hipEventDisableTiming) != hipSuccess) return SGX_ERR_DEVICE;
+#endif
+    return SGX_OK;
+}
+
 extern "C" int sgx_obj3d_create(int width, int height, int max_images, int max_jobs, int max_crop_points, const sgx_obj3d_params *params, sgx_obj3d **out)
 {
+    if (out) *out = nullptr;
     if (!out || !params || width < 1 || height < 1 || max_images < 1 || max_jobs < 1 || max_crop_points < 0) return SGX_ERR_INVALID;
     if (params->sor_mean_k < 1 || !obj_finite(params->camera_valid_depth_min) || !obj_finite(params->camera_valid_depth_max) || !obj_finite(params->cluster_tolerance))
         return SGX_ERR_INVALID;
@@ -51,21 +69,8 @@ extern "C" int sgx_obj3d_create(int width, int height, int max_images, int max_j
     sgx_obj3d *h = new sgx_obj3d;
     h->width = width; h->height = height; h->max_images = max_images; h->max_jobs = max_jobs; h->cap = max_crop_points; h->p = *params;
     h->slot_cap = max_crop_points / (params->cluster_min_size > 1 ? params->cluster_min_size : 1) + 1;       // a surviving cluster has at least min_size points
-    const size_t J = (size_t)max_jobs, P = J * (size_t)max_crop_points, S = J * (size_t)h->slot_cap;
-    const bool ok = hipMalloc((void **)&h->jobs, sizeof(SgxObjJob) * J) == hipSuccess && hipMalloc((void **)&h->wx, 4 * P) == hipSuccess &&
-                    hipMalloc((void **)&h->wy, 4 * P) == hipSuccess && hipMalloc((void **)&h->wz, 4 * P) == hipSuccess && hipMalloc((void **)&h->dist, 4 * P) == hipSuccess &&
-                    hipMalloc((void **)&h->state, 4 * P) == hipSuccess && hipMalloc((void **)&h->parent, 4 * P) == hipSuccess &&
-                    hipMalloc((void **)&h->label, 4 * P) == hipSuccess && hipMalloc((void **)&h->csize, 4 * P) == hipSuccess &&
-                    hipMalloc((void **)&h->ji, 4 * SGX_OBJ_JI * J) == hipSuccess && hipMalloc((void **)&h->jd, 8 * SGX_OBJ_JD * J) == hipSuccess &&
-                    hipMalloc((void **)&h->sroot, 4 * S) == hipSuccess && hipMalloc((void **)&h->ssize, 4 * S) == hipSuccess &&
-                    hipMalloc((void **)&h->smm, 4 * SGX_OBJ_MM * S) == hipSuccess && hipMalloc((void **)&h->sorder, 4 * S) == hipSuccess &&
-                    hipMalloc((void **)&h->scen, 12 * S) == hipSuccess;
-    if (!ok) { delete h; return SGX_ERR_NOMEM; }
-#ifndef SGX_EMU
-    if (hipHostMalloc((void **)&h->pinned, sizeof(SgxObjJob) * J, hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&h->staged, hipEventDisableTiming) != hipSuccess) {
-        delete h; return SGX_ERR_NOMEM;
-    }
-#endif
+    const int rc = obj_allocate(h);
+    if (rc != SGX_OK) { delete h; return rc; }
     *out = h;
     return SGX_OK;
 }
@@ -155,9 +160,6 @@ extern "C" int sgx_obj3d_detect(sgx_obj3d *h, const float *depth, const float *c
 {
     if (!h || !depth || !cam4 || !twc || !job || !result || job->image != 0) return SGX_ERR_INVALID;
     const size_t px = (size_t)h->width * h->height;
-    if (!h->one_depth && hipMalloc((void **)&h->one_depth, 4 * px) != hipSuccess) { h->one_depth = nullptr; return SGX_ERR_NOMEM; }
-    if (!h->one_twc && hipMalloc((void **)&h->one_twc, 8 * 16) != hipSuccess) { h->one_twc = nullptr; return SGX_ERR_NOMEM; }
-    if (!h->one_result && hipMalloc((void **)&h->one_result, sizeof(SgxObjResult)) != hipSuccess) { h->one_result = nullptr; return SGX_ERR_NOMEM; }
     SGX_CHECK_HIP(hipMemcpy(h->one_depth, depth, 4 * px, hipMemcpyHostToDevice));
     SGX_CHECK_HIP(hipMemcpy(h->one_twc, twc, 8 * 16, hipMemcpyHostToDevice));
     const int r = sgx_obj3d_detect_batch_dev(h, h->one_depth, h->width, 1, cam4, h->one_twc, job, 1, (sgx_obj3d_result *)h->one_result, nullptr);

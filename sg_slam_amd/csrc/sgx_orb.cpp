@@ -3,6 +3,7 @@
 // with -DSGX_EMU (kernel-logic emulator, tests only).  Reference behaviour: src/sg-slam/src/ORBextractor.cc (cited inline).
 #include "sgx_orb_kernels.h"
 #include "sgx_prof.h"
+#include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #ifdef SGX_DEBUG_TAPS
 #include "../../include/sgx_debug.h"      // test / tuning taps: compiled into tests/taps/libsgx_taps.so and the emulator only
@@ -24,7 +25,7 @@ thread_local sgx_dim3 blockIdx, blockDim, gridDim;
 struct sgx_orb {
     sgx_orb_config cfg;
     OrbPlan p;                     // what creation decided; the launches read p.g, the pyramid plan, oct_maxlim and the packed umax
-    std::vector<void *> dev;       // every device allocation of the handle
+    SgxDevMem mem;                 // every device allocation of the handle
     // device tables: the plan's vectors
     SgxRun *d_runs = nullptr; SgxBlurTile *d_blur_tiles = nullptr; signed char *d_pattern = nullptr;
     SgxXTab *d_xt[SGX_MAX_LEVELS] = {}; SgxYTab *d_yt[SGX_MAX_LEVELS] = {};        // k_resize; d_yt[l] is level l's slice of d_yt_all
@@ -35,12 +36,6 @@ struct sgx_orb {
     // single-frame staging for sgx_orb_extract
     uint8_t *d_gray1 = nullptr; uint8_t *d_kps1 = nullptr; uint8_t *d_desc1 = nullptr; int *d_count1 = nullptr;
     int detected_batch = 0;        // batch of the last sgx_orb_detect_batch_dev whose pyramid and sel lists are still in the workspace (0: none; any other extraction clears it)
-
-    ~sgx_orb() { for (void *q : dev) (void)hipFree(q); }
-    template <class Tp> int alloc(Tp **d, size_t n) { void *q = nullptr; if (hipMalloc(&q, (n ? n : 1) * sizeof(Tp)) != hipSuccess) return SGX_ERR_NOMEM; dev.push_back(q); *d = (Tp *)q; return SGX_OK; }
-    // a host array as a device allocation of the handle (blocking copy)
-    template <class Tp> int upload(Tp **d, const Tp *src, size_t n) { if (alloc(d, n)) return SGX_ERR_NOMEM; return !n || hipMemcpy(*d, src, n * sizeof(Tp), hipMemcpyHostToDevice) == hipSuccess ? SGX_OK : SGX_ERR_DEVICE; }
-    template <class Tp> int upload(Tp **d, const std::vector<Tp> &v) { return upload(d, v.data(), v.size()); }
 };
 
 static thread_local int g_orb_unfused_pyramid = 0;      // test tap: 1 = one k_resize launch per level instead of the fused k_pyramid
@@ -102,18 +97,19 @@ static int orb_allocate(sgx_orb *h)
 {
     const OrbPlan &p = h->p; const SgxOrbGeom &g = p.g;
     const size_t B = (size_t)h->cfg.max_batch, nl = (size_t)g.nlevels;
+    SgxDevMem &m = h->mem;
     int rc;
-    if ((rc = h->upload(&h->d_runs, p.runs)) || (rc = h->upload(&h->d_blur_tiles, p.blur_tiles)) || (rc = h->upload(&h->d_pattern, sgx_orb_pattern_xy, 1024)) ||
-        (rc = h->upload(&h->d_yt_all, p.yt_all)) || (rc = h->upload(&h->d_xg_all, p.xgroups)) || (rc = h->upload(&h->d_pyr_rects, p.rects))) return rc;
+    if ((rc = m.upload(&h->d_runs, p.runs)) || (rc = m.upload(&h->d_blur_tiles, p.blur_tiles)) || (rc = m.upload(&h->d_pattern, sgx_orb_pattern_xy, 1024)) ||
+        (rc = m.upload(&h->d_yt_all, p.yt_all)) || (rc = m.upload(&h->d_xg_all, p.xgroups)) || (rc = m.upload(&h->d_pyr_rects, p.rects))) return rc;
     for (size_t l = 1; l < nl; l++) {
-        if ((rc = h->upload(&h->d_xt[l], p.xt[l]))) return rc;
+        if ((rc = m.upload(&h->d_xt[l], p.xt[l]))) return rc;
         h->d_yt[l] = h->d_yt_all + p.pyr_tabs.yoff[l];
     }
-    if (h->alloc(&h->d_pyr, B * g.pyr_pitch + 256) || h->alloc(&h->d_blur, B * g.blur_pitch + 256) || h->alloc(&h->d_cand, B * g.cand_pitch) ||
-        h->alloc(&h->d_node_scratch, B * g.cand_pitch) || h->alloc(&h->d_cand_count, B * nl) || h->alloc(&h->d_sel, B * nl * SGX_OCT_MAXN) ||
-        h->alloc(&h->d_sel_count, B * nl) || h->alloc(&h->d_status, 1) ||
-        h->alloc(&h->d_gray1, (size_t)((g.W + 3) & ~3) * g.H) ||         // staging copy of a host frame, rows padded to dwords (the kernels stage aligned dwords)
-        h->alloc(&h->d_kps1, (size_t)g.kp_cap * 28) || h->alloc(&h->d_desc1, (size_t)g.kp_cap * 32) || h->alloc(&h->d_count1, 1)) return SGX_ERR_NOMEM;
+    if (m.alloc(&h->d_pyr, B * g.pyr_pitch + 256) || m.alloc(&h->d_blur, B * g.blur_pitch + 256) || m.alloc(&h->d_cand, B * g.cand_pitch) ||
+        m.alloc(&h->d_node_scratch, B * g.cand_pitch) || m.alloc(&h->d_cand_count, B * nl) || m.alloc(&h->d_sel, B * nl * SGX_OCT_MAXN) ||
+        m.alloc(&h->d_sel_count, B * nl) || m.alloc(&h->d_status, 1) ||
+        m.alloc(&h->d_gray1, (size_t)((g.W + 3) & ~3) * g.H) ||          // staging copy of a host frame, rows padded to dwords (the kernels stage aligned dwords)
+        m.alloc(&h->d_kps1, (size_t)g.kp_cap * 28) || m.alloc(&h->d_desc1, (size_t)g.kp_cap * 32) || m.alloc(&h->d_count1, 1)) return SGX_ERR_NOMEM;
     SGX_CHECK_HIP(hipMemsetAsync(h->d_status, 0, 4, 0));
     SGX_CHECK_HIP(hipStreamSynchronize(0));
     return SGX_OK;

@@ -2,6 +2,8 @@
 // replicas and persistent state (mnIterations, the best model) on the device; iterate() runs the kernels of sgx_pnp_kernels.h in chunks of SGX_PNP_MAXIT hypotheses.
 // The single solver (sgx_pnp_solver_*) is a batch of one fed from host memory.
 #include "sgx_pnp_kernels.h"
+#include "sgx_grand.h"
+#include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #include <limits.h>
 #include <math.h>
@@ -12,39 +14,17 @@
 #include "../../include/sgx_debug.h"      // test taps: compiled into tests/taps/libsgx_taps.so and the emulator only
 #endif
 
-
-#define SGX_PNP_RNG 36               /* ints per glibc rand() replica: r[31], f, b, pad */
-
-// glibc random_r TYPE_3 (r[i] = r[i - 3] + r[i - 31]), the generator behind rand(): srand(seed) on the host, the draws on the device
-static void pnp_gsrand(unsigned seed, int32_t *g)
-{
-    int32_t word = seed ? (int32_t)seed : 1; g[0] = word;
-    for (int i = 1; i < 31; i++) { const long hi = word / 127773, lo = word % 127773; long w = 16807 * lo - 2836 * hi; if (w < 0) w += 2147483647; word = (int32_t)w; g[i] = word; }
-    int f = 3, b = 0;
-    for (int i = 0; i < 310; i++) { g[f] = (int32_t)((uint32_t)g[f] + (uint32_t)g[b]); f = (f + 1) % 31; b = (b + 1) % 31; }
-    g[31] = f; g[32] = b; g[33] = 0; g[34] = 0; g[35] = 0;
-}
-
-SGX_DEV int32_t sgx_pnp_grand(int32_t *g)
-{
-    int f = g[31], b = g[32];
-    g[f] = (int32_t)((uint32_t)g[f] + (uint32_t)g[b]);
-    const int32_t o = (int32_t)(((uint32_t)g[f]) >> 1);
-    g[31] = (f + 1) % 31; g[32] = (b + 1) % 31;
-    return o;
-}
-
 // replica draws of one chunk (one lane per solver): the state at the start of the call is kept in saved; the draws of a chunk continue from the live state
 SGX_KERNEL(64) k_pnp_rng(SgxPnpArgs A, int32_t *rng, int32_t *saved, int32_t *draws, int save)
 {
     SGX_THREADS_BEGIN(tid)
     const int b = (int)blockIdx.x * 64 + tid;
     if (b < A.B) {
-        int32_t *g = rng + SGX_PNP_RNG * b, *sv = saved + SGX_PNP_RNG * b;
-        if (save) for (int i = 0; i < SGX_PNP_RNG; i++) sv[i] = g[i];
+        int32_t *g = rng + SGX_GRAND_WORDS * b, *sv = saved + SGX_GRAND_WORDS * b;
+        if (save) for (int i = 0; i < SGX_GRAND_WORDS; i++) sv[i] = g[i];
         const int total = sgx_pnp_call_total(A.state + SGX_PNP_ST * b, A.n_iterations);
         int nh = total - A.chunk0; if (nh > A.chunk_n) nh = A.chunk_n; if (nh < 0 || A.call[SGX_PNP_CS * b] >= 0) nh = 0;
-        for (int i = 0; i < 4 * nh; i++) draws[(size_t)b * 4 * A.cap + i] = sgx_pnp_grand(g);
+        for (int i = 0; i < 4 * nh; i++) draws[(size_t)b * 4 * A.cap + i] = sgx_grand(g);
     }
     SGX_THREADS_END
 }
@@ -55,9 +35,9 @@ SGX_KERNEL(64) k_pnp_rng_commit(SgxPnpArgs A, int32_t *rng, const int32_t *saved
     SGX_THREADS_BEGIN(tid)
     const int b = (int)blockIdx.x * 64 + tid;
     if (b < A.B) {
-        int32_t *g = rng + SGX_PNP_RNG * b; const int32_t *sv = saved + SGX_PNP_RNG * b;
-        for (int i = 0; i < SGX_PNP_RNG; i++) g[i] = sv[i];
-        for (int i = 0; i < 4 * A.call[SGX_PNP_CS * b + 1]; i++) (void)sgx_pnp_grand(g);
+        int32_t *g = rng + SGX_GRAND_WORDS * b; const int32_t *sv = saved + SGX_GRAND_WORDS * b;
+        for (int i = 0; i < SGX_GRAND_WORDS; i++) g[i] = sv[i];
+        for (int i = 0; i < 4 * A.call[SGX_PNP_CS * b + 1]; i++) (void)sgx_grand(g);
     }
     SGX_THREADS_END
 }
@@ -77,43 +57,38 @@ struct sgx_pnp_batch {
     float *p2d = nullptr, *p3dw = nullptr, *sigma2 = nullptr, *cam = nullptr, *th2 = nullptr, *best_tcw = nullptr, *tcw_out = nullptr;
     uint8_t *best_mask = nullptr, *inl_out = nullptr;
     double *hyp = nullptr, *ws = nullptr;
-    ~sgx_pnp_batch()
-    {
-        for (void *p : { (void *)offsets, (void *)state, (void *)call, (void *)counts, (void *)draws, (void *)rng, (void *)rng_saved, (void *)p2d, (void *)p3dw, (void *)sigma2,
-                         (void *)cam, (void *)th2, (void *)best_tcw, (void *)tcw_out, (void *)best_mask, (void *)inl_out, (void *)hyp, (void *)ws })
-            if (p) (void)hipFree(p);
-    }
+    SgxDevMem mem;
 };
 
 extern "C" int sgx_pnp_batch_create(int max_solvers, int max_correspondences, sgx_pnp_batch **out)
 {
+    if (out) *out = nullptr;
     if (!out || max_solvers < 1 || max_correspondences < 0) return SGX_ERR_INVALID;
     sgx_pnp_batch *t = new sgx_pnp_batch;
     const size_t B = (size_t)max_solvers, N = (size_t)(max_correspondences > 0 ? max_correspondences : 1);
     t->maxB = max_solvers; t->maxN = max_correspondences;
-    bool ok = hipMalloc((void **)&t->offsets, 4 * (B + 1)) == hipSuccess && hipMalloc((void **)&t->state, 4 * SGX_PNP_ST * B) == hipSuccess &&
-              hipMalloc((void **)&t->call, 4 * SGX_PNP_CS * B) == hipSuccess && hipMalloc((void **)&t->rng, 4 * SGX_PNP_RNG * B) == hipSuccess &&
-              hipMalloc((void **)&t->rng_saved, 4 * SGX_PNP_RNG * B) == hipSuccess && hipMalloc((void **)&t->p2d, 8 * N) == hipSuccess &&
-              hipMalloc((void **)&t->p3dw, 12 * N) == hipSuccess && hipMalloc((void **)&t->sigma2, 4 * N) == hipSuccess && hipMalloc((void **)&t->cam, 16 * B) == hipSuccess &&
-              hipMalloc((void **)&t->th2, 4 * B) == hipSuccess && hipMalloc((void **)&t->best_tcw, 64 * B) == hipSuccess && hipMalloc((void **)&t->tcw_out, 64 * B) == hipSuccess &&
-              hipMalloc((void **)&t->best_mask, N) == hipSuccess && hipMalloc((void **)&t->inl_out, N) == hipSuccess &&
-              hipMalloc((void **)&t->ws, 8 * 36 * N) == hipSuccess;
-    if (!ok) { delete t; return SGX_ERR_NOMEM; }
+    SgxDevMem &m = t->mem;
+    int rc;
+    if ((rc = m.alloc(&t->offsets, B + 1)) || (rc = m.alloc(&t->state, SGX_PNP_ST * B)) || (rc = m.alloc(&t->call, SGX_PNP_CS * B)) ||
+        (rc = m.alloc(&t->rng, SGX_GRAND_WORDS * B)) || (rc = m.alloc(&t->rng_saved, SGX_GRAND_WORDS * B)) || (rc = m.alloc(&t->p2d, 2 * N)) || (rc = m.alloc(&t->p3dw, 3 * N)) ||
+        (rc = m.alloc(&t->sigma2, N)) || (rc = m.alloc(&t->cam, 4 * B)) || (rc = m.alloc(&t->th2, B)) || (rc = m.alloc(&t->best_tcw, 16 * B)) ||
+        (rc = m.alloc(&t->tcw_out, 16 * B)) || (rc = m.alloc(&t->best_mask, N)) || (rc = m.alloc(&t->inl_out, N)) || (rc = m.alloc(&t->ws, 36 * N))) { delete t; return rc; }
     *out = t;
     return SGX_OK;
 }
 
 extern "C" void sgx_pnp_batch_destroy(sgx_pnp_batch *t) { delete t; }
 
-// hypothesis buffers for `need` hypotheses per solver (a relocalisation call runs about 35; at most SGX_PNP_MAXIT per launch)
+// hypothesis buffers for `need` hypotheses per solver (a relocalisation call runs about 35; at most SGX_PNP_MAXIT per launch).  All or nothing: after a failure the
+// batch holds none of the three and cap is 0
 static int pnp_reserve(sgx_pnp_batch *t, int need)
 {
     if (need <= t->cap) return SGX_OK;
-    for (void *p : { (void *)t->hyp, (void *)t->counts, (void *)t->draws }) if (p) (void)hipFree(p);
-    t->hyp = nullptr; t->counts = nullptr; t->draws = nullptr; t->cap = 0;
+    const auto drop = [t] { t->mem.release(t->hyp); t->mem.release(t->counts); t->mem.release(t->draws); t->hyp = nullptr; t->counts = nullptr; t->draws = nullptr; t->cap = 0; };
+    drop();
     const size_t B = (size_t)t->maxB, c = (size_t)need;
-    if (hipMalloc((void **)&t->hyp, 8 * SGX_PNP_HYP * c * B) != hipSuccess || hipMalloc((void **)&t->counts, 4 * c * B) != hipSuccess ||
-        hipMalloc((void **)&t->draws, 16 * c * B) != hipSuccess) return SGX_ERR_NOMEM;
+    int rc;
+    if ((rc = t->mem.alloc(&t->hyp, SGX_PNP_HYP * c * B)) || (rc = t->mem.alloc(&t->counts, c * B)) || (rc = t->mem.alloc(&t->draws, 4 * c * B))) { drop(); return rc; }
     t->cap = need;
     return SGX_OK;
 }
@@ -155,7 +130,7 @@ extern "C" int sgx_pnp_batch_set_dev(sgx_pnp_batch *t, int B, const int32_t *off
     for (int b = 0; b < B; b++) if (offsets[b + 1] < offsets[b]) return SGX_ERR_INVALID;
     const int n = offsets[B];
     if (n > t->maxN || (n > 0 && (!p2d_dev || !sigma2_dev || !p3dw_dev))) return SGX_ERR_INVALID;
-    std::vector<int> st((size_t)SGX_PNP_ST * B, 0), rng((size_t)SGX_PNP_RNG * B);
+    std::vector<int> st((size_t)SGX_PNP_ST * B, 0), rng((size_t)SGX_GRAND_WORDS * B);
     std::vector<float> th2(B), tcw((size_t)16 * B, 0.f);
     int max_its = 1;
     for (int b = 0; b < B; b++) {
@@ -166,10 +141,10 @@ extern "C" int sgx_pnp_batch_set_dev(sgx_pnp_batch *t, int B, const int32_t *off
         s[SGX_PNP_N] = N; s[SGX_PNP_MININ] = minIn; s[SGX_PNP_MAXITS] = maxIts;
         th2[b] = (float)ransac[6 * b + 5];
         if (maxIts > max_its) max_its = maxIts;
-        pnp_gsrand(rand_seeds ? rand_seeds[b] : 0u, rng.data() + SGX_PNP_RNG * b);
+        sgx_gsrand(rand_seeds ? rand_seeds[b] : 0u, rng.data() + SGX_GRAND_WORDS * b);
     }
     const sgx_stream_t s = (sgx_stream_t)stream;
-    t->B = B; t->ntot = n; t->max_its = max_its; t->offsets_h.assign(offsets, offsets + B + 1);
+    t->B = 0;                                                    // not set until every copy below has arrived: iterate_dev refuses a batch that a failed copy left half written
     SGX_CHECK_HIP(hipMemcpyAsync(t->offsets, offsets, 4 * (size_t)(B + 1), hipMemcpyHostToDevice, s));
     SGX_CHECK_HIP(hipMemcpyAsync(t->state, st.data(), 4 * st.size(), hipMemcpyHostToDevice, s));
     SGX_CHECK_HIP(hipMemcpyAsync(t->rng, rng.data(), 4 * rng.size(), hipMemcpyHostToDevice, s));
@@ -184,6 +159,8 @@ extern "C" int sgx_pnp_batch_set_dev(sgx_pnp_batch *t, int B, const int32_t *off
     }
     // host inputs are staged: the caller may reuse them when this returns
     SGX_CHECK_HIP(hipStreamSynchronize(s));
+    t->offsets_h.assign(offsets, offsets + B + 1);
+    t->B = B; t->ntot = n; t->max_its = max_its;
     return SGX_OK;
 }
 
@@ -224,28 +201,27 @@ struct sgx_pnp_solver {
     sgx_pnp_batch *t = nullptr;
     int N = 0, minIn = 0, maxIts = 1;
     int32_t *res = nullptr, *dd = nullptr; float *tcw = nullptr; uint8_t *inl = nullptr;
-    ~sgx_pnp_solver() { delete t; for (void *p : { (void *)res, (void *)dd, (void *)tcw, (void *)inl }) if (p) (void)hipFree(p); }
+    size_t dd_cap = 0;                                           // int32 values dd holds: the caller's draws of the longest call so far
+    SgxDevMem mem;
+    ~sgx_pnp_solver() { delete t; }
 };
 
 extern "C" int sgx_pnp_solver_create(int n, const float *p2d, const float *sigma2, const float *p3dw, const float *cam4, unsigned rand_seed, sgx_pnp_solver **out)
 {
+    if (out) *out = nullptr;
     if (!out || n < 0 || !cam4 || (n > 0 && (!p2d || !sigma2 || !p3dw))) return SGX_ERR_INVALID;
     sgx_pnp_solver *s = new sgx_pnp_solver;
     s->N = n;
-    const size_t m = (size_t)(n > 0 ? n : 1);
-    float *d2 = nullptr, *ds = nullptr, *d3 = nullptr;
-    bool ok = sgx_pnp_batch_create(1, n, &s->t) == SGX_OK && hipMalloc((void **)&s->res, 16) == hipSuccess && hipMalloc((void **)&s->tcw, 64) == hipSuccess &&
-              hipMalloc((void **)&s->inl, m) == hipSuccess && hipMalloc((void **)&d2, 8 * m) == hipSuccess && hipMalloc((void **)&ds, 4 * m) == hipSuccess &&
-              hipMalloc((void **)&d3, 12 * m) == hipSuccess;
-    if (ok && n > 0)
-        ok = hipMemcpy(d2, p2d, 8 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(ds, sigma2, 4 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(d3, p3dw, 12 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+    const size_t m = (size_t)n;
     const int32_t off[2] = { 0, n };
     const double defaults[6] = { 0.99, 8, 300, 4, 0.4f, 5.991f };                // SetRansacParameters() defaults (PnPsolver.h:67-68)
     const uint32_t seed = rand_seed;
-    if (ok) ok = sgx_pnp_batch_set_dev(s->t, 1, off, d2, ds, d3, cam4, defaults, &seed, nullptr) == SGX_OK;
-    for (void *p : { (void *)d2, (void *)ds, (void *)d3 }) if (p) (void)hipFree(p);
-    if (!ok) { delete s; return SGX_ERR_NOMEM; }
+    SgxDevMem staged;                                            // the correspondences on their way into the batch of one
+    float *d2 = nullptr, *ds = nullptr, *d3 = nullptr;
+    int rc;
+    if ((rc = sgx_pnp_batch_create(1, n, &s->t)) || (rc = s->mem.alloc(&s->res, 4)) || (rc = s->mem.alloc(&s->tcw, 16)) || (rc = s->mem.alloc(&s->inl, m)) ||
+        (rc = staged.upload(&d2, p2d, 2 * m)) || (rc = staged.upload(&ds, sigma2, m)) || (rc = staged.upload(&d3, p3dw, 3 * m)) ||
+        (rc = sgx_pnp_batch_set_dev(s->t, 1, off, d2, ds, d3, cam4, defaults, &seed, nullptr))) { delete s; return rc; }
     pnp_ransac(n, defaults, &s->minIn, &s->maxIts);
     *out = s;
     return SGX_OK;
@@ -293,9 +269,12 @@ extern "C" int sgx_pnp_solver_iterate(sgx_pnp_solver *s, int n_iterations, const
     int total = n_iterations > st[SGX_PNP_MAXITS] - st[SGX_PNP_ITS] ? n_iterations : st[SGX_PNP_MAXITS] - st[SGX_PNP_ITS];
     if (total < 0 || s->N < st[SGX_PNP_MININ]) total = 0;
     if (rand_draws && total > 0) {
-        if (s->dd) (void)hipFree(s->dd);
-        s->dd = nullptr;
-        if (hipMalloc((void **)&s->dd, 16 * (size_t)total) != hipSuccess) return SGX_ERR_NOMEM;
+        if (4 * (size_t)total > s->dd_cap) {
+            s->mem.release(s->dd); s->dd = nullptr; s->dd_cap = 0;
+            const int rc = s->mem.alloc(&s->dd, 4 * (size_t)total);
+            if (rc != SGX_OK) return rc;
+            s->dd_cap = 4 * (size_t)total;
+        }
         SGX_CHECK_HIP(hipMemcpy(s->dd, rand_draws, 16 * (size_t)total, hipMemcpyHostToDevice));
     }
     const int r = sgx_pnp_batch_iterate_dev(s->t, n_iterations, rand_draws && total > 0 ? s->dd : nullptr, 0, s->res, s->tcw, s->inl, nullptr);

@@ -1,6 +1,8 @@
 // sgx_sim3solver.cpp — host side of Sim3Solver (src/sg-slam/src/Sim3Solver.cc) behind the C ABI: the solver object (correspondences, RANSAC state, best model),
 // SetRansacParameters and the resumable iterate(); the hypotheses of a call run on the device (sgx_sim3solver_kernels.h).
 #include "sgx_sim3solver_kernels.h"
+#include "sgx_grand.h"
+#include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #ifdef SGX_DEBUG_TAPS
 #include "../../include/sgx_debug.h"      // test / tuning taps: compiled into tests/taps/libsgx_taps.so and the emulator only
@@ -18,16 +20,8 @@ struct sgx_sim3_solver {
     float *dX1 = nullptr, *dX2 = nullptr, *dP1 = nullptr, *dP2 = nullptr, *dE1 = nullptr, *dE2 = nullptr, *dHyp = nullptr; int *dDraws = nullptr, *dRes = nullptr; uint8_t *dInl = nullptr;
     float bestT12[16], bestR[9], bestt[3], bests = 1.f;
     // glibc rand() replica (TYPE_3: r[i] = r[i - 3] + r[i - 31]) for callers that do not pass their own rand() values
-    int32_t gr[34]; int gf = 3, gb = 0;
-    void gsrand(unsigned seed)
-    {
-        int32_t word = seed ? (int32_t)seed : 1; gr[0] = word;
-        for (int i = 1; i < 31; i++) { const long hi = word / 127773, lo = word % 127773; long w = 16807 * lo - 2836 * hi; if (w < 0) w += 2147483647; word = (int32_t)w; gr[i] = word; }
-        gf = 3; gb = 0;
-        for (int i = 0; i < 310; i++) { gr[gf] = (int32_t)((uint32_t)gr[gf] + (uint32_t)gr[gb]); gf = (gf + 1) % 31; gb = (gb + 1) % 31; }
-    }
-    int32_t grand() { gr[gf] = (int32_t)((uint32_t)gr[gf] + (uint32_t)gr[gb]); const int32_t o = (int32_t)(((uint32_t)gr[gf]) >> 1); gf = (gf + 1) % 31; gb = (gb + 1) % 31; return o; }
-    ~sgx_sim3_solver() { for (void *p : { (void *)dX1, (void *)dX2, (void *)dP1, (void *)dP2, (void *)dE1, (void *)dE2, (void *)dHyp, (void *)dDraws, (void *)dRes, (void *)dInl }) if (p) (void)hipFree(p); }
+    int32_t g[SGX_GRAND_WORDS];
+    SgxDevMem mem;
 };
 
 extern "C" int sgx_sim3_solver_set_ransac_parameters(sgx_sim3_solver *s, double probability, int min_inliers, int max_iterations)
@@ -50,27 +44,26 @@ extern "C" int sgx_sim3_solver_set_ransac_parameters(sgx_sim3_solver *s, double 
 extern "C" int sgx_sim3_solver_create(int n, const float *x3dc1, const float *x3dc2, const float *max_err1, const float *max_err2, const float *K1, const float *K2, int fix_scale,
                                       unsigned rand_seed, sgx_sim3_solver **out)
 {
+    if (out) *out = nullptr;
     if (!out || n < 0 || !K1 || !K2 || (n > 0 && (!x3dc1 || !x3dc2 || !max_err1 || !max_err2))) return SGX_ERR_INVALID;
     sgx_sim3_solver *s = new sgx_sim3_solver;
     s->N = n; s->fix_scale = fix_scale ? 1 : 0; memcpy(s->K1, K1, 16); memcpy(s->K2, K2, 16);
     memset(s->bestT12, 0, sizeof s->bestT12); memset(s->bestR, 0, sizeof s->bestR); memset(s->bestt, 0, sizeof s->bestt);
-    s->gsrand(rand_seed);
-    const size_t m = (size_t)(n > 0 ? n : 1);
+    sgx_gsrand(rand_seed, s->g);
+    const size_t m = (size_t)(n > 0 ? n : 1), k = (size_t)n;
     std::vector<float> p1(2 * m), p2(2 * m);
     for (int i = 0; i < n; i++) {                                // FromCameraToImage :407-425
         const float iz1 = 1 / x3dc1[3 * i + 2], iz2 = 1 / x3dc2[3 * i + 2];
         p1[2 * (size_t)i] = K1[0] * (x3dc1[3 * i] * iz1) + K1[2]; p1[2 * (size_t)i + 1] = K1[1] * (x3dc1[3 * i + 1] * iz1) + K1[3];
         p2[2 * (size_t)i] = K2[0] * (x3dc2[3 * i] * iz2) + K2[2]; p2[2 * (size_t)i + 1] = K2[1] * (x3dc2[3 * i + 1] * iz2) + K2[3];
     }
-    bool ok = hipMalloc((void **)&s->dX1, 12 * m) == hipSuccess && hipMalloc((void **)&s->dX2, 12 * m) == hipSuccess && hipMalloc((void **)&s->dP1, 8 * m) == hipSuccess &&
-              hipMalloc((void **)&s->dP2, 8 * m) == hipSuccess && hipMalloc((void **)&s->dE1, 4 * m) == hipSuccess && hipMalloc((void **)&s->dE2, 4 * m) == hipSuccess &&
-              hipMalloc((void **)&s->dHyp, sizeof(float) * SGX_S3_HYP * SGX_S3_MAXIT) == hipSuccess && hipMalloc((void **)&s->dDraws, 12 * SGX_S3_MAXIT) == hipSuccess &&
-              hipMalloc((void **)&s->dRes, 16) == hipSuccess && hipMalloc((void **)&s->dInl, m) == hipSuccess;
-    if (ok && n > 0)
-        ok = hipMemcpy(s->dX1, x3dc1, 12 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->dX2, x3dc2, 12 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(s->dP1, p1.data(), 8 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->dP2, p2.data(), 8 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(s->dE1, max_err1, 4 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->dE2, max_err2, 4 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { delete s; return SGX_ERR_NOMEM; }
+    SgxDevMem &d = s->mem;
+    int rc;
+    if ((rc = d.upload(&s->dX1, x3dc1, 3 * k)) || (rc = d.upload(&s->dX2, x3dc2, 3 * k)) || (rc = d.upload(&s->dP1, p1.data(), 2 * k)) ||
+        (rc = d.upload(&s->dP2, p2.data(), 2 * k)) || (rc = d.upload(&s->dE1, max_err1, k)) || (rc = d.upload(&s->dE2, max_err2, k)) ||
+        (rc = d.alloc(&s->dHyp, (size_t)SGX_S3_HYP * SGX_S3_MAXIT)) || (rc = d.alloc(&s->dDraws, 3 * SGX_S3_MAXIT)) || (rc = d.alloc(&s->dRes, 4)) || (rc = d.alloc(&s->dInl, m))) {
+        delete s; return rc;
+    }
     if (n > 0) sgx_sim3_solver_set_ransac_parameters(s, 0.99, 6, 300);             // the constructor ends with SetRansacParameters() (:110)
     *out = s;
     return SGX_OK;
@@ -92,8 +85,8 @@ extern "C" int sgx_sim3_solver_iterate(sgx_sim3_solver *s, int n_iterations, con
         std::vector<int32_t> draws((size_t)3 * n_it);
         // the reference draws from the process-global rand() as it goes; a caller that shares that stream passes the values, otherwise the solver's own replica supplies them.
         // Draws of iterations that are not run (early success) are handed back below.
-        int32_t gr0[34]; int gf0 = s->gf, gb0 = s->gb; memcpy(gr0, s->gr, sizeof gr0);
-        for (int i = 0; i < 3 * n_it; i++) draws[(size_t)i] = rand_draws ? rand_draws[3 * run_total + i] : s->grand();
+        int32_t g0[SGX_GRAND_WORDS]; memcpy(g0, s->g, sizeof g0);
+        for (int i = 0; i < 3 * n_it; i++) draws[(size_t)i] = rand_draws ? rand_draws[3 * run_total + i] : sgx_grand(s->g);
         SGX_CHECK_HIP(hipMemcpy(s->dDraws, draws.data(), draws.size() * 4, hipMemcpyHostToDevice));
         SgxS3Args A; memset(&A, 0, sizeof A);
         A.N = s->N; A.fix_scale = s->fix_scale; A.n_iter = n_it; A.min_inliers = s->minInliers; A.best_in = s->nBestInliers;
@@ -105,8 +98,8 @@ extern "C" int sgx_sim3_solver_iterate(sgx_sim3_solver *s, int n_iterations, con
         SGX_CHECK_HIP(hipMemcpy(res, s->dRes, 16, hipMemcpyDeviceToHost));
         const int fnd = res[0], run = res[1], best_h = res[2];
         if (!rand_draws && run < n_it) {                                             // give back the draws of the iterations that did not run
-            memcpy(s->gr, gr0, sizeof gr0); s->gf = gf0; s->gb = gb0;
-            for (int i = 0; i < 3 * run; i++) (void)s->grand();
+            memcpy(s->g, g0, sizeof g0);
+            for (int i = 0; i < 3 * run; i++) (void)sgx_grand(s->g);
         }
         s->nIterations += run; run_total += run;
         if (best_h >= 0) {

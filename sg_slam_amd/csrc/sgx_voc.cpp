@@ -3,6 +3,7 @@
 // ScoringObject.cpp, FORB.cpp}; callers Frame::ComputeBoW (Frame.cc:422-429), KeyFrame::ComputeBoW (KeyFrame.cc:60-69), System::System (System.cc:65-80).
 #include "sgx_voc_kernels.h"
 #include "sgx_stage.h"
+#include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #ifdef SGX_DEBUG_TAPS
 #include "../../include/sgx_debug.h"      // test / tuning taps: compiled into tests/taps/libsgx_taps.so and the emulator only
@@ -19,20 +20,12 @@ struct sgx_voc {
     int k = 0, L = 0, scoring = 0, weighting = 0, nnodes = 0, nwords = 0;
     bool empty = true;
     SgxVocDev dev{};
-    std::vector<void *> allocs;
-    ~sgx_voc() { for (void *p : allocs) (void)hipFree(p); }
-    template <class T> int upload(const std::vector<T> &h, const T **out)
-    {
-        void *p = nullptr;
-        if (hipMalloc(&p, (h.size() ? h.size() : 1) * sizeof(T)) != hipSuccess) return SGX_ERR_NOMEM;
-        allocs.push_back(p);
-        if (!h.empty() && hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return SGX_ERR_DEVICE;
-        *out = (const T *)p; return SGX_OK;
-    }
+    SgxDevMem mem;
 };
 
 extern "C" int sgx_voc_create(int k, int L, int scoring, int weighting, int nnodes, const int32_t *parent, const uint8_t *desc32, const double *weight, const uint8_t *is_leaf, sgx_voc **out)
 {
+    if (out) *out = nullptr;
     if (!out || k < 0 || k > 20 || L < 1 || L > 10 || scoring < 0 || scoring > 5 || weighting < 0 || weighting > 3 || nnodes < 1 || (nnodes > 1 && (!parent || !desc32 || !weight || !is_leaf)))
         return SGX_ERR_INVALID;                                   // the header checks of loadFromTextFile (TemplatedVocabulary.h:1373-1377)
     for (int i = 1; i < nnodes; i++) if (parent[i] < 0 || parent[i] >= i) return SGX_ERR_INVALID;      // a node follows its parent in both file formats
@@ -50,8 +43,8 @@ extern "C" int sgx_voc_create(int k, int L, int scoring, int weighting, int nnod
     }
     v->empty = v->nwords == 0 || cstart[1] == 0;
     int rc;
-    if ((rc = v->upload(cstart, &v->dev.child_start)) != SGX_OK || (rc = v->upload(cidx, &v->dev.child_idx)) != SGX_OK || (rc = v->upload(word, &v->dev.word_id)) != SGX_OK ||
-        (rc = v->upload(d, &v->dev.desc)) != SGX_OK || (rc = v->upload(w, &v->dev.weight)) != SGX_OK) { delete v; return rc; }
+    if ((rc = v->mem.upload(&v->dev.child_start, cstart)) || (rc = v->mem.upload(&v->dev.child_idx, cidx)) || (rc = v->mem.upload(&v->dev.word_id, word)) ||
+        (rc = v->mem.upload(&v->dev.desc, d)) || (rc = v->mem.upload(&v->dev.weight, w))) { delete v; return rc; }
     v->dev.L = L; v->dev.nnodes = nnodes;
     *out = v;
     return SGX_OK;

@@ -134,6 +134,20 @@ def run_case(lib, name):
     return got
 
 
+def check_regrow_carries_replica(lib):
+    """one Initializer (12 keys in frame 1, 8 iterations, srand(5)) under its own rand() replica: a second frame of 12 keys, then one of 40, for which the batch of one
+    behind it is rebuilt.  The replica's state moves into the new batch, so the second call draws glibc's values 8 x its .. 16 x its - 1"""
+    its = 8
+    a = make_scene(seed=31, n=12, noise=0.2); b = make_scene(seed=31, n=12, noise=0.2, extra2=28)
+    assert len(a[1]) == 12 and len(b[1]) == 40 and (a[0] == b[0]).all()
+    d = glibc_rand(5, 16 * its)
+    R = ref.InitializerRef(a[0], CAM, 1.0, its)
+    S = Initializer(a[0], CAM, 1.0, its, rand_seed=5, lib=lib)
+    assert_same(S.Initialize(a[1], a[2]), R.initialize(a[1], a[2], d[:8 * its]), 'regrow: 12 keys')
+    assert_same(S.Initialize(b[1], b[2]), R.initialize(b[1], b[2], d[8 * its:]), 'regrow: 40 keys')
+    S.close()
+
+
 def check_batch_equals_single(lib, names, caller_draws=False):
     """the cases `names` (same iterations) in one batch == one Initializer each, with their own rand() replicas or with each pair's libc values passed in"""
     cs = [next(c for c in CASES if c[0] == n) for n in names]

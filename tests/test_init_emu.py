@@ -93,6 +93,10 @@ def test_replica_draws_equal_libc_rand(emu):
     assert (ic.glibc_rand(0, 8) == ic.glibc_rand(1, 8)).all()
 
 
+def test_second_frame_with_more_keys_continues_the_replica(emu):
+    ic.check_regrow_carries_replica(emu)
+
+
 def test_draw_sets_are_the_swap_and_pop_of_the_reference():
     """RandomInt(0, size - 1) over the shrinking vAvailableIndices with swap-with-back removal, against a literal list implementation"""
     d = ic.glibc_rand(5, 8 * 50).reshape(50, 8)

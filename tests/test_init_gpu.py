@@ -21,6 +21,10 @@ def test_device_batch_with_caller_draws_equals_single(gpulib):
     ic.check_batch_equals_single(gpulib, [c[0] for c in ic.CASES if c[2] == 200][:8], caller_draws=True)
 
 
+def test_device_second_frame_with_more_keys_continues_the_replica(gpulib):
+    ic.check_regrow_carries_replica(gpulib)
+
+
 def test_device_call_longer_than_one_chunk(gpulib):
     """300 iterations: two launches of the hypothesis kernels"""
     c = next(c for c in ic.CASES if c[0] == 'general_300_its300'); assert c[2] > 256
