@@ -427,6 +427,73 @@ int sgx_objdb_add(sgx_objdb *db, const sgx_semantic_object *obj, int32_t *object
 int sgx_objdb_size(const sgx_objdb *db);                                      /* number of objects (mvSemanticObject.size()) */
 int sgx_objdb_get(const sgx_objdb *db, int index, sgx_semantic_object *out);  /* mvSemanticObject[index] */
 
+/* ---- PointCloudMapping (src/sg-slam/include/PointcloudMapping.h, src/sg-slam/src/PointcloudMapping.cc) -----------------------------------------------------------
+ * The cloud of a keyframe as PointCloudMapping::generatePointCloud / generatePointCloudForDyamic (:69-194) build it and MapViewer filters it (:252-286 voxel_local /
+ * sor_local, :332-338 voxel_global / sor_global on temp_globalMap): every pixel of the depth image as a coloured point, pcl::VoxelGrid<PointXYZRGB> with leaf L on all
+ * three axes, pcl::StatisticalOutlierRemoval (mean_k, stddev_mul), the axis map slam_to_ros_mode_transform (:364-375).  PCL is restated from its published sources
+ * (tests/cloud_ref.py), unpinned.
+ * Generate: the cloud has width * height points, index m * width + n, every one x = y = z = 0, r = g = b = 0, a = 255 (PCL's default point).  A pixel is skipped when
+ * d < min || d > max || isnan(d), and, when consider_dynamic and the image's have_dynamic flag are set, when it lies in a dynamic rect: n > int(x) && n < int(x + w) &&
+ * m > int(y) && m < int(y + h) (:449-458; float sum, C truncation; a value no int holds converts to the nearest int, NaN to 0).  Any other pixel gets z = d,
+ * x = (n - cx) * d / fx, y = (m - cy) * d / fy in float and r = color[3n + 2], g = color[3n + 1], b = color[3n].  A skipped pixel is NOT dropped: it stays a point at
+ * the camera origin with colour 0 and goes through the filters, as in the reference.
+ * SGX_CLOUD_LOCAL (localMap): the filters run in the camera frame, then every surviving point becomes (z, -x, -y).  SGX_CLOUD_WORLD (temp_globalMap): every point,
+ * the origin points included, becomes (float)(((T[r][0]*x + T[r][1]*y) + T[r][2]*z) + T[r][3]) in double, then (z, -x, -y), then the filters run.
+ * VoxelGrid: inv = 1.0f / L; min_p, max_p the extremes over the finite points; dx = (int64)((max_p[0] - min_p[0]) * inv) + 1 (dy, dz alike); min_b = (int)floor(min_p *
+ * inv), max_b alike, div = max_b - min_b + 1; ijk = (int)(floor(p * inv) - (float)min_b), idx = ijk0 + ijk1 * div0 + ijk2 * div0 * div1; one point per occupied idx
+ * in ascending idx: float running sums of x, y, z, (float)r, (float)g, (float)b, (float)a over the voxel's points, xyz = sum / (float)n, channel = (uint32)(sum /
+ * (float)n).  StatisticalOutlierRemoval on the voxel cloud as for sgx_obj3d: a point goes when its mean distance to its mean_k nearest neighbours is > thr.
+ * Defined cases:
+ *  1. fewer than mean_k + 1 voxel points (the reference reads a stale neighbour list): no points, flags has SGX_CLOUD_FEW_POINTS;
+ *  2. dx * dy * dz > INT32_MAX (PCL warns and passes the cloud through unfiltered), or |min_p * inv| or |max_p * inv| >= 2^31, or div0 * div1 * div2 > INT32_MAX (PCL's
+ *     int index overflows): no points, flags has SGX_CLOUD_LEAF_TOO_SMALL, and the call succeeds: a batch does not fail because of one keyframe;
+ *  3. the points of a voxel are summed in ascending point index (PCL sorts (idx, point) with an unstable sort);
+ *  4. a zero that the axis map produces is written as +0;
+ *  5. a point that is not finite (a Twc that is not finite) joins neither the extremes nor a voxel, as in PCL.
+ * SGX_ERR_INVALID: mean_k < 1, a leaf that is not finite or <= 0, depth bounds that are not finite, more than max_boxes rects or a NaN in Twc (both in sgx_cloud_build,
+ * which sees them; sgx_cloud_build_batch_dev reads nothing back: it takes min(n_boxes, max_boxes) rects, and a NaN in Twc gives case 5).
+ * The result record: n_points (points written), n_pixels_used (pixels not skipped), n_voxels (voxel points before the outlier filter), flags, mean and thr of the
+ * outlier filter, larger_window_points (voxel points whose neighbour search needed more than the first cell window: an implementation figure, equal between the device
+ * and the emulator). */
+#define SGX_CLOUD_LOCAL 0
+#define SGX_CLOUD_WORLD 1
+#define SGX_CLOUD_FEW_POINTS 1
+#define SGX_CLOUD_LEAF_TOO_SMALL 2
+#define SGX_CLOUD_MAX_BOXES 128
+typedef struct sgx_cloud_params {
+    double sor_stddev_mul;                                  /* PointCloudMapping.Sor_Local_StddevMulThresh / Sor_Global_StddevMulThresh */
+    int32_t sor_mean_k;                                     /* PointCloudMapping.Sor_Local_MeanK / Sor_Global_MeanK */
+    int32_t consider_dynamic;                               /* PointCloudMapping.is_map_construction_consider_dynamic */
+    float voxel_leaf_size;                                  /* PointCloudMapping.Voxel_Local_LeafSize / Voxel_Global_LeafSize */
+    float camera_valid_depth_min, camera_valid_depth_max;   /* PointCloudMapping.camera_valid_depth_Min / Max */
+    int32_t reserved;
+} sgx_cloud_params;
+typedef struct sgx_cloud_point { float x, y, z; uint32_t rgba; } sgx_cloud_point;      /* rgba = a << 24 | r << 16 | g << 8 | b: PCL's PointXYZRGB, the x y z rgb fields of a PointCloud2 */
+typedef struct sgx_cloud_result {
+    int32_t n_points, n_pixels_used, n_voxels, flags, larger_window_points, reserved;
+    double mean, thr;
+} sgx_cloud_result;
+typedef struct sgx_cloud sgx_cloud;
+/* width x height images (at most 2^20 pixels), at most max_images keyframes per batch and max_boxes <= SGX_CLOUD_MAX_BOXES dynamic rects per keyframe; mode =
+ * SGX_CLOUD_LOCAL or SGX_CLOUD_WORLD.  The workspace is 76 bytes per pixel and keyframe.  A failed create clears *out and returns the status that occurred. */
+int sgx_cloud_create(int width, int height, int max_images, int max_boxes, int mode, const sgx_cloud_params *params, sgx_cloud **out);
+void sgx_cloud_destroy(sgx_cloud *h);
+/* n_images keyframes in one launch sequence, asynchronous on `stream`, no read-back: depth_dev = n_images x height x depth_pitch floats (metres, as mImDep),
+ * color_dev = n_images x height x color_pitch bytes (3 bytes per pixel in mImRGB's order), cam4 = fx, fy, cx, cy (host), twc_dev = n_images x 16 doubles (Twc
+ * row-major; may be NULL in SGX_CLOUD_LOCAL), boxes_dev = n_images x max_boxes x (x, y, w, h) floats, n_boxes_dev and have_dynamic_dev = n_images int32
+ * (mvPotentialDynamicBorderForMapping, its size, mbHaveDynamicObjectForMapping; all three may be NULL: no dynamic region), points_dev = max_images x width * height
+ * records (keyframe i writes its n_points records from i * width * height on), results_dev = n_images records.  A handle serves one batch at a time. */
+int sgx_cloud_build_batch_dev(sgx_cloud *h, const float *depth_dev, int depth_pitch, const uint8_t *color_dev, int color_pitch, int n_images, const float *cam4,
+                              const double *twc_dev, const float *boxes_dev, const int32_t *n_boxes_dev, const int32_t *have_dynamic_dev, sgx_cloud_point *points_dev,
+                              sgx_cloud_result *results_dev, void *stream);
+/* one keyframe from host memory (tight images; twc = 16 doubles, may be NULL in SGX_CLOUD_LOCAL; boxes = n_boxes x 4 floats): the record, and its n_points points
+ * into points (SGX_ERR_OVERFLOW when cap is smaller; the record is written all the same).  Synchronous. */
+int sgx_cloud_build(sgx_cloud *h, const float *depth, const uint8_t *color, const float *cam4, const double *twc, const float *boxes, int n_boxes, int have_dynamic,
+                    sgx_cloud_point *points, int cap, sgx_cloud_result *result);
+/* camera_to_map_tf of MapViewer (:254-265), host code: tcw = the keyframe's float pose Tcw (16 floats, row-major).  Rwc = Rcw^T, twc = -Rwc * tcw rounded to float
+ * from a double product (cv::gemm); Q = Eigen::Quaterniond(Rwc as double); origin = (twc[2], -twc[0], -twc[1]); rotation = (Q.z, -Q.x, -Q.y, Q.w) in tf's x, y, z, w. */
+int sgx_cloud_camera_to_map_tf(const float *tcw, double origin[3], double rotation[4]);
+
 /* ---- ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (src/sg-slam/include/ORBVocabulary.h:31-32) ----------------------------------------------
  * The bag-of-words transform behind Frame::ComputeBoW (src/sg-slam/src/Frame.cc:422-429) and KeyFrame::ComputeBoW (src/sg-slam/src/KeyFrame.cc:60-69):
  *     mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4)          src/sg-slam/Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1139-1206

@@ -38,6 +38,10 @@ int sgx_pnp_debug_betas(int which, const double *L, const double *rho, double *b
 /* test tap: the per-point state of job `job` of the handle's last batch, over its *n crop points in the reference's order (ascending flat index): kept[i] = the
  * outlier filter kept point i, labels[i] = the smallest point of its component (-1 when the point was removed).  Synchronises; SGX_ERR_OVERFLOW when *n > cap. */
 int sgx_obj3d_debug_read(sgx_obj3d *h, int job, uint8_t *kept, int32_t *labels, int cap, int *n);
+/* test tap: keyframe `image` of the handle's last batch before the outlier filter: its *n voxel points in ascending idx (mode's frame: camera axes in SGX_CLOUD_LOCAL,
+ * ROS axes in SGX_CLOUD_WORLD), dist[i] = the mean distance of point i to its mean_k nearest neighbours, kept[i] = the filter kept it (each destination may be NULL).
+ * Synchronises; SGX_ERR_OVERFLOW when *n > cap. */
+int sgx_cloud_debug_read(sgx_cloud *h, int image, sgx_cloud_point *voxels, float *dist, uint8_t *kept, int cap, int *n);
 int sgx_debug_corun_bf16(int blocks, int iters, int launches, void *stream);      /* test tap: `launches` launches of a kernel that only issues bf16 matrix products, asynchronous on `stream` (co-runner of the packed-fp32 regression test) */
 /* test tap: DetectionOutput + detect() filtering alone on caller-supplied head outputs (host arrays: loc batch x num_priors x 4, conf batch x num_priors x num_class) */
 int sgx_det_debug_detection_output(sgx_det *h, const float *loc, const float *conf, int batch, sgx_det_result *results);

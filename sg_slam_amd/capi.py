@@ -72,6 +72,19 @@ class SemanticObjectRecord(C.Structure):
     _fields_ = [('class_id', C.c_int32), ('object_id', C.c_int32), ('prob', C.c_float), ('centroid', C.c_float * 3), ('size', C.c_float * 3)]
 
 
+class CloudParams(C.Structure):
+    _fields_ = [('sor_stddev_mul', C.c_double), ('sor_mean_k', C.c_int32), ('consider_dynamic', C.c_int32), ('voxel_leaf_size', C.c_float),
+                ('camera_valid_depth_min', C.c_float), ('camera_valid_depth_max', C.c_float), ('reserved', C.c_int32)]
+
+
+CLOUD_POINT_DTYPE = np.dtype([('x', 'f4'), ('y', 'f4'), ('z', 'f4'), ('rgba', 'u4')])   # sgx_cloud_point, 16 B: PCL's PointXYZRGB packing
+CLOUD_RESULT_DTYPE = np.dtype([('n_points', 'i4'), ('n_pixels_used', 'i4'), ('n_voxels', 'i4'), ('flags', 'i4'), ('larger_window_points', 'i4'), ('reserved', 'i4'),
+                               ('mean', 'f8'), ('thr', 'f8')])   # sgx_cloud_result, 40 B
+SGX_CLOUD_LOCAL, SGX_CLOUD_WORLD = 0, 1
+SGX_CLOUD_FEW_POINTS, SGX_CLOUD_LEAF_TOO_SMALL = 1, 2
+SGX_CLOUD_MAX_BOXES = 128
+
+
 class InitReport(C.Structure):
     _fields_ = [('SH', C.c_float), ('SF', C.c_float), ('RH', C.c_float), ('model', C.c_int32), ('n_matches', C.c_int32), ('n_inliers_h', C.c_int32),
                 ('n_inliers_f', C.c_int32), ('n_hyp', C.c_int32), ('best_hyp', C.c_int32), ('n_good', C.c_int32 * 8), ('cos_parallax', C.c_float * 8),
@@ -122,6 +135,7 @@ SYMBOLS = [
     'sgx_init_batch_destroy', 'sgx_orb_detect_batch_dev', 'sgx_orb_describe_batch_dev', 'sgx_frame_compact_keys_src_batch_dev',
     'sgx_voc_bow_batch_dev', 'sgx_kfdb_create', 'sgx_kfdb_destroy', 'sgx_kfdb_size', 'sgx_kfdb_add', 'sgx_kfdb_erase', 'sgx_kfdb_clear', 'sgx_kfdb_set_covisibility',
     'sgx_kfdb_slots', 'sgx_kfdb_detect_relocalization_candidates', 'sgx_kfdb_detect_loop_candidates', 'sgx_kfdb_min_score', 'sgx_kfdb_detect_batch_dev',
+    'sgx_cloud_create', 'sgx_cloud_destroy', 'sgx_cloud_build_batch_dev', 'sgx_cloud_build', 'sgx_cloud_camera_to_map_tf',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -131,7 +145,7 @@ TAP_SYMBOLS = [
     'sgx_det_debug_set_block_fusion', 'sgx_det_debug_set_irb', 'sgx_det_debug_set_gemm', 'sgx_det_debug_time_ops', 'sgx_det_debug_run_step', 'sgx_flow_debug_read_level',
     'sgx_flow_debug_level_size', 'sgx_flow_debug_read_slot', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas', 'sgx_obj3d_debug_read',
     'sgx_tracker_debug_set_describe_early', 'sgx_tracker_debug_set_boxes', 'sgx_tracker_debug_sync_trace', 'sgx_tracker_debug_fail_after',
-    'sgx_debug_devmem_fail_after',
+    'sgx_debug_devmem_fail_after', 'sgx_cloud_debug_read',
 ]
 
 
@@ -270,6 +284,11 @@ class SgxLib:
         d.sgx_objdb_add.argtypes = [vp, C.POINTER(SemanticObjectRecord), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         d.sgx_objdb_size.argtypes = [vp]
         d.sgx_objdb_get.argtypes = [vp, C.c_int, C.POINTER(SemanticObjectRecord)]
+        d.sgx_cloud_create.argtypes = [C.c_int] * 5 + [C.POINTER(CloudParams), C.POINTER(vp)]
+        d.sgx_cloud_destroy.argtypes = [vp]; d.sgx_cloud_destroy.restype = None
+        d.sgx_cloud_build_batch_dev.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int] + [vp] * 8
+        d.sgx_cloud_build.argtypes = [vp] * 6 + [C.c_int, C.c_int, vp, C.c_int, vp]
+        d.sgx_cloud_camera_to_map_tf.argtypes = [vp, vp, vp]
         d.sgx_mappoint_update_normal_and_depth.argtypes = [C.c_int] + [vp] * 6 + [C.c_int, vp, vp, vp]
         d.sgx_mappoint_distinctive_descriptors.argtypes = [C.c_int, vp, vp, vp, vp]
         d.sgx_triangulate_new_map_points.argtypes = [C.c_int, vp] + [C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 5 + [vp, vp, vp, C.c_int, vp, vp, vp]
@@ -335,6 +354,8 @@ class SgxLib:
                 d.sgx_tracker_debug_fail_after.argtypes = [C.c_int]
             if hasattr(d, 'sgx_debug_devmem_fail_after'):
                 d.sgx_debug_devmem_fail_after.argtypes = [C.c_int]
+            if hasattr(d, 'sgx_cloud_debug_read'):
+                d.sgx_cloud_debug_read.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
 
     def tap(self, name):
         """a test / tuning tap entry (include/sgx_debug.h); the product library has none"""

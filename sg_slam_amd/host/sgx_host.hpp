@@ -659,6 +659,38 @@ private:
     sgx_obj3d *h_ = nullptr; float cam_[4];
 };
 
+// PointCloudMapping (PointcloudMapping.h): the filtered local-map cloud of a keyframe (generatePointCloud*, voxel_local, sor_local, slam_to_ros_mode_transform) and
+// camera_to_map_tf, as MapViewer publishes them for octomap_server; thin over sgx_cloud_*.  The semantic objects of the keyframe are Detector3D::Detect's (above).
+struct LocalMap { std::vector<sgx_cloud_point> points; sgx_cloud_result record; double origin[3], rotation[4]; };     // rotation = x, y, z, w
+class PointCloudMapping {
+public:
+    // the reference's constructor arguments that the local map reads (PointcloudMapping.h) plus the image size and the camera (fx, fy, cx, cy)
+    PointCloudMapping(bool is_map_construction_consider_dynamic_, float camera_valid_depth_Min_, float camera_valid_depth_Max_, int Sor_Local_MeanK_,
+                      double Sor_Local_StddevMulThresh_, float Voxel_Local_LeafSize_, int width, int height, const float cam[4], int max_boxes = SGX_CLOUD_MAX_BOXES)
+        : N_(width * height)
+    {
+        sgx_cloud_params p; std::memset(&p, 0, sizeof p);
+        p.sor_stddev_mul = Sor_Local_StddevMulThresh_; p.sor_mean_k = Sor_Local_MeanK_; p.consider_dynamic = is_map_construction_consider_dynamic_ ? 1 : 0;
+        p.voxel_leaf_size = Voxel_Local_LeafSize_; p.camera_valid_depth_min = camera_valid_depth_Min_; p.camera_valid_depth_max = camera_valid_depth_Max_;
+        for (int i = 0; i < 4; i++) cam_[i] = cam[i];
+        check(sgx_cloud_create(width, height, 1, max_boxes, SGX_CLOUD_LOCAL, &p, &h_), "sgx_cloud_create");
+    }
+    ~PointCloudMapping() { if (h_) sgx_cloud_destroy(h_); }
+    PointCloudMapping(const PointCloudMapping &) = delete; PointCloudMapping &operator=(const PointCloudMapping &) = delete;
+    // void insertKeyFrame(KeyFrame*, cv::Mat &color, cv::Mat &depth) and the MapViewer pass over it: color = mImRGB (height x width x 3 bytes, tight), depth = mImDep
+    // (float metres), Tcw = the keyframe's float pose (row-major), boxes = mvPotentialDynamicBorderForMapping as (x, y, w, h), haveDynamic = mbHaveDynamicObjectForMapping
+    void insertKeyFrame(const uint8_t *color, const float *depth, const float Tcw[16], const std::vector<float> &boxes, bool haveDynamic, LocalMap &out)
+    {
+        out.points.resize((size_t)N_);
+        check(sgx_cloud_build(h_, depth, color, cam_, nullptr, boxes.data(), (int)(boxes.size() / 4), haveDynamic ? 1 : 0, out.points.data(), N_, &out.record), "sgx_cloud_build");
+        out.points.resize((size_t)out.record.n_points);
+        check(sgx_cloud_camera_to_map_tf(Tcw, out.origin, out.rotation), "sgx_cloud_camera_to_map_tf");
+    }
+    sgx_cloud *handle() { return h_; }
+private:
+    sgx_cloud *h_ = nullptr; int N_; float cam_[4];
+};
+
 // cv::undistortPoints(points, out, K, D, noArray(), K) as Frame::UndistortKeyPoints calls it (Frame.cc:654-684), and Frame::ComputeImageBounds (:686-714);
 // K4 = fx, fy, cx, cy, distCoef = 4, 5 or 8 coefficients.  Points are (x, y) pairs.
 inline std::vector<float> UndistortPoints(const std::vector<float> &points, const float K4[4], const std::vector<float> &distCoef)

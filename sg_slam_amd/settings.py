@@ -52,3 +52,18 @@ def load_mapping(path):
                 EuclideanClusterMaxSize=int(d('EuclideanClusterMaxSize')), DetectSimilarCompareRatio=float(np.float32(d('DetectSimilarCompareRatio'))),
                 camera_valid_depth_Min=float(np.float32(float(kv['PointCloudMapping.camera_valid_depth_Min']))),
                 camera_valid_depth_Max=float(np.float32(float(kv['PointCloudMapping.camera_valid_depth_Max']))))
+
+
+def load_pointcloud_mapping(path):
+    """The PointCloudMapping.* parameters System::System reads for the map cloud (src/sg-slam/src/PointcloudMapping.cc): the three switches
+    (is_map_construction_consider_dynamic, is_octo_semantic_map_construction, is_global_pc_reconstruction), the valid depth range, and mean_k, stddev_mul (double) and
+    the voxel leaf (float) of the local and of the global filter.  A missing key raises KeyError: the reference has no defaults for them."""
+    kv = parse(path)
+    d = lambda k: float(kv['PointCloudMapping.' + k])
+    out = {k: int(d(k)) for k in ('is_map_construction_consider_dynamic', 'is_octo_semantic_map_construction', 'is_global_pc_reconstruction')}
+    for k in ('camera_valid_depth_Min', 'camera_valid_depth_Max'):
+        out[k] = float(np.float32(d(k)))
+    for w in ('Local', 'Global'):
+        out['Sor_%s_MeanK' % w] = int(d('Sor_%s_MeanK' % w)); out['Sor_%s_StddevMulThresh' % w] = d('Sor_%s_StddevMulThresh' % w)
+        out['Voxel_%s_LeafSize' % w] = float(np.float32(d('Voxel_%s_LeafSize' % w)))
+    return out
