@@ -902,6 +902,34 @@ int sgx_tracker_frame_dev(sgx_tracker *t, const int32_t **d_n, const sgx_keypoin
 int sgx_tracker_frame_keys_un_dev(sgx_tracker *t, const sgx_keypoint **d_keys_un);
 sgx_orb *sgx_tracker_extractor(sgx_tracker *t);
 
+/* ---- Frame::ComputeStereoMatches (Frame.cc:716-890): the stereo constructor's mvuRight / mvDepth from a rectified pair ---------------------------------------------
+ * For every left keypoint: the right keypoint of smallest descriptor distance on its row band (+-2 * scale rows, +-1 octave, uL - maxD <= uR <= uL, distance below 75),
+ * an 11 x 11 SAD window slid over +-5 px in both pyramids at the left keypoint's level, a parabola through the best offset, depth = bf / disparity, and the cut of
+ * every match whose SAD is at least 1.5 * 1.4 times the median.  Results equal the reference bit for bit; three cases it leaves undefined are defined:
+ * mb = bf / fx (read before it is assigned there), so maxD = bf / mb; a window or a table row outside the image gives no match; no accepted match, nothing to cut.
+ * The handle owns the workspace for max_batch pairs of extractors with the geometry of `geometry_of` (image size, levels, scale factor, nfeatures); nothing is
+ * allocated per call. */
+typedef struct sgx_stereo sgx_stereo;
+int sgx_stereo_create(const sgx_orb *geometry_of, int max_batch, sgx_stereo **out);      /* *out is NULL after a failed call */
+void sgx_stereo_destroy(sgx_stereo *h);
+/* `batch` pairs on `stream`, asynchronous, nothing read back.  The pyramids are those of the LAST sgx_orb_extract_batch_dev or sgx_orb_detect_batch_dev of each
+ * extractor handle, which must have run on the same stream on the same d_gray / pitch: pair f reads frame left_first_frame + f of orb_left and frame
+ * right_first_frame + f of orb_right.  orb_left == orb_right is allowed and is the fast form: one extraction of 2 * batch images, the left ones first, and
+ * right_first_frame = batch (d_gray_right = d_gray_left; the right key, descriptor and count pointers are those of frame `batch`).  cap: slots per frame of every
+ * key / descriptor / output array = sgx_orb_keypoint_capacity of the extractors.  d_uright / d_zdepth: batch x cap as sgx_frame_stereo_from_rgbd_batch_dev writes
+ * them, -1 where there is no match; d_nmatched (optional): matches kept per pair.  SGX_ERR_INVALID, with nothing enqueued: a NULL pointer, batch > max_batch, another
+ * cap, an extractor of another geometry, an extractor without a pyramid for first_frame + batch frames or with one of another image. */
+int sgx_stereo_match_batch_dev(sgx_stereo *h, int batch,
+                               sgx_orb *orb_left, int left_first_frame, const uint8_t *d_gray_left, int pitch_left,
+                               sgx_orb *orb_right, int right_first_frame, const uint8_t *d_gray_right, int pitch_right,
+                               int cap, const sgx_keypoint *d_keys_left, const uint8_t *d_desc_left, const int32_t *d_n_left,
+                               const sgx_keypoint *d_keys_right, const uint8_t *d_desc_right, const int32_t *d_n_right,
+                               float fx, float bf, float *d_uright, float *d_zdepth, int32_t *d_nmatched /* may be NULL */, void *stream);
+/* one pair from host memory, synchronous, as sgx_orb_extract is: orb_left and orb_right are two handles (the reference's two extractors) whose last call was
+ * sgx_orb_extract on the left and on the right image; keys / descriptors are what those calls returned.  uright / zdepth: n_left floats each. */
+int sgx_stereo_match(sgx_stereo *h, sgx_orb *orb_left, sgx_orb *orb_right, const sgx_keypoint *keys_left, const uint8_t *desc_left, int n_left,
+                     const sgx_keypoint *keys_right, const uint8_t *desc_right, int n_right, float fx, float bf, float *uright, float *zdepth, int *nmatched /* may be NULL */);
+
 /* ---- per-kernel HIP-event timing (process-wide) ---------------------------------------------------
  * When enabled, every batched entry point records a hipEvent pair on the caller's stream around each
  * kernel launch.  sgx_profile_read sums the elapsed times per kernel class since the last reset

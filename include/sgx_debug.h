@@ -89,6 +89,12 @@ int sgx_tracker_debug_fail_after(int n);
  * allocation with SGX_ERR_NOMEM, the copy of a table or input uploaded at creation with SGX_ERR_DEVICE.  n <= 0 turns it off.  Returns the status that the previous
  * arming delivered, SGX_OK when it never fired. */
 int sgx_debug_devmem_fail_after(int n);
+/* test tap: left frame `frame` of the handle's last sgx_stereo_match_batch_dev, one entry per keypoint slot (cap of them; each destination may be NULL): bestIdxR and
+ * the Hamming bestDist of the row-table search (0 / 100 where it found none), the exit the keypoint took (-1 no keypoint, 0 no candidates on its row, 1 maxU < 0,
+ * 2 bestDist >= 75, 3 the reference's border test, 4 a window outside its level, 5 bestincR at the end of the range, 6 deltaR outside [-1, 1], 7 disparity outside
+ * [0, maxD), 8 accepted, 9 accepted with the disparity == 0 clamp, 10 accepted and reset by the median cut), bestincR (0 where the window search did not run) and the
+ * 11 SAD values (cap x 11, -1 where it did not run).  Synchronises. */
+int sgx_stereo_debug_read(sgx_stereo *h, int frame, int32_t *best_idx, int32_t *best_dist, int32_t *exit_code, int32_t *best_inc, int32_t *sads);
 
 #ifdef __cplusplus
 }

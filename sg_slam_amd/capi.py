@@ -136,6 +136,7 @@ SYMBOLS = [
     'sgx_voc_bow_batch_dev', 'sgx_kfdb_create', 'sgx_kfdb_destroy', 'sgx_kfdb_size', 'sgx_kfdb_add', 'sgx_kfdb_erase', 'sgx_kfdb_clear', 'sgx_kfdb_set_covisibility',
     'sgx_kfdb_slots', 'sgx_kfdb_detect_relocalization_candidates', 'sgx_kfdb_detect_loop_candidates', 'sgx_kfdb_min_score', 'sgx_kfdb_detect_batch_dev',
     'sgx_cloud_create', 'sgx_cloud_destroy', 'sgx_cloud_build_batch_dev', 'sgx_cloud_build', 'sgx_cloud_camera_to_map_tf',
+    'sgx_stereo_create', 'sgx_stereo_destroy', 'sgx_stereo_match_batch_dev', 'sgx_stereo_match',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -145,7 +146,7 @@ TAP_SYMBOLS = [
     'sgx_det_debug_set_block_fusion', 'sgx_det_debug_set_irb', 'sgx_det_debug_set_gemm', 'sgx_det_debug_time_ops', 'sgx_det_debug_run_step', 'sgx_flow_debug_read_level',
     'sgx_flow_debug_level_size', 'sgx_flow_debug_read_slot', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas', 'sgx_obj3d_debug_read',
     'sgx_tracker_debug_set_describe_early', 'sgx_tracker_debug_set_boxes', 'sgx_tracker_debug_sync_trace', 'sgx_tracker_debug_fail_after',
-    'sgx_debug_devmem_fail_after', 'sgx_cloud_debug_read',
+    'sgx_debug_devmem_fail_after', 'sgx_cloud_debug_read', 'sgx_stereo_debug_read',
 ]
 
 
@@ -289,6 +290,10 @@ class SgxLib:
         d.sgx_cloud_build_batch_dev.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int] + [vp] * 8
         d.sgx_cloud_build.argtypes = [vp] * 6 + [C.c_int, C.c_int, vp, C.c_int, vp]
         d.sgx_cloud_camera_to_map_tf.argtypes = [vp, vp, vp]
+        d.sgx_stereo_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
+        d.sgx_stereo_destroy.argtypes = [vp]; d.sgx_stereo_destroy.restype = None
+        d.sgx_stereo_match_batch_dev.argtypes = [vp, C.c_int] + [vp, C.c_int, vp, C.c_int] * 2 + [C.c_int] + [vp] * 6 + [C.c_float, C.c_float, vp, vp, vp, vp]
+        d.sgx_stereo_match.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, C.c_float, vp, vp, vp]
         d.sgx_mappoint_update_normal_and_depth.argtypes = [C.c_int] + [vp] * 6 + [C.c_int, vp, vp, vp]
         d.sgx_mappoint_distinctive_descriptors.argtypes = [C.c_int, vp, vp, vp, vp]
         d.sgx_triangulate_new_map_points.argtypes = [C.c_int, vp] + [C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 5 + [vp, vp, vp, C.c_int, vp, vp, vp]
@@ -356,6 +361,8 @@ class SgxLib:
                 d.sgx_debug_devmem_fail_after.argtypes = [C.c_int]
             if hasattr(d, 'sgx_cloud_debug_read'):
                 d.sgx_cloud_debug_read.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
+            if hasattr(d, 'sgx_stereo_debug_read'):
+                d.sgx_stereo_debug_read.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
 
     def tap(self, name):
         """a test / tuning tap entry (include/sgx_debug.h); the product library has none"""

@@ -16,6 +16,7 @@
 #include <new>
 #include <vector>
 #include "sgx_orb_plan.h"
+#include "sgx_orb_view.h"
 
 #ifdef SGX_EMU
 thread_local sgx_dim3 blockIdx, blockDim, gridDim;
@@ -36,6 +37,8 @@ struct sgx_orb {
     // single-frame staging for sgx_orb_extract
     uint8_t *d_gray1 = nullptr; uint8_t *d_kps1 = nullptr; uint8_t *d_desc1 = nullptr; int *d_count1 = nullptr;
     int detected_batch = 0;        // batch of the last sgx_orb_detect_batch_dev whose pyramid and sel lists are still in the workspace (0: none; any other extraction clears it)
+    // the pyramid in the workspace: frames of the last extraction or detection (0: none), the level-0 image it was built from, 1 when that image is d_gray1 (sgx_orb_extract)
+    int pyr_batch = 0; const uint8_t *pyr_gray = nullptr; int pyr_gray_pitch = 0, pyr_staged = 0;
 };
 
 static thread_local int g_orb_unfused_pyramid = 0;      // test tap: 1 = one k_resize launch per level instead of the fused k_pyramid
@@ -233,9 +236,11 @@ extern "C" int sgx_orb_extract_batch_dev(sgx_orb *h, const uint8_t *d_gray, int 
     if (!h || !d_gray || !d_kps || !d_desc || !d_count) return SGX_ERR_INVALID;
     if (!frames_ok(h, d_gray, pitch, batch, cap) || batch > h->cfg.max_batch) return SGX_ERR_INVALID;
     const OrbSwitches sw = orb_switches();
-    h->detected_batch = 0;
+    h->detected_batch = 0; h->pyr_batch = 0;
     { const int rc = launch_detect(h, sw, d_gray, pitch, batch, (sgx_stream_t)stream_); if (rc != SGX_OK) return rc; }
-    return launch_describe(h, sw, d_gray, pitch, batch, (sgx_stream_t)stream_, d_kps, d_desc, d_count, cap);
+    { const int rc = launch_describe(h, sw, d_gray, pitch, batch, (sgx_stream_t)stream_, d_kps, d_desc, d_count, cap); if (rc != SGX_OK) return rc; }
+    h->pyr_batch = batch; h->pyr_gray = d_gray; h->pyr_gray_pitch = pitch; h->pyr_staged = 0;
+    return SGX_OK;
 }
 
 // The extractor in two calls, for callers that erase keypoints between detection and description (the dynamic-feature mask): see include/sgx.h
@@ -243,10 +248,11 @@ extern "C" int sgx_orb_detect_batch_dev(sgx_orb *h, const uint8_t *d_gray, int p
 {
     if (!h || !d_gray || !d_kps || !d_count) return SGX_ERR_INVALID;
     if (!frames_ok(h, d_gray, pitch, batch, cap) || batch > h->cfg.max_batch) return SGX_ERR_INVALID;
-    h->detected_batch = 0;
+    h->detected_batch = 0; h->pyr_batch = 0;
     { const int rc = launch_detect(h, orb_switches(), d_gray, pitch, batch, (sgx_stream_t)stream_, d_kps, d_count, cap); if (rc != SGX_OK) return rc; }
     SGX_CHECK_HIP(hipGetLastError());
     h->detected_batch = batch;
+    h->pyr_batch = batch; h->pyr_gray = d_gray; h->pyr_gray_pitch = pitch; h->pyr_staged = 0;
     return SGX_OK;
 }
 
@@ -277,6 +283,7 @@ extern "C" int sgx_orb_extract(sgx_orb *h, const uint8_t *gray, int stride, sgx_
         SGX_CHECK_HIP(hipMemcpyAsync(h->d_gray1 + (size_t)y * P, gray + (size_t)y * stride, W, hipMemcpyHostToDevice, 0));
     int rc = sgx_orb_extract_batch_dev(h, h->d_gray1, P, 1, (sgx_keypoint *)h->d_kps1, h->d_desc1, h->d_count1, kc, 0);
     if (rc != SGX_OK) return rc;
+    h->pyr_staged = 1;
     int cnt = 0;
     SGX_CHECK_HIP(hipMemcpyAsync(&cnt, h->d_count1, 4, hipMemcpyDeviceToHost, 0));
     SGX_CHECK_HIP(hipStreamSynchronize(0));
@@ -287,6 +294,23 @@ extern "C" int sgx_orb_extract(sgx_orb *h, const uint8_t *gray, int stride, sgx_
     SGX_CHECK_HIP(hipMemcpyAsync(desc, h->d_desc1, (size_t)cnt * 32, hipMemcpyDeviceToHost, 0));
     SGX_CHECK_HIP(hipStreamSynchronize(0));
     *n = cnt;
+    return SGX_OK;
+}
+
+// the handle as another unit of the library may see it (sgx_orb_view.h)
+static_assert(SGX_VIEW_LEVELS == SGX_MAX_LEVELS, "sgx_orb_view.h mirrors the level tables");
+int sgx_orb_view(const sgx_orb *h, SgxOrbView *v)
+{
+    if (!h || !v) return SGX_ERR_INVALID;
+    memset(v, 0, sizeof *v);
+    const SgxOrbGeom &g = h->p.g;
+    v->lv.nlevels = g.nlevels; v->lv.W = g.W; v->lv.H = g.H; v->lv.kp_cap = g.kp_cap; v->lv.pyr_pitch = g.pyr_pitch;
+    for (int l = 0; l < g.nlevels; l++) {
+        v->lv.w[l] = g.lv[l].w; v->lv.h[l] = g.lv[l].h; v->lv.stride[l] = g.lv[l].stride; v->lv.off[l] = g.lv[l].off;
+        v->lv.scale[l] = h->p.scale[l]; v->lv.inv_scale[l] = h->p.inv_scale[l];
+    }
+    v->lv.stride[0] = 0; v->lv.off[0] = 0;          // level 0 is the caller's image: its pitch is an argument of every call
+    v->d_pyr = h->d_pyr; v->d_gray = h->pyr_gray; v->gray_pitch = h->pyr_gray_pitch; v->pyr_batch = h->pyr_batch; v->staged = h->pyr_staged;
     return SGX_OK;
 }
 

@@ -4,6 +4,7 @@
 //   example_backend det model.param model.bin frame.raw   frame.raw = 480 x 640 x 3 u8 (BGR)
 //   example_backend flow cur.raw prev.raw pts.bin          two 480 x 640 u8 frames, pts.bin = int32 n | n x 2 f32: calcOpticalFlowPyrLK + findFundamentalMat (Frame.cc:445, :469-472)
 //   example_backend sim3 pairs.bin                        int32 n, fix_scale | p1c p2c (n x 3 f32) obs1 obs2 (n x 2 f32) info1 info2 (n f32) | K1 K2 (4 f32) | S12 (8 f64): OptimizeSim3
+//   example_backend stereo left.raw right.raw width height nfeatures scale nlevels fx bf   two rectified gray images: the stereo Frame constructor up to ComputeStereoMatches (Frame.cc:70-99, :716-890)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -106,6 +107,19 @@ int main(int argc, char **argv)
         printf("T12"); for (int i = 0; i < 16; i++) printf(" %.9g", found ? T12[i] : 0.f); printf("\n");
         return 0;
     }
-    fprintf(stderr, "usage: %s ba graph.bin | det model.param model.bin frame.raw | flow cur.raw prev.raw pts.bin | sim3 pairs.bin | voc voc.txt desc.bin | s3solver pairs.bin\n", argv[0]);
+    if (argc >= 11 && !strcmp(argv[1], "stereo")) {                 // the stereo Frame constructor up to ComputeStereoMatches (Frame.cc:70-99): left.raw right.raw width height nfeatures scale nlevels fx bf
+        const int W = atoi(argv[4]), H = atoi(argv[5]);
+        const std::vector<uint8_t> l = slurp(argv[2]), r = slurp(argv[3]);
+        if (l.size() != (size_t)W * H || r.size() != l.size()) { fprintf(stderr, "stereo: the images are not %d x %d bytes\n", W, H); return 2; }
+        sgx::ORBextractor exl(atoi(argv[6]), (float)atof(argv[7]), atoi(argv[8]), 20, 7, W, H), exr(atoi(argv[6]), (float)atof(argv[7]), atoi(argv[8]), 20, 7, W, H);
+        sgx::StereoMatcher stereo(exl, exr);
+        sgx::StereoMatches m;
+        stereo(sgx::GrayView{l.data(), H, W, W}, sgx::GrayView{r.data(), H, W, W}, (float)atof(argv[9]), (float)atof(argv[10]), m);
+        printf("keys %d right %d matched %d\n", (int)m.mvKeys.size(), (int)m.mvKeysRight.size(), m.nmatched);
+        for (size_t i = 0; i < m.mvKeys.size(); i++) printf("%.9g %.9g %.9g %.9g\n", m.mvKeys[i].x, m.mvKeys[i].y, m.mvuRight[i], m.mvDepth[i]);
+        return 0;
+    }
+    fprintf(stderr, "usage: %s ba graph.bin | det model.param model.bin frame.raw | flow cur.raw prev.raw pts.bin | sim3 pairs.bin | voc voc.txt desc.bin | s3solver pairs.bin |"
+                    " stereo left.raw right.raw width height nfeatures scale nlevels fx bf\n", argv[0]);
     return 2;
 }

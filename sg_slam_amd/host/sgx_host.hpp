@@ -691,6 +691,33 @@ private:
     sgx_cloud *h_ = nullptr; int N_; float cam_[4];
 };
 
+// Frame::ComputeStereoMatches (Frame.cc:716-890) as the stereo constructor Frame::Frame(imLeft, imRight, ...) calls it (:70-99): the two extractors of the reference
+// (mpORBextractorLeft / Right, of one geometry) run on the two images, then mvuRight / mvDepth come from their keys, descriptors and pyramids; thin over sgx_stereo_*.
+// mvuRight is computed from the raw keypoints, as in the reference.
+struct StereoMatches { std::vector<sgx_keypoint> mvKeys, mvKeysRight; std::vector<uint8_t> mDescriptors, mDescriptorsRight; std::vector<float> mvuRight, mvDepth; int nmatched = 0; };
+class StereoMatcher {
+public:
+    StereoMatcher(ORBextractor &extractorLeft, ORBextractor &extractorRight) : left_(extractorLeft), right_(extractorRight)
+    {
+        check(sgx_stereo_create(left_.handle(), 1, &h_), "sgx_stereo_create");
+    }
+    ~StereoMatcher() { if (h_) sgx_stereo_destroy(h_); }
+    StereoMatcher(const StereoMatcher &) = delete; StereoMatcher &operator=(const StereoMatcher &) = delete;
+    // ExtractORB(0, imLeft), ExtractORB(1, imRight), ComputeStereoMatches(); fx = K(0, 0), bf = mbf
+    void operator()(const GrayView &imLeft, const GrayView &imRight, float fx, float bf, StereoMatches &out)
+    {
+        left_(imLeft, nullptr, out.mvKeys, out.mDescriptors); right_(imRight, nullptr, out.mvKeysRight, out.mDescriptorsRight);
+        const size_t N = out.mvKeys.size();
+        out.mvuRight.assign(N, -1.0f); out.mvDepth.assign(N, -1.0f); out.nmatched = 0;
+        if (N == 0) return;                                          // Frame.cc:94-95
+        check(sgx_stereo_match(h_, left_.handle(), right_.handle(), out.mvKeys.data(), out.mDescriptors.data(), (int)N, out.mvKeysRight.data(), out.mDescriptorsRight.data(),
+                               (int)out.mvKeysRight.size(), fx, bf, out.mvuRight.data(), out.mvDepth.data(), &out.nmatched), "sgx_stereo_match");
+    }
+    sgx_stereo *handle() { return h_; }
+private:
+    ORBextractor &left_, &right_; sgx_stereo *h_ = nullptr;
+};
+
 // cv::undistortPoints(points, out, K, D, noArray(), K) as Frame::UndistortKeyPoints calls it (Frame.cc:654-684), and Frame::ComputeImageBounds (:686-714);
 // K4 = fx, fy, cx, cy, distCoef = 4, 5 or 8 coefficients.  Points are (x, y) pairs.
 inline std::vector<float> UndistortPoints(const std::vector<float> &points, const float K4[4], const std::vector<float> &distCoef)
