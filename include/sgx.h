@@ -594,6 +594,92 @@ int sgx_kfdb_detect_batch_dev(sgx_kfdb *db, int mode, int Q, const int32_t *ids_
                               const int32_t *conn_offsets_dev, const int32_t *conn_ids_dev, const float *min_score_dev,
                               int32_t *cand_dev, int32_t *n_cand_dev, sgx_kfdb_report *report_dev, int32_t *words_dev, float *score_dev, void *stream);
 
+/* ---- Covisibility graph (src/sg-slam/src/KeyFrame.cc, MapPoint.cc, Tracking.cc:1314-1458, LocalMapping.cc:632-696) --------------------------------------------------
+ * The handle holds the relation "keyframe k observes map point p at keypoint index i" on the device, and what the reference derives from it: mConnectedKeyFrameWeights,
+ * the ordered list, the spanning tree (parent, children, mbFirstConnection), every point's observation list and nObs.  Three walks of it are batched launch sequences:
+ * KeyFrame::UpdateConnections (KeyFrame.cc:290-380), Tracking::UpdateLocalKeyFrames + UpdateLocalPoints (Tracking.cc:1324-1458) and the votes of
+ * LocalMapping::KeyFrameCulling (LocalMapping.cc:632-696).  Everything is integer; a batch of Q equals Q single calls in order, bit for bit.
+ * Kept as written: the gate th = 15 and the fall-back to the single maximum (pKFmax moves on a strictly greater count); mConnectedKeyFrameWeights holds every count >= 1
+ * while the ordered list after UpdateConnections holds only the gated entries; an effective AddConnection / EraseConnection rebuilds the ordered list from the whole
+ * weight map (UpdateBestCovisibles), an AddConnection with the weight unchanged does nothing: the ordered list is state (a mode per keyframe), not a function of the
+ * weights; lists are sorted ascending on (weight, keyframe) and reversed; an empty KFcounter leaves the old connections; the parent is the front of the list at the first
+ * connection of a keyframe whose id is not 0; a mvuRight >= 0 observation counts 2 in nObs, EraseObservation at nObs <= 2 is SetBadFlag; stage 2 of
+ * UpdateLocalKeyFrames walks only the stage-1 keyframes, tests size() > 80 before each, adds the first unmarked of GetBestCovisibilityKeyFrames(10), the first unmarked
+ * child, and for an unmarked parent adds it and leaves the loop; UpdateLocalPoints keeps the first occurrence; culling counts a point only if close (or monocular),
+ * redundant = Observations() > 3 and at least 3 other keyframes at octave <= own + 1, vote nRedundantObservations > 0.9 * nMPs in double, id 0 never voted.
+ * A point exists exactly while it has an observation; any other id in [0, max_points) behaves as isBad().
+ * Defined where the reference is not:
+ *   1. containers keyed or tie-broken by KeyFrame* (map, set, sort of pair<int, KeyFrame*>) run in ascending keyframe id.
+ *   2. mvpMapPoints and mObservations are one relation: a second index of one keyframe for the same point, or a point for an index that holds another one, is
+ *      SGX_ERR_INVALID (erase first, or use replace_point).
+ *   3. a frame has no id: it behaves as one whose mnId is fresh and nonzero.
+ *   4. an erased keyframe contributes nothing: in a kept local_kf row, as a culling candidate (counts 0, no vote), as mpReferenceKF (ref_tracked 0).  It stays in the
+ *      lists of keyframes whose EraseConnection the reference does not call (those absent from its own map), flagged isBad(), as in the reference; its slot returns to
+ *      the pool when no list names it any more.  Its id cannot be added again while it is held so.
+ *   5. culling votes are taken against the map as it stands; the reference's loop erases between candidates.  The equivalent caller loop: query, erase the first voted
+ *      candidate, query again and go on behind it in the candidate list of the FIRST query.
+ *   6. ids out of range and negative counts are SGX_ERR_INVALID, in a batch as that query's status with nothing else of it written; an unknown keyframe id in a query
+ *      likewise (culling: n_cand = SGX_ERR_INVALID); exhausted capacity is SGX_ERR_NOMEM; a refused mutation leaves the handle unchanged.
+ *   7. erase_keyframe of id 0 does nothing (KeyFrame.cc:458); of a keyframe without parent, its unreachable children are left without one.
+ *
+ * sgx_covis_create: at most 4096 keyframes of at most cap <= 8192 keypoints (SGX_ERR_UNSUPPORTED beyond), point ids in [0, max_points), max_observations live
+ *   observations, batches of at most max_queries; monocular = mbMonocular, th_depth = mThDepth.  Device memory: the relation 4 x (3 max_points + 9 chunks + max_keyframes x
+ *   cap) bytes with chunks = max_observations / 8 + min(max_points, max_observations) + 1, attributes max_keyframes x cap, weights 2 x max_keyframes^2, workspace
+ *   4 x max_queries x (5 max_keyframes + max_points + 888) bytes (sgx_covis_info reports both totals).
+ * Mutations: host pointers, synchronous; none may run while a batch of this handle is in flight.  A mutation uploads the words it changes, never the map.
+ *   add_keyframe: mnId (>= 0, not present), per keypoint the octave of mvKeysUn (0..31), mvuRight and mvDepth; close = !(depth > th_depth || depth < 0) in float.
+ *   set_observations: pairs (idx, point) in order: point >= 0 is AddMapPoint + AddObservation, -1 is EraseMapPointMatch + EraseObservation with its SetBadFlag.
+ *   set_points_bad: MapPoint::SetBadFlag.  replace_point: the relation part of MapPoint::Replace(old -> new).  erase_keyframe: KeyFrame::SetBadFlag past its mbNotErase
+ *   gate: EraseConnection in every neighbour, EraseObservation of every point, the spanning-tree loop.
+ * Getters: host pointers, synchronous.  get_weights: mConnectedKeyFrameWeights in id order; get_ordered: mvpOrderedConnectedKeyFrames / mvOrderedWeights;
+ *   best_covisibles: GetBestCovisibilityKeyFrames(N), what sgx_kfdb_set_covisibility takes; get_tree: parent id (-1 none), mbFirstConnection, children in id order;
+ *   get_observations: mObservations in keyframe-id order and nObs; get_keyframe_points: mvpMapPoints.  Array capacities: max_keyframes (cap for keyframe_points). */
+typedef struct sgx_covis sgx_covis;
+typedef struct sgx_covis_report {
+    int32_t status;                         /* SGX_OK, SGX_ERR_INVALID (malformed query / unknown keyframe), SGX_ERR_NOMEM (local_map: more than mcap points) */
+    int32_t n_counter;                      /* KFcounter.size() / keyframeCounter.size() */
+    int32_t max_weight, max_kf;             /* nmax and pKFmax (id, -1 none) */
+    int32_t n_ordered;                      /* update_connections: mvpOrderedConnectedKeyFrames.size() */
+    int32_t parent;                         /* update_connections: the parent id after the call (-1 none) */
+    int32_t n_stage1, n_local_kf, n_local_points, ref_tracked;      /* local_map */
+} sgx_covis_report;
+int sgx_covis_create(int max_keyframes, int cap, int max_points, int max_observations, int max_queries, int monocular, float th_depth, sgx_covis **out);
+void sgx_covis_destroy(sgx_covis *h);
+int sgx_covis_size(const sgx_covis *h);                                                                       /* live keyframes */
+int sgx_covis_info(const sgx_covis *h, int64_t *device_bytes, int64_t *workspace_bytes, int32_t *n_observations);
+int sgx_covis_clear(sgx_covis *h);
+int sgx_covis_add_keyframe(sgx_covis *h, int32_t kf_id, int n, const int32_t *octave, const float *uright, const float *depth);
+int sgx_covis_set_observations(sgx_covis *h, int32_t kf_id, int n, const int32_t *idx, const int32_t *point_id);
+int sgx_covis_set_points_bad(sgx_covis *h, int n, const int32_t *ids);
+int sgx_covis_replace_point(sgx_covis *h, int32_t old_id, int32_t new_id);
+int sgx_covis_erase_keyframe(sgx_covis *h, int32_t kf_id);
+int sgx_covis_get_weights(sgx_covis *h, int32_t kf_id, int32_t *kf_ids, int32_t *weights, int32_t *n);
+int sgx_covis_get_ordered(sgx_covis *h, int32_t kf_id, int32_t *kf_ids, int32_t *weights, int32_t *n);
+int sgx_covis_best_covisibles(sgx_covis *h, int32_t kf_id, int N, int32_t *kf_ids, int32_t *n);
+int sgx_covis_get_tree(sgx_covis *h, int32_t kf_id, int32_t *parent, int32_t *first_connection, int32_t *children, int32_t *n_children);
+int sgx_covis_get_observations(const sgx_covis *h, int32_t point_id, int32_t *kf_ids, int32_t *idx, int32_t *n, int32_t *n_obs);
+int sgx_covis_get_keyframe_points(const sgx_covis *h, int32_t kf_id, int32_t *point_ids, int32_t *n);
+/* The queries: every pointer is device memory, asynchronous on `stream`, one launch sequence for the Q queries, Q <= max_queries.  A handle serves one call at a time.
+ * update_connections: KeyFrame::UpdateConnections of keyframe kf_ids_dev[q], q ascending; one report each.
+ * local_map: frame q = the first n_dev[q] entries of row q of frame_mp_dev (row pitch cap; point ids, -1 none; in/out: a bad point becomes -1).  local_kf_dev (rows of
+ *   max_keyframes ids), n_local_kf_dev and ref_kf_dev are in/out: mvpLocalKeyFrames and mpReferenceKF; when no point votes they stay and the points are rebuilt from the
+ *   old list.  ref_tracked_dev = mpReferenceKF->TrackedMapPoints(min_obs_dev[q]).  local_points_dev / local_obs_dev: rows of mcap, mvpLocalMapPoints as ids and their
+ *   Observations(); n_local_points_dev is the true count, the first mcap are written, and more than mcap is status SGX_ERR_NOMEM.
+ * keyframe_culling: for current keyframe kf_ids_dev[q], cand_dev (rows of max_cand) = GetVectorCovisibleKeyFrames() in order (the first max_cand; n_cand_dev the true
+ *   count), and per candidate nRedundantObservations, nMPs and the vote (0 / 1). */
+int sgx_covis_update_connections_batch_dev(sgx_covis *h, int Q, const int32_t *kf_ids_dev, sgx_covis_report *report_dev, void *stream);
+int sgx_covis_local_map_batch_dev(sgx_covis *h, int Q, int cap, int32_t *frame_mp_dev, const int32_t *n_dev, const int32_t *min_obs_dev, int32_t *local_kf_dev,
+                                  int32_t *n_local_kf_dev, int32_t *ref_kf_dev, int32_t *ref_tracked_dev, int mcap, int32_t *local_points_dev, int32_t *local_obs_dev,
+                                  int32_t *n_local_points_dev, sgx_covis_report *report_dev, void *stream);
+int sgx_covis_keyframe_culling_batch_dev(sgx_covis *h, int Q, const int32_t *kf_ids_dev, int max_cand, int32_t *cand_dev, int32_t *n_cand_dev,
+                                         int32_t *n_redundant_dev, int32_t *n_mps_dev, int32_t *cull_dev, void *stream);
+/* One query from host memory, synchronous, a batch of one through the entries above (frame_mp, local_kf, n_local_kf and ref_kf in/out; local_kf has max_keyframes
+ * entries).  The return value is the query's status: SGX_ERR_INVALID with nothing written, or for local_map SGX_ERR_NOMEM with the first mcap points written. */
+int sgx_covis_update_connections(sgx_covis *h, int32_t kf_id, sgx_covis_report *report);
+int sgx_covis_local_map(sgx_covis *h, int n, int32_t *frame_mp, int min_obs, int32_t *local_kf, int32_t *n_local_kf, int32_t *ref_kf, int32_t *ref_tracked,
+                        int mcap, int32_t *local_points, int32_t *local_obs, int32_t *n_local_points, sgx_covis_report *report);
+int sgx_covis_keyframe_culling(sgx_covis *h, int32_t kf_id, int max_cand, int32_t *cand, int32_t *n_cand, int32_t *n_redundant, int32_t *n_mps, int32_t *cull);
+
 /* The colour conversion at the top of Tracking::GrabImageRGBD (src/sg-slam/src/Tracking.cc:214-227): cvtColor(CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) on
  * 8-bit images, OpenCV's fixed point (R*4899 + G*9617 + B*1868 + 8192) >> 14.  blue_first = !mbRGB.  Pitches in bytes, multiples of 4; pointers 4-byte aligned. */
 int sgx_frame_gray_from_color_batch_dev(int batch, int width, int height, const uint8_t *d_src, int src_pitch, int channels, int blue_first,

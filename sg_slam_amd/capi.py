@@ -100,6 +100,10 @@ KFDB_REPORT_DTYPE = np.dtype([('n_sharing', 'i4'), ('max_common_words', 'i4'), (
                               ('best_acc_score', 'f4'), ('min_score_to_retain', 'f4'), ('n_candidates', 'i4'), ('status', 'i4')])   # sgx_kfdb_report, 36 B
 
 
+COVIS_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_counter', 'max_weight', 'max_kf', 'n_ordered', 'parent', 'n_stage1', 'n_local_kf', 'n_local_points',
+                                                   'ref_tracked')])   # sgx_covis_report, 40 B
+
+
 class OrbConfig(C.Structure):
     _fields_ = [('nfeatures', C.c_int32), ('scale_factor', C.c_float), ('nlevels', C.c_int32),
                 ('ini_th_fast', C.c_int32), ('min_th_fast', C.c_int32), ('width', C.c_int32),
@@ -137,6 +141,10 @@ SYMBOLS = [
     'sgx_kfdb_slots', 'sgx_kfdb_detect_relocalization_candidates', 'sgx_kfdb_detect_loop_candidates', 'sgx_kfdb_min_score', 'sgx_kfdb_detect_batch_dev',
     'sgx_cloud_create', 'sgx_cloud_destroy', 'sgx_cloud_build_batch_dev', 'sgx_cloud_build', 'sgx_cloud_camera_to_map_tf',
     'sgx_stereo_create', 'sgx_stereo_destroy', 'sgx_stereo_match_batch_dev', 'sgx_stereo_match',
+    'sgx_covis_create', 'sgx_covis_destroy', 'sgx_covis_size', 'sgx_covis_info', 'sgx_covis_clear', 'sgx_covis_add_keyframe', 'sgx_covis_set_observations',
+    'sgx_covis_set_points_bad', 'sgx_covis_replace_point', 'sgx_covis_erase_keyframe', 'sgx_covis_get_weights', 'sgx_covis_get_ordered', 'sgx_covis_best_covisibles',
+    'sgx_covis_get_tree', 'sgx_covis_get_observations', 'sgx_covis_get_keyframe_points', 'sgx_covis_update_connections_batch_dev', 'sgx_covis_local_map_batch_dev',
+    'sgx_covis_keyframe_culling_batch_dev', 'sgx_covis_update_connections', 'sgx_covis_local_map', 'sgx_covis_keyframe_culling',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -317,6 +325,28 @@ class SgxLib:
         d.sgx_kfdb_detect_loop_candidates.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_float, vp, vp, C.POINTER(KfdbReport)]
         d.sgx_kfdb_min_score.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
         d.sgx_kfdb_detect_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int] + [vp] * 10
+        d.sgx_covis_create.argtypes = [C.c_int] * 6 + [C.c_float, vp]
+        d.sgx_covis_destroy.argtypes = [vp]; d.sgx_covis_destroy.restype = None
+        d.sgx_covis_size.argtypes = [vp]
+        d.sgx_covis_info.argtypes = [vp, vp, vp, vp]
+        d.sgx_covis_clear.argtypes = [vp]
+        d.sgx_covis_add_keyframe.argtypes = [vp, C.c_int32, C.c_int, vp, vp, vp]
+        d.sgx_covis_set_observations.argtypes = [vp, C.c_int32, C.c_int, vp, vp]
+        d.sgx_covis_set_points_bad.argtypes = [vp, C.c_int, vp]
+        d.sgx_covis_replace_point.argtypes = [vp, C.c_int32, C.c_int32]
+        d.sgx_covis_erase_keyframe.argtypes = [vp, C.c_int32]
+        d.sgx_covis_get_weights.argtypes = [vp, C.c_int32, vp, vp, vp]
+        d.sgx_covis_get_ordered.argtypes = [vp, C.c_int32, vp, vp, vp]
+        d.sgx_covis_best_covisibles.argtypes = [vp, C.c_int32, C.c_int, vp, vp]
+        d.sgx_covis_get_tree.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+        d.sgx_covis_get_observations.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+        d.sgx_covis_get_keyframe_points.argtypes = [vp, C.c_int32, vp, vp]
+        d.sgx_covis_update_connections_batch_dev.argtypes = [vp, C.c_int, vp, vp, vp]
+        d.sgx_covis_local_map_batch_dev.argtypes = [vp, C.c_int, C.c_int] + [vp] * 7 + [C.c_int] + [vp] * 5
+        d.sgx_covis_keyframe_culling_batch_dev.argtypes = [vp, C.c_int, vp, C.c_int] + [vp] * 6
+        d.sgx_covis_update_connections.argtypes = [vp, C.c_int32, vp]
+        d.sgx_covis_local_map.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+        d.sgx_covis_keyframe_culling.argtypes = [vp, C.c_int32, C.c_int, vp, vp, vp, vp, vp]
         d.sgx_match_search_by_bow_kf.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 4 + [C.c_float, C.c_int, vp, vp]
         d.sgx_match_fuse_search.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 6 + [C.POINTER(Camera), vp, vp, C.c_int, C.c_float, C.c_float, vp, vp, vp]
         d.sgx_hamming_matrix_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]

@@ -1,0 +1,187 @@
+"""CovisibilityGraph — Python mirror of the covisibility graph over the C ABI (sgx_covis_*).
+
+The relation "keyframe k observes map point p at keypoint index i" lives on the device with what the reference derives from it (mConnectedKeyFrameWeights, the ordered
+lists, the spanning tree, every point's observations and nObs).  Mutations take host arrays and are synchronous; the three walks — KeyFrame::UpdateConnections
+(KeyFrame.cc:290-380), Tracking::UpdateLocalMap (Tracking.cc:1314-1458) and the votes of LocalMapping::KeyFrameCulling (LocalMapping.cc:632-696) — are batched launch
+sequences on a stream.  Keyframes are named by the caller's mnId, points by dense handles in [0, max_points)."""
+import ctypes as C
+import numpy as np
+from .capi import _vp, COVIS_REPORT_DTYPE
+
+
+def _i4(v):
+    return np.ascontiguousarray(v, 'i4').reshape(-1)
+
+
+class CovisibilityGraph:
+    def __init__(self, max_keyframes=1024, cap=2048, max_points=1 << 17, max_observations=1 << 20, max_queries=64, monocular=False, th_depth=40.0, lib=None):
+        if lib is None:
+            import sg_slam_amd
+            lib = sg_slam_amd.load()
+        self.lib = lib
+        self.max_keyframes = int(max_keyframes); self.cap = int(cap); self.max_points = int(max_points); self.max_queries = int(max_queries)
+        self.h = C.c_void_p()
+        lib.check(lib.dll.sgx_covis_create(self.max_keyframes, self.cap, self.max_points, int(max_observations), self.max_queries, int(bool(monocular)), float(th_depth),
+                                           C.byref(self.h)), 'sgx_covis_create')
+        self._on_host = 'EMULATOR' in lib.version()               # the emulator's "device" memory is host memory
+
+    # ---- mutations (host arrays, synchronous)
+    def add_keyframe(self, kf_id, octave, uright, depth):
+        o = _i4(octave); u = np.ascontiguousarray(uright, 'f4').reshape(-1); d = np.ascontiguousarray(depth, 'f4').reshape(-1)
+        assert len(o) == len(u) == len(d)
+        self.lib.check(self.lib.dll.sgx_covis_add_keyframe(self.h, int(kf_id), len(o), _vp(o), _vp(u), _vp(d)), 'sgx_covis_add_keyframe')
+
+    def set_observations(self, kf_id, idx, point_ids):
+        """pairs in order: point >= 0 = AddMapPoint + AddObservation, -1 = EraseMapPointMatch + EraseObservation"""
+        i = _i4(idx); p = _i4(point_ids)
+        assert len(i) == len(p)
+        self.lib.check(self.lib.dll.sgx_covis_set_observations(self.h, int(kf_id), len(i), _vp(i), _vp(p)), 'sgx_covis_set_observations')
+
+    def erase_observation(self, kf_id, idx):
+        self.set_observations(kf_id, [idx], [-1])
+
+    def set_points_bad(self, ids):
+        p = _i4(ids)
+        self.lib.check(self.lib.dll.sgx_covis_set_points_bad(self.h, len(p), _vp(p)), 'sgx_covis_set_points_bad')
+
+    def replace_point(self, old, new):
+        self.lib.check(self.lib.dll.sgx_covis_replace_point(self.h, int(old), int(new)), 'sgx_covis_replace_point')
+
+    def erase_keyframe(self, kf_id):
+        self.lib.check(self.lib.dll.sgx_covis_erase_keyframe(self.h, int(kf_id)), 'sgx_covis_erase_keyframe')
+
+    def clear(self):
+        self.lib.check(self.lib.dll.sgx_covis_clear(self.h), 'sgx_covis_clear')
+
+    def size(self):
+        return int(self.lib.dll.sgx_covis_size(self.h))
+
+    def info(self):
+        """(device bytes, of which workspace bytes, live observations)"""
+        a = C.c_int64(); b = C.c_int64(); n = C.c_int32()
+        self.lib.check(self.lib.dll.sgx_covis_info(self.h, C.byref(a), C.byref(b), C.byref(n)), 'sgx_covis_info')
+        return a.value, b.value, n.value
+
+    # ---- getters (synchronous)
+    def _pairs(self, fn, kf_id):
+        a = np.zeros(self.max_keyframes, 'i4'); b = np.zeros(self.max_keyframes, 'i4'); n = C.c_int32()
+        self.lib.check(getattr(self.lib.dll, fn)(self.h, int(kf_id), _vp(a), _vp(b), C.byref(n)), fn)
+        return [int(x) for x in a[:n.value]], [int(x) for x in b[:n.value]]
+
+    def weights(self, kf_id):
+        """mConnectedKeyFrameWeights as (ids ascending, weights)"""
+        return self._pairs('sgx_covis_get_weights', kf_id)
+
+    def ordered(self, kf_id):
+        """(mvpOrderedConnectedKeyFrames as ids, mvOrderedWeights)"""
+        return self._pairs('sgx_covis_get_ordered', kf_id)
+
+    def best_covisibles(self, kf_id, N=10):
+        """GetBestCovisibilityKeyFrames(N) as ids: what KeyFrameDatabase.set_covisibility takes"""
+        a = np.zeros(max(int(N), 1), 'i4'); n = C.c_int32()
+        self.lib.check(self.lib.dll.sgx_covis_best_covisibles(self.h, int(kf_id), int(N), _vp(a), C.byref(n)), 'sgx_covis_best_covisibles')
+        return [int(x) for x in a[:n.value]]
+
+    def tree(self, kf_id):
+        """(parent id or -1, mbFirstConnection, children ids ascending)"""
+        p = C.c_int32(); f = C.c_int32(); c = np.zeros(self.max_keyframes, 'i4'); n = C.c_int32()
+        self.lib.check(self.lib.dll.sgx_covis_get_tree(self.h, int(kf_id), C.byref(p), C.byref(f), _vp(c), C.byref(n)), 'sgx_covis_get_tree')
+        return p.value, bool(f.value), [int(x) for x in c[:n.value]]
+
+    def observations(self, point_id):
+        """(mObservations as [(keyframe id, index)] in keyframe order, nObs)"""
+        k, i = np.zeros(self.max_keyframes, 'i4'), np.zeros(self.max_keyframes, 'i4'); n = C.c_int32(); no = C.c_int32()
+        self.lib.check(self.lib.dll.sgx_covis_get_observations(self.h, int(point_id), _vp(k), _vp(i), C.byref(n), C.byref(no)), 'sgx_covis_get_observations')
+        return [(int(a), int(b)) for a, b in zip(k[:n.value], i[:n.value])], no.value
+
+    def keyframe_points(self, kf_id):
+        p = np.zeros(self.cap, 'i4'); n = C.c_int32()
+        self.lib.check(self.lib.dll.sgx_covis_get_keyframe_points(self.h, int(kf_id), _vp(p), C.byref(n)), 'sgx_covis_get_keyframe_points')
+        return p[:n.value].copy()
+
+    # ---- device plumbing
+    def _dev(self, a):
+        a = np.ascontiguousarray(a)
+        if self._on_host: return a.copy()
+        import torch
+        return torch.from_numpy(a).cuda()
+
+    def _host(self, x):
+        return x if self._on_host else x.cpu().numpy()
+
+    def _stream(self, stream):
+        if self._on_host: return None
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return C.c_void_p(s.cuda_stream)
+
+    def _sync(self, stream):
+        if self._on_host: return
+        import torch
+        (stream if stream is not None else torch.cuda.current_stream()).synchronize()
+
+    # ---- the queries
+    def update_connections_batch_dev(self, Q, kf_ids_dev, report_dev, stream=None):
+        self._keep = (kf_ids_dev, report_dev)
+        self.lib.check(self.lib.dll.sgx_covis_update_connections_batch_dev(self.h, int(Q), _vp(kf_ids_dev), _vp(report_dev), self._stream(stream)),
+                       'sgx_covis_update_connections_batch_dev')
+
+    def update_connections(self, kf_ids, stream=None):
+        """KeyFrame::UpdateConnections of the listed keyframes, in order, as one batch; the report records"""
+        k = _i4(kf_ids); Q = len(k)
+        rep = self._dev(np.zeros(Q * COVIS_REPORT_DTYPE.itemsize, 'u1'))
+        self.update_connections_batch_dev(Q, self._dev(k), rep, stream)
+        self._sync(stream)
+        return self._host(rep).view(COVIS_REPORT_DTYPE).copy()
+
+    def local_map_batch_dev(self, Q, cap, frame_mp_dev, n_dev, min_obs_dev, local_kf_dev, n_local_kf_dev, ref_kf_dev, ref_tracked_dev, mcap, local_points_dev, local_obs_dev,
+                            n_local_points_dev, report_dev, stream=None):
+        self._keep = (frame_mp_dev, n_dev, min_obs_dev, local_kf_dev, n_local_kf_dev, ref_kf_dev, ref_tracked_dev, local_points_dev, local_obs_dev, n_local_points_dev, report_dev)
+        self.lib.check(self.lib.dll.sgx_covis_local_map_batch_dev(self.h, int(Q), int(cap), _vp(frame_mp_dev), _vp(n_dev), _vp(min_obs_dev), _vp(local_kf_dev), _vp(n_local_kf_dev),
+                                                                  _vp(ref_kf_dev), _vp(ref_tracked_dev), int(mcap), _vp(local_points_dev), _vp(local_obs_dev),
+                                                                  _vp(n_local_points_dev), _vp(report_dev), self._stream(stream)), 'sgx_covis_local_map_batch_dev')
+
+    def local_map(self, frames, min_obs, local_kfs=None, ref_kfs=None, mcap=4096, stream=None):
+        """Tracking::UpdateLocalMap for Q frames (lists of point ids, -1 = none) from the host, read back.  local_kfs / ref_kfs: mvpLocalKeyFrames (id lists) and
+        mpReferenceKF (-1 none) going in.  Returns one dict per frame: frame (mvpMapPoints after), local_kf, ref_kf, ref_tracked, points, obs, n_points, report."""
+        Q = len(frames); cap = max([len(f) for f in frames] + [1]); N = self.max_keyframes
+        fm = np.full((Q, cap), -1, 'i4'); n = np.zeros(Q, 'i4'); lk = np.full((Q, N), -1, 'i4'); nlk = np.zeros(Q, 'i4'); ref = np.full(Q, -1, 'i4')
+        for q, f in enumerate(frames):
+            fm[q, :len(f)] = f; n[q] = len(f)
+            if local_kfs is not None: lk[q, :len(local_kfs[q])] = local_kfs[q]; nlk[q] = len(local_kfs[q])
+            if ref_kfs is not None: ref[q] = ref_kfs[q]
+        mo = np.broadcast_to(np.asarray(min_obs, 'i4'), (Q,)).copy()
+        d = [self._dev(x) for x in (fm, n, mo, lk, nlk, ref, np.zeros(Q, 'i4'), np.full((Q, mcap), -1, 'i4'), np.full((Q, mcap), -1, 'i4'), np.zeros(Q, 'i4'),
+                                    np.zeros(Q * COVIS_REPORT_DTYPE.itemsize, 'u1'))]
+        self.local_map_batch_dev(Q, cap, d[0], d[1], d[2], d[3], d[4], d[5], d[6], mcap, d[7], d[8], d[9], d[10], stream)
+        self._sync(stream)
+        fm, _, _, lk, nlk, ref, rt, pts, obs, npts, rep = [self._host(x) for x in d]
+        rep = rep.view(COVIS_REPORT_DTYPE)
+        out = []
+        for q in range(Q):
+            m = min(int(npts[q]), mcap)
+            out.append(dict(frame=fm[q, :n[q]].copy(), local_kf=[int(x) for x in lk[q, :nlk[q]]], ref_kf=int(ref[q]), ref_tracked=int(rt[q]), points=pts[q, :m].copy(),
+                            obs=obs[q, :m].copy(), n_points=int(npts[q]), report=rep[q].copy()))
+        return out
+
+    def keyframe_culling_batch_dev(self, Q, kf_ids_dev, max_cand, cand_dev, n_cand_dev, n_redundant_dev, n_mps_dev, cull_dev, stream=None):
+        self._keep = (kf_ids_dev, cand_dev, n_cand_dev, n_redundant_dev, n_mps_dev, cull_dev)
+        self.lib.check(self.lib.dll.sgx_covis_keyframe_culling_batch_dev(self.h, int(Q), _vp(kf_ids_dev), int(max_cand), _vp(cand_dev), _vp(n_cand_dev), _vp(n_redundant_dev),
+                                                                         _vp(n_mps_dev), _vp(cull_dev), self._stream(stream)), 'sgx_covis_keyframe_culling_batch_dev')
+
+    def keyframe_culling(self, kf_ids, max_cand=None, stream=None):
+        """the votes of LocalMapping::KeyFrameCulling for the listed current keyframes, against the map as it stands: per keyframe a list of
+        (candidate id, nRedundantObservations, nMPs, vote), or None for an unknown keyframe"""
+        k = _i4(kf_ids); Q = len(k); M = int(max_cand or self.max_keyframes)
+        d = [self._dev(x) for x in (k, np.full((Q, M), -1, 'i4'), np.zeros(Q, 'i4'), np.zeros((Q, M), 'i4'), np.zeros((Q, M), 'i4'), np.zeros((Q, M), 'i4'))]
+        self.keyframe_culling_batch_dev(Q, d[0], M, d[1], d[2], d[3], d[4], d[5], stream)
+        self._sync(stream)
+        _, cand, nc, red, mps, cull = [self._host(x) for x in d]
+        return [None if nc[q] < 0 else [(int(cand[q, r]), int(red[q, r]), int(mps[q, r]), int(cull[q, r])) for r in range(min(int(nc[q]), M))] for q in range(Q)]
+
+    def close(self):
+        if self.h: self.lib.dll.sgx_covis_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try: self.close()
+        except Exception: pass

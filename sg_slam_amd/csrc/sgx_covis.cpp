@@ -1,0 +1,603 @@
+// sgx_covis.cpp — the covisibility graph behind the C ABI (sgx_covis_*): the relation keyframe x map point as a heap the host mirrors and patches on the device
+// (KeyFrame::AddMapPoint / EraseMapPointMatch, MapPoint::AddObservation / EraseObservation / SetBadFlag / Replace, src/sg-slam/src/MapPoint.cc:98-215), the graph
+// (weights, list modes, spanning tree) as device state, and the three walks of it as the launch sequences of sgx_covis_kernels.h.
+#include "sgx_covis_kernels.h"
+#include "sgx_devmem.h"
+#include "../../include/sgx.h"
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <map>
+#include <set>
+#include <utility>
+#include <vector>
+
+static_assert(sizeof(sgx_covis_report) == sizeof(SgxCovisReport), "the kernels write sgx_covis_report records");
+
+enum { H_FREE = 0, H_LIVE = 1, H_HDR = 2, COVIS_JCAP = 1 << 16, COVIS_GRID = 128 };
+
+struct sgx_covis {
+    int max_kf = 0, cap = 0, max_points = 0, max_obs = 0, max_q = 0, mono = 0, nchunks = 0;
+    float th_depth = 0.0f;
+    // the relation: the host's copy of the device heap; a mutation pokes it, remembers what it overwrote, and flushes the words it changed
+    std::vector<int32_t> heap; std::vector<unsigned char> attr;
+    size_t o_head = 0, o_cnt = 0, o_nobs = 0, o_next = 0, o_ent = 0, o_mp = 0;
+    std::vector<std::pair<size_t, int32_t>> undo;
+    // keyframe slots
+    struct Slot { int32_t id = -1; int state = SGX_COVIS_FREE, n = 0; };
+    std::vector<Slot> slot; std::vector<int> free_slots;      // lowest last
+    std::map<int32_t, int> by_id; std::set<int32_t> dead_ids;
+    int nslots = 0; bool tables_dirty = true;
+    // device
+    int *d_heap = nullptr, *d_kf = nullptr, *d_sorted_id = nullptr, *d_sorted_slot = nullptr, *d_jidx = nullptr, *d_jval = nullptr, *d_refs = nullptr;
+    unsigned char *d_attr = nullptr; unsigned short *d_W = nullptr;
+    int *ws_q = nullptr, *ws_cnt = nullptr, *ws_ord = nullptr, *ws_ordw = nullptr, *ws_lkf = nullptr, *ws_pcnt = nullptr, *ws_top = nullptr, *ws_ntop = nullptr, *d_stamp = nullptr;
+    int *s_kf = nullptr;
+    int64_t device_bytes = 0, workspace_bytes = 0;
+    SgxDevMem mem;
+
+    int32_t &H(size_t i) { return heap[i]; }
+    void poke(size_t i, int32_t v) { if (heap[i] != v) { undo.emplace_back(i, heap[i]); heap[i] = v; } }
+    void rollback() { for (size_t j = undo.size(); j-- > 0;) heap[undo[j].first] = undo[j].second; undo.clear(); }
+};
+
+static SgxCovisArgs covis_args(sgx_covis *h)
+{
+    SgxCovisArgs A{};
+    A.nslots = h->nslots; A.max_kf = h->max_kf; A.cap = h->cap; A.max_points = h->max_points; A.nlive = (int)h->by_id.size(); A.monocular = h->mono;
+    A.heap = h->d_heap; A.o_head = h->o_head; A.o_cnt = h->o_cnt; A.o_nobs = h->o_nobs; A.o_next = h->o_next; A.o_ent = h->o_ent; A.o_mp = h->o_mp;
+    A.attr = h->d_attr; A.kf = h->d_kf; A.W = h->d_W; A.sorted_id = h->d_sorted_id; A.sorted_slot = h->d_sorted_slot;
+    A.ws_q = h->ws_q; A.ws_cnt = h->ws_cnt; A.ws_ord = h->ws_ord; A.ws_ordw = h->ws_ordw; A.ws_lkf = h->ws_lkf; A.ws_pcnt = h->ws_pcnt; A.ws_top = h->ws_top; A.ws_ntop = h->ws_ntop;
+    A.stamp = h->d_stamp;
+    return A;
+}
+
+// the words a mutation changed, each once with its final value, as one or more scatter launches; the mutation has returned only when they are on the device
+static int covis_flush(sgx_covis *h)
+{
+    std::vector<int32_t> idx; idx.reserve(h->undo.size());
+    for (const auto &u : h->undo) idx.push_back((int32_t)u.first);
+    h->undo.clear();
+    std::sort(idx.begin(), idx.end()); idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+    std::vector<int32_t> val(idx.size());
+    for (size_t j = 0; j < idx.size(); j++) val[j] = h->heap[(size_t)idx[j]];
+    for (size_t at = 0; at < idx.size(); at += COVIS_JCAP) {
+        const int n = (int)std::min((size_t)COVIS_JCAP, idx.size() - at);
+        SGX_CHECK_HIP(hipMemcpy(h->d_jidx, idx.data() + at, (size_t)n * 4, hipMemcpyHostToDevice));
+        SGX_CHECK_HIP(hipMemcpy(h->d_jval, val.data() + at, (size_t)n * 4, hipMemcpyHostToDevice));
+        SGX_LAUNCH(k_covis_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), (sgx_stream_t)0, h->d_heap, (const int *)h->d_jidx, (const int *)h->d_jval, n);
+        SGX_CHECK_HIP(hipGetLastError());
+        SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    }
+    return SGX_OK;
+}
+
+// ---- the observation lists: a chain of 8-entry chunks per point, the head chunk holding the remainder; per-point order means nothing to any result
+static void obs_add(sgx_covis *h, int p, int t, int i)
+{
+    const int cnt = h->H(h->o_cnt + p);
+    if (cnt % SGX_COVIS_CHUNK == 0) {
+        const int c = h->H(H_FREE);
+        h->poke(H_FREE, h->H(h->o_next + c));
+        h->poke(h->o_next + c, cnt ? h->H(h->o_head + p) : -1);
+        h->poke(h->o_head + p, c);
+    }
+    h->poke(h->o_ent + (size_t)h->H(h->o_head + p) * SGX_COVIS_CHUNK + cnt % SGX_COVIS_CHUNK, t << 16 | i);
+    h->poke(h->o_cnt + p, cnt + 1);
+    h->poke(h->o_nobs + p, h->H(h->o_nobs + p) + ((h->attr[(size_t)t * h->cap + i] & SGX_COVIS_ATTR_RIGHT) ? 2 : 1));      // MapPoint.cc:105-108
+    h->poke(H_LIVE, h->H(H_LIVE) + 1);
+}
+
+template <class F> static void obs_each(const sgx_covis *h, int p, F f)          // f(entry address, slot, index) -> true to stop
+{
+    int left = h->heap[h->o_cnt + p], m = ((left - 1) & (SGX_COVIS_CHUNK - 1)) + 1;
+    for (int c = h->heap[h->o_head + p]; left > 0 && c >= 0; c = h->heap[h->o_next + c], m = SGX_COVIS_CHUNK) {
+        for (int j = 0; j < m; j++) { const size_t at = h->o_ent + (size_t)c * SGX_COVIS_CHUNK + j; const int e = h->heap[at]; if (f(at, e >> 16, e & 0xffff)) return; }
+        left -= m;
+    }
+}
+
+static int obs_index(const sgx_covis *h, int p, int t)                           // GetIndexInKeyFrame
+{
+    int r = -1;
+    obs_each(h, p, [&](size_t, int tt, int i) { if (tt == t) { r = i; return true; } return false; });
+    return r;
+}
+
+static void obs_clear(sgx_covis *h, int p)
+{
+    const int cnt = h->H(h->o_cnt + p);
+    if (!cnt) return;
+    for (int c = h->H(h->o_head + p), left = cnt; left > 0 && c >= 0;) {
+        const int nx = h->H(h->o_next + c);
+        h->poke(h->o_next + c, h->H(H_FREE)); h->poke(H_FREE, c);
+        left -= left == cnt ? ((cnt - 1) & (SGX_COVIS_CHUNK - 1)) + 1 : SGX_COVIS_CHUNK;
+        c = nx;
+    }
+    h->poke(h->o_cnt + p, 0); h->poke(h->o_nobs + p, 0); h->poke(h->o_head + p, -1);
+    h->poke(H_LIVE, h->H(H_LIVE) - cnt);
+}
+
+static void point_set_bad(sgx_covis *h, int p)                                   // MapPoint::SetBadFlag (:151-168)
+{
+    obs_each(h, p, [&](size_t, int t, int i) { h->poke(h->o_mp + (size_t)t * h->cap + i, -1); return false; });
+    obs_clear(h, p);
+}
+
+static void point_erase_observation(sgx_covis *h, int p, int t)                  // MapPoint::EraseObservation (:111-137)
+{
+    size_t at = 0; int idx = -1;
+    obs_each(h, p, [&](size_t a, int tt, int i) { if (tt == t) { at = a; idx = i; return true; } return false; });
+    if (idx < 0) return;
+    const int cnt = h->H(h->o_cnt + p), head = h->H(h->o_head + p);
+    const size_t last = h->o_ent + (size_t)head * SGX_COVIS_CHUNK + (cnt - 1) % SGX_COVIS_CHUNK;
+    h->poke(at, h->H(last));
+    if ((cnt - 1) % SGX_COVIS_CHUNK == 0) {                                      // the head chunk is empty now
+        h->poke(h->o_head + p, cnt > 1 ? h->H(h->o_next + head) : -1);
+        h->poke(h->o_next + head, h->H(H_FREE)); h->poke(H_FREE, head);
+    }
+    h->poke(h->o_cnt + p, cnt - 1);
+    h->poke(h->o_nobs + p, h->H(h->o_nobs + p) - ((h->attr[(size_t)t * h->cap + idx] & SGX_COVIS_ATTR_RIGHT) ? 2 : 1));
+    h->poke(H_LIVE, h->H(H_LIVE) - 1);
+    if (h->H(h->o_nobs + p) <= 2) point_set_bad(h, p);                           // "If only 2 observations or less, discard point"
+}
+
+static void covis_reset_host(sgx_covis *h)
+{
+    std::fill(h->heap.begin(), h->heap.end(), 0);
+    for (int p = 0; p < h->max_points; p++) h->heap[h->o_head + p] = -1;
+    for (int c = 0; c < h->nchunks; c++) h->heap[h->o_next + c] = c + 1 < h->nchunks ? c + 1 : -1;
+    std::fill(h->heap.begin() + (long)h->o_mp, h->heap.end(), -1);
+    h->heap[H_FREE] = 0; h->heap[H_LIVE] = 0;
+    std::fill(h->attr.begin(), h->attr.end(), 0);
+    for (auto &s : h->slot) s = sgx_covis::Slot();
+    h->free_slots.clear();
+    for (int s = h->max_kf - 1; s >= 0; s--) h->free_slots.push_back(s);
+    h->by_id.clear(); h->dead_ids.clear(); h->undo.clear(); h->nslots = 0; h->tables_dirty = true;
+}
+
+static int covis_reset_device(sgx_covis *h)
+{
+    SGX_CHECK_HIP(hipMemcpy(h->d_heap, h->heap.data(), h->heap.size() * 4, hipMemcpyHostToDevice));
+    SGX_CHECK_HIP(hipMemset(h->d_W, 0, (size_t)h->max_kf * h->max_kf * 2));
+    SGX_CHECK_HIP(hipMemset(h->d_kf, 0, (size_t)h->max_kf * CV_FIELDS * 4));
+    SGX_CHECK_HIP(hipMemset(h->d_attr, 0, (size_t)h->max_kf * h->cap));
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));                         // a fill may return before it is done; the caller's next batch runs on another stream
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_create(int max_keyframes, int cap, int max_points, int max_observations, int max_queries, int monocular, float th_depth, sgx_covis **out)
+{
+    if (out) *out = nullptr;
+    if (!out || max_keyframes < 1 || cap < 1 || max_points < 1 || max_observations < 1 || max_queries < 1 || th_depth != th_depth) return SGX_ERR_INVALID;
+    if (max_keyframes > SGX_COVIS_MAX_KF || cap > SGX_COVIS_MAX_CAP) return SGX_ERR_UNSUPPORTED;      // a slot and an index share one word; a histogram over the slots sits in LDS
+    sgx_covis *h = new sgx_covis;
+    h->max_kf = max_keyframes; h->cap = cap; h->max_points = max_points; h->max_obs = max_observations; h->max_q = max_queries; h->mono = monocular != 0; h->th_depth = th_depth;
+    // every point with an observation holds ceil(cnt / 8) <= 1 + cnt / 8 chunks, so this many never run out while the observations are within max_observations
+    h->nchunks = max_observations / SGX_COVIS_CHUNK + std::min(max_points, max_observations) + 1;
+    const size_t P = (size_t)max_points, N = (size_t)max_keyframes, Qn = (size_t)max_queries;
+    h->o_head = H_HDR; h->o_cnt = h->o_head + P; h->o_nobs = h->o_cnt + P; h->o_next = h->o_nobs + P; h->o_ent = h->o_next + (size_t)h->nchunks;
+    h->o_mp = h->o_ent + (size_t)h->nchunks * SGX_COVIS_CHUNK;
+    const size_t heap_n = h->o_mp + N * (size_t)cap;
+    if (heap_n >= (size_t)INT_MAX || Qn * std::max(N, P) >= (size_t)INT_MAX) { delete h; return SGX_ERR_UNSUPPORTED; }
+    h->heap.resize(heap_n); h->attr.resize(N * (size_t)cap); h->slot.resize(N);
+    covis_reset_host(h);
+    SgxDevMem &m = h->mem;
+    int rc;
+    if ((rc = m.alloc(&h->d_heap, heap_n)) || (rc = m.alloc(&h->d_attr, N * (size_t)cap)) || (rc = m.alloc(&h->d_kf, N * CV_FIELDS)) || (rc = m.alloc(&h->d_W, N * N)) ||
+        (rc = m.alloc(&h->d_sorted_id, N)) || (rc = m.alloc(&h->d_sorted_slot, N)) || (rc = m.alloc(&h->d_jidx, (size_t)COVIS_JCAP)) || (rc = m.alloc(&h->d_jval, (size_t)COVIS_JCAP)) ||
+        (rc = m.alloc(&h->d_refs, N)) || (rc = m.alloc(&h->s_kf, 1)) ||
+        (rc = m.alloc(&h->ws_q, Qn * CQ_FIELDS)) || (rc = m.alloc(&h->ws_cnt, Qn * N)) || (rc = m.alloc(&h->ws_ord, Qn * N)) || (rc = m.alloc(&h->ws_ordw, Qn * N)) ||
+        (rc = m.alloc(&h->ws_lkf, Qn * N)) || (rc = m.alloc(&h->ws_pcnt, Qn * N)) || (rc = m.alloc(&h->ws_top, Qn * SGX_COVIS_LOCAL_LIMIT * SGX_COVIS_BEST)) ||
+        (rc = m.alloc(&h->ws_ntop, Qn * SGX_COVIS_LOCAL_LIMIT)) || (rc = m.alloc(&h->d_stamp, Qn * P))) { delete h; return rc; }
+    h->workspace_bytes = (int64_t)(Qn * 4 * (CQ_FIELDS + 5 * N + SGX_COVIS_LOCAL_LIMIT * (SGX_COVIS_BEST + 1) + P));
+    h->device_bytes = h->workspace_bytes + (int64_t)(heap_n * 4 + N * (size_t)cap + N * CV_FIELDS * 4 + N * N * 2 + N * 12 + (size_t)COVIS_JCAP * 8 + 4);
+    if ((rc = covis_reset_device(h)) != SGX_OK) { delete h; return rc; }
+    *out = h;
+    return SGX_OK;
+}
+
+extern "C" void sgx_covis_destroy(sgx_covis *h) { delete h; }
+
+extern "C" int sgx_covis_size(const sgx_covis *h) { return h ? (int)h->by_id.size() : SGX_ERR_INVALID; }
+
+extern "C" int sgx_covis_info(const sgx_covis *h, int64_t *device_bytes, int64_t *workspace_bytes, int32_t *n_observations)
+{
+    if (!h) return SGX_ERR_INVALID;
+    if (device_bytes) *device_bytes = h->device_bytes;
+    if (workspace_bytes) *workspace_bytes = h->workspace_bytes;
+    if (n_observations) *n_observations = h->heap[H_LIVE];
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_clear(sgx_covis *h)
+{
+    if (!h) return SGX_ERR_INVALID;
+    covis_reset_host(h);
+    return covis_reset_device(h);
+}
+
+static int covis_upload_record(sgx_covis *h, int s, int mode, int first)
+{
+    const sgx_covis::Slot &S = h->slot[(size_t)s];
+    int32_t rec[CV_FIELDS] = {};
+    rec[CV_ID] = S.id; rec[CV_STATE] = S.state; rec[CV_N] = S.n; rec[CV_MODE] = mode; rec[CV_SINGLE] = -1; rec[CV_PARENT] = -1; rec[CV_FIRST] = first;
+    SGX_CHECK_HIP(hipMemcpy(h->d_kf + (size_t)s * CV_FIELDS, rec, sizeof(rec), hipMemcpyHostToDevice));
+    return SGX_OK;
+}
+
+// erased keyframes that no row lists any more give their slots back
+static int covis_reclaim(sgx_covis *h)
+{
+    if (h->dead_ids.empty()) return SGX_OK;
+    SgxCovisArgs A = covis_args(h);
+    SGX_LAUNCH(k_covis_refs, dim3((unsigned)((h->nslots + 255) / 256)), dim3(256), (sgx_stream_t)0, A, h->d_refs);
+    SGX_CHECK_HIP(hipGetLastError());
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    std::vector<int32_t> refs((size_t)h->nslots);
+    SGX_CHECK_HIP(hipMemcpy(refs.data(), h->d_refs, refs.size() * 4, hipMemcpyDeviceToHost));
+    for (int s = h->nslots - 1; s >= 0; s--) {
+        sgx_covis::Slot &S = h->slot[(size_t)s];
+        if (S.state != SGX_COVIS_DEAD || refs[(size_t)s]) continue;
+        h->dead_ids.erase(S.id);
+        S = sgx_covis::Slot();
+        const int rc = covis_upload_record(h, s, SGX_COVIS_ALL, 0);
+        if (rc != SGX_OK) return rc;
+        h->free_slots.insert(std::lower_bound(h->free_slots.begin(), h->free_slots.end(), s, [](int a, int b) { return a > b; }), s);
+    }
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_add_keyframe(sgx_covis *h, int32_t kf_id, int n, const int32_t *octave, const float *uright, const float *depth)
+{
+    if (!h || kf_id < 0 || n < 0 || n > h->cap || (n > 0 && (!octave || !uright || !depth)) || h->by_id.count(kf_id) || h->dead_ids.count(kf_id)) return SGX_ERR_INVALID;
+    for (int i = 0; i < n; i++) if (octave[i] < 0 || octave[i] > SGX_COVIS_ATTR_OCTAVE) return SGX_ERR_INVALID;
+    if (h->free_slots.empty()) { const int rc = covis_reclaim(h); if (rc != SGX_OK) return rc; }
+    if (h->free_slots.empty()) return SGX_ERR_NOMEM;
+    const int s = h->free_slots.back();
+    unsigned char *a = &h->attr[(size_t)s * h->cap];
+    for (int i = 0; i < n; i++) {
+        const bool close = !(depth[i] > h->th_depth || depth[i] < 0);                                          // LocalMapping.cc:660, in float as written
+        a[i] = (unsigned char)(octave[i] | (uright[i] >= 0 ? SGX_COVIS_ATTR_RIGHT : 0) | (close ? SGX_COVIS_ATTR_CLOSE : 0));
+    }
+    if (n) SGX_CHECK_HIP(hipMemcpy(h->d_attr + (size_t)s * h->cap, a, (size_t)n, hipMemcpyHostToDevice));
+    SGX_CHECK_HIP(hipMemset(h->d_W + (size_t)s * h->max_kf, 0, (size_t)h->max_kf * 2));
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    h->free_slots.pop_back();
+    sgx_covis::Slot &S = h->slot[(size_t)s];
+    S.id = kf_id; S.state = SGX_COVIS_LIVE; S.n = n;
+    if (s + 1 > h->nslots) h->nslots = s + 1;
+    h->by_id[kf_id] = s; h->tables_dirty = true;
+    return covis_upload_record(h, s, SGX_COVIS_ALL, 1);
+}
+
+extern "C" int sgx_covis_set_observations(sgx_covis *h, int32_t kf_id, int n, const int32_t *idx, const int32_t *point_id)
+{
+    if (!h || n < 0 || (n > 0 && (!idx || !point_id))) return SGX_ERR_INVALID;
+    const auto it = h->by_id.find(kf_id);
+    if (it == h->by_id.end()) return SGX_ERR_INVALID;
+    const int s = it->second, N = h->slot[(size_t)s].n;
+    int rc = SGX_OK;
+    for (int j = 0; j < n && rc == SGX_OK; j++) {
+        const int i = idx[j], p = point_id[j];
+        if (i < 0 || i >= N || p < -1 || p >= h->max_points) { rc = SGX_ERR_INVALID; break; }
+        const size_t at = h->o_mp + (size_t)s * h->cap + i;
+        const int cur = h->H(at);
+        if (p < 0) {                                                             // EraseMapPointMatch + EraseObservation
+            if (cur >= 0) { h->poke(at, -1); point_erase_observation(h, cur, s); }
+        } else if (cur != p) {                                                   // AddMapPoint + AddObservation; the same point at the same index again is nothing
+            if (cur >= 0 || obs_index(h, p, s) >= 0) rc = SGX_ERR_INVALID;       // one relation: an index holds one point, a keyframe sees a point once
+            else if (h->H(H_LIVE) >= h->max_obs) rc = SGX_ERR_NOMEM;
+            else { h->poke(at, p); obs_add(h, p, s, i); }
+        }
+    }
+    if (rc != SGX_OK) { h->rollback(); return rc; }
+    return covis_flush(h);
+}
+
+extern "C" int sgx_covis_set_points_bad(sgx_covis *h, int n, const int32_t *ids)
+{
+    if (!h || n < 0 || (n > 0 && !ids)) return SGX_ERR_INVALID;
+    for (int j = 0; j < n; j++) if (ids[j] < 0 || ids[j] >= h->max_points) return SGX_ERR_INVALID;
+    for (int j = 0; j < n; j++) point_set_bad(h, ids[j]);
+    return covis_flush(h);
+}
+
+extern "C" int sgx_covis_replace_point(sgx_covis *h, int32_t old_id, int32_t new_id)
+{
+    if (!h || old_id < 0 || old_id >= h->max_points || new_id < 0 || new_id >= h->max_points) return SGX_ERR_INVALID;
+    if (old_id == new_id) return SGX_OK;                                          // MapPoint.cc:179-180
+    std::vector<std::pair<int, int>> obs;
+    obs_each(h, old_id, [&](size_t, int t, int i) { obs.emplace_back(t, i); return false; });
+    obs_clear(h, old_id);                                                         // obs = mObservations; mObservations.clear(); mbBad = true
+    for (const auto &o : obs) {
+        const size_t at = h->o_mp + (size_t)o.first * h->cap + o.second;
+        if (obs_index(h, new_id, o.first) < 0) { h->poke(at, new_id); obs_add(h, new_id, o.first, o.second); }      // ReplaceMapPointMatch + AddObservation
+        else h->poke(at, -1);                                                     // EraseMapPointMatch
+    }
+    return covis_flush(h);
+}
+
+extern "C" int sgx_covis_erase_keyframe(sgx_covis *h, int32_t kf_id)
+{
+    if (!h) return SGX_ERR_INVALID;
+    const auto it = h->by_id.find(kf_id);
+    if (it == h->by_id.end()) return SGX_ERR_INVALID;
+    if (kf_id == 0) return SGX_OK;                                                // KeyFrame.cc:458-459
+    const int s = it->second, N = h->slot[(size_t)s].n;
+    for (int i = 0; i < N; i++) {
+        const size_t at = h->o_mp + (size_t)s * h->cap + i;
+        const int p = h->H(at);
+        if (p < 0) continue;
+        h->poke(at, -1);                                                          // the erased keyframe keeps nothing (the reference leaves its mvpMapPoints stale)
+        point_erase_observation(h, p, s);
+    }
+    int rc = covis_flush(h);
+    if (rc != SGX_OK) return rc;
+    SgxCovisArgs A = covis_args(h);
+    SGX_LAUNCH(k_covis_erase_graph, dim3(1), dim3(256), (sgx_stream_t)0, A, s);
+    SGX_CHECK_HIP(hipGetLastError());
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    h->slot[(size_t)s].state = SGX_COVIS_DEAD; h->slot[(size_t)s].n = 0;
+    h->dead_ids.insert(kf_id); h->by_id.erase(it); h->tables_dirty = true;
+    return SGX_OK;
+}
+
+static int covis_sync_tables(sgx_covis *h)
+{
+    if (!h->tables_dirty) return SGX_OK;
+    std::vector<int32_t> sid, sslot;
+    for (const auto &e : h->by_id) { sid.push_back(e.first); sslot.push_back(e.second); }
+    if (!sid.empty()) {
+        SGX_CHECK_HIP(hipMemcpy(h->d_sorted_id, sid.data(), sid.size() * 4, hipMemcpyHostToDevice));
+        SGX_CHECK_HIP(hipMemcpy(h->d_sorted_slot, sslot.data(), sslot.size() * 4, hipMemcpyHostToDevice));
+    }
+    h->tables_dirty = false;
+    return SGX_OK;
+}
+
+// ---- getters: host pointers, synchronous
+static int covis_slot_of(const sgx_covis *h, int32_t kf_id) { const auto it = h->by_id.find(kf_id); return it == h->by_id.end() ? -1 : it->second; }
+
+extern "C" int sgx_covis_get_weights(sgx_covis *h, int32_t kf_id, int32_t *kf_ids, int32_t *weights, int32_t *n)
+{
+    if (!h || !n) return SGX_ERR_INVALID;
+    const int s = covis_slot_of(h, kf_id);
+    if (s < 0) return SGX_ERR_INVALID;
+    std::vector<unsigned short> row((size_t)h->nslots);
+    SGX_CHECK_HIP(hipMemcpy(row.data(), h->d_W + (size_t)s * h->max_kf, row.size() * 2, hipMemcpyDeviceToHost));
+    std::vector<std::pair<int32_t, int32_t>> v;
+    for (int t = 0; t < h->nslots; t++) if (row[(size_t)t]) v.emplace_back(h->slot[(size_t)t].id, (int32_t)row[(size_t)t]);
+    std::sort(v.begin(), v.end());
+    if (!v.empty() && (!kf_ids || !weights)) return SGX_ERR_INVALID;
+    for (size_t j = 0; j < v.size(); j++) { kf_ids[j] = v[j].first; weights[j] = v[j].second; }
+    *n = (int32_t)v.size();
+    return SGX_OK;
+}
+
+static int covis_ordered(sgx_covis *h, int32_t kf_id, std::vector<int32_t> &ids, std::vector<int32_t> &w)
+{
+    if (covis_slot_of(h, kf_id) < 0) return SGX_ERR_INVALID;
+    int rc = covis_sync_tables(h);
+    if (rc != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipMemcpy(h->s_kf, &kf_id, 4, hipMemcpyHostToDevice));
+    SgxCovisArgs A = covis_args(h);
+    A.Q = 1; A.q_kf = h->s_kf;
+    SGX_LAUNCH(k_covis_ordered, dim3(1), dim3(256), (sgx_stream_t)0, A);
+    SGX_CHECK_HIP(hipGetLastError());
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    int32_t wq[CQ_FIELDS];
+    SGX_CHECK_HIP(hipMemcpy(wq, h->ws_q, sizeof(wq), hipMemcpyDeviceToHost));
+    ids.resize((size_t)wq[CQ_NORD]); w.resize(ids.size());
+    if (!ids.empty()) {
+        SGX_CHECK_HIP(hipMemcpy(ids.data(), h->ws_ord, ids.size() * 4, hipMemcpyDeviceToHost));
+        SGX_CHECK_HIP(hipMemcpy(w.data(), h->ws_ordw, ids.size() * 4, hipMemcpyDeviceToHost));
+        for (auto &x : ids) x = h->slot[(size_t)x].id;
+    }
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_get_ordered(sgx_covis *h, int32_t kf_id, int32_t *kf_ids, int32_t *weights, int32_t *n)
+{
+    if (!h || !n) return SGX_ERR_INVALID;
+    std::vector<int32_t> ids, w;
+    const int rc = covis_ordered(h, kf_id, ids, w);
+    if (rc != SGX_OK) return rc;
+    if (!ids.empty() && (!kf_ids || !weights)) return SGX_ERR_INVALID;
+    for (size_t j = 0; j < ids.size(); j++) { kf_ids[j] = ids[j]; weights[j] = w[j]; }
+    *n = (int32_t)ids.size();
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_best_covisibles(sgx_covis *h, int32_t kf_id, int N, int32_t *kf_ids, int32_t *n)
+{
+    if (!h || !n || N < 0) return SGX_ERR_INVALID;
+    std::vector<int32_t> ids, w;
+    const int rc = covis_ordered(h, kf_id, ids, w);
+    if (rc != SGX_OK) return rc;
+    const size_t m = std::min(ids.size(), (size_t)N);
+    if (m && !kf_ids) return SGX_ERR_INVALID;
+    for (size_t j = 0; j < m; j++) kf_ids[j] = ids[j];
+    *n = (int32_t)m;
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_get_tree(sgx_covis *h, int32_t kf_id, int32_t *parent, int32_t *first_connection, int32_t *children, int32_t *n_children)
+{
+    if (!h) return SGX_ERR_INVALID;
+    const int s = covis_slot_of(h, kf_id);
+    if (s < 0) return SGX_ERR_INVALID;
+    std::vector<int32_t> rec((size_t)h->nslots * CV_FIELDS);
+    SGX_CHECK_HIP(hipMemcpy(rec.data(), h->d_kf, rec.size() * 4, hipMemcpyDeviceToHost));
+    const int p = rec[(size_t)s * CV_FIELDS + CV_PARENT];
+    if (parent) *parent = p >= 0 ? h->slot[(size_t)p].id : -1;
+    if (first_connection) *first_connection = rec[(size_t)s * CV_FIELDS + CV_FIRST];
+    std::vector<int32_t> c;
+    for (int t = 0; t < h->nslots; t++) if (h->slot[(size_t)t].state == SGX_COVIS_LIVE && rec[(size_t)t * CV_FIELDS + CV_PARENT] == s) c.push_back(h->slot[(size_t)t].id);
+    std::sort(c.begin(), c.end());
+    if (n_children) *n_children = (int32_t)c.size();
+    if (children) for (size_t j = 0; j < c.size(); j++) children[j] = c[j];
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_get_observations(const sgx_covis *h, int32_t point_id, int32_t *kf_ids, int32_t *idx, int32_t *n, int32_t *n_obs)
+{
+    if (!h || !n || point_id < 0 || point_id >= h->max_points) return SGX_ERR_INVALID;
+    std::vector<std::pair<int32_t, int32_t>> v;
+    obs_each(h, point_id, [&](size_t, int t, int i) { v.emplace_back(h->slot[(size_t)t].id, i); return false; });
+    std::sort(v.begin(), v.end());
+    if (!v.empty() && (!kf_ids || !idx)) return SGX_ERR_INVALID;
+    for (size_t j = 0; j < v.size(); j++) { kf_ids[j] = v[j].first; idx[j] = v[j].second; }
+    *n = (int32_t)v.size();
+    if (n_obs) *n_obs = h->heap[h->o_nobs + (size_t)point_id];
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_get_keyframe_points(const sgx_covis *h, int32_t kf_id, int32_t *point_ids, int32_t *n)
+{
+    if (!h || !n) return SGX_ERR_INVALID;
+    const int s = covis_slot_of(h, kf_id);
+    if (s < 0) return SGX_ERR_INVALID;
+    const int N = h->slot[(size_t)s].n;
+    if (N && !point_ids) return SGX_ERR_INVALID;
+    if (N) memcpy(point_ids, &h->heap[h->o_mp + (size_t)s * h->cap], (size_t)N * 4);
+    *n = N;
+    return SGX_OK;
+}
+
+// ---- the queries: device pointers, asynchronous on `stream`
+extern "C" int sgx_covis_update_connections_batch_dev(sgx_covis *h, int Q, const int32_t *kf_ids_dev, sgx_covis_report *report_dev, void *stream)
+{
+    if (!h || Q < 0 || Q > h->max_q) return SGX_ERR_INVALID;
+    if (Q == 0) return SGX_OK;
+    if (!kf_ids_dev || !report_dev) return SGX_ERR_INVALID;
+    const int rc = covis_sync_tables(h);
+    if (rc != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    SgxCovisArgs A = covis_args(h);
+    A.Q = Q; A.q_kf = kf_ids_dev; A.report = (SgxCovisReport *)report_dev;
+    SGX_LAUNCH(k_covis_count, dim3((unsigned)Q), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_apply, dim3(1), dim3(256), s, A);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_local_map_batch_dev(sgx_covis *h, int Q, int cap, int32_t *frame_mp_dev, const int32_t *n_dev, const int32_t *min_obs_dev, int32_t *local_kf_dev,
+                                             int32_t *n_local_kf_dev, int32_t *ref_kf_dev, int32_t *ref_tracked_dev, int mcap, int32_t *local_points_dev, int32_t *local_obs_dev,
+                                             int32_t *n_local_points_dev, sgx_covis_report *report_dev, void *stream)
+{
+    if (!h || Q < 0 || Q > h->max_q || cap < 0 || mcap < 0) return SGX_ERR_INVALID;
+    if (Q == 0) return SGX_OK;
+    if (!frame_mp_dev || !n_dev || !min_obs_dev || !local_kf_dev || !n_local_kf_dev || !ref_kf_dev || !ref_tracked_dev || !local_points_dev || !local_obs_dev ||
+        !n_local_points_dev || !report_dev) return SGX_ERR_INVALID;
+    const int rc = covis_sync_tables(h);
+    if (rc != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    SgxCovisArgs A = covis_args(h);
+    A.Q = Q; A.report = (SgxCovisReport *)report_dev;
+    A.f_cap = cap; A.frame_mp = frame_mp_dev; A.f_n = n_dev; A.min_obs = min_obs_dev; A.local_kf = local_kf_dev; A.n_local_kf = n_local_kf_dev; A.ref_kf = ref_kf_dev;
+    A.ref_tracked = ref_tracked_dev; A.mcap = mcap; A.local_points = local_points_dev; A.local_obs = local_obs_dev; A.n_local_points = n_local_points_dev;
+    const unsigned G = (unsigned)std::max(1, std::min(h->nslots, (int)COVIS_GRID));
+    SGX_CHECK_HIP(hipMemsetAsync(h->d_stamp, 0x7f, (size_t)Q * h->max_points * 4, s));
+    SGX_LAUNCH(k_covis_lm_votes, dim3((unsigned)Q), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_lm_top, dim3((unsigned)SGX_COVIS_LOCAL_LIMIT, (unsigned)Q), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_lm_stage2, dim3((unsigned)Q), dim3(64), s, A);
+    SGX_LAUNCH(k_covis_lm_stamp, dim3(G, (unsigned)Q), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_lm_count, dim3(G, (unsigned)Q), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_lm_emit, dim3(G, (unsigned)Q), dim3(256), s, A);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_keyframe_culling_batch_dev(sgx_covis *h, int Q, const int32_t *kf_ids_dev, int max_cand, int32_t *cand_dev, int32_t *n_cand_dev,
+                                                    int32_t *n_redundant_dev, int32_t *n_mps_dev, int32_t *cull_dev, void *stream)
+{
+    if (!h || Q < 0 || Q > h->max_q || max_cand < 1) return SGX_ERR_INVALID;
+    if (Q == 0) return SGX_OK;
+    if (!kf_ids_dev || !cand_dev || !n_cand_dev || !n_redundant_dev || !n_mps_dev || !cull_dev) return SGX_ERR_INVALID;
+    const int rc = covis_sync_tables(h);
+    if (rc != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    SgxCovisArgs A = covis_args(h);
+    A.Q = Q; A.q_kf = kf_ids_dev; A.max_cand = max_cand; A.cand = cand_dev; A.n_cand = n_cand_dev; A.n_red = n_redundant_dev; A.n_mps = n_mps_dev; A.cull = cull_dev;
+    SGX_LAUNCH(k_covis_ordered, dim3((unsigned)Q), dim3(256), s, A);
+    const unsigned G = (unsigned)std::max(1, std::min(h->nslots, max_cand));
+    SGX_LAUNCH(k_covis_cull, dim3(G, (unsigned)Q), dim3(256), s, A);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+// ---- one query from host memory through the batch entries: staged in device buffers of the call, run on the legacy stream, read back
+template <class T> static int covis_stage(SgxDevMem &m, T **d, const T *src, size_t n, size_t cap)
+{
+    const int rc = m.alloc(d, cap);
+    if (rc != SGX_OK) return rc;
+    if (n && src) SGX_CHECK_HIP(hipMemcpy(*d, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_update_connections(sgx_covis *h, int32_t kf_id, sgx_covis_report *report)
+{
+    if (!h) return SGX_ERR_INVALID;
+    SgxDevMem m; int32_t *d_id = nullptr; sgx_covis_report *d_rep = nullptr; int rc;
+    if ((rc = covis_stage(m, &d_id, &kf_id, 1, 1)) || (rc = m.alloc(&d_rep, 1))) return rc;
+    if ((rc = sgx_covis_update_connections_batch_dev(h, 1, d_id, d_rep, nullptr)) != SGX_OK) return rc;
+    sgx_covis_report R;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    SGX_CHECK_HIP(hipMemcpy(&R, d_rep, sizeof(R), hipMemcpyDeviceToHost));
+    if (report) *report = R;
+    return R.status;
+}
+
+extern "C" int sgx_covis_local_map(sgx_covis *h, int n, int32_t *frame_mp, int min_obs, int32_t *local_kf, int32_t *n_local_kf, int32_t *ref_kf, int32_t *ref_tracked,
+                                   int mcap, int32_t *local_points, int32_t *local_obs, int32_t *n_local_points, sgx_covis_report *report)
+{
+    if (!h || n < 0 || (n > 0 && !frame_mp) || !local_kf || !n_local_kf || !ref_kf || mcap < 0 || (mcap > 0 && (!local_points || !local_obs)) || !n_local_points) return SGX_ERR_INVALID;
+    if (*n_local_kf < 0 || *n_local_kf > h->max_kf) return SGX_ERR_INVALID;
+    SgxDevMem m; int rc;
+    int32_t *d_f = nullptr, *d_n = nullptr, *d_mo = nullptr, *d_lk = nullptr, *d_nlk = nullptr, *d_ref = nullptr, *d_rt = nullptr, *d_pts = nullptr, *d_obs = nullptr, *d_np = nullptr;
+    sgx_covis_report *d_rep = nullptr;
+    const int32_t n32 = n, mo32 = min_obs;
+    if ((rc = covis_stage(m, &d_f, (const int32_t *)frame_mp, (size_t)n, (size_t)n)) || (rc = covis_stage(m, &d_n, &n32, 1, 1)) || (rc = covis_stage(m, &d_mo, &mo32, 1, 1)) ||
+        (rc = covis_stage(m, &d_lk, (const int32_t *)local_kf, (size_t)*n_local_kf, (size_t)h->max_kf)) || (rc = covis_stage(m, &d_nlk, (const int32_t *)n_local_kf, 1, 1)) ||
+        (rc = covis_stage(m, &d_ref, (const int32_t *)ref_kf, 1, 1)) || (rc = m.alloc(&d_rt, 1)) || (rc = m.alloc(&d_pts, (size_t)mcap)) || (rc = m.alloc(&d_obs, (size_t)mcap)) ||
+        (rc = m.alloc(&d_np, 1)) || (rc = m.alloc(&d_rep, 1))) return rc;
+    if ((rc = sgx_covis_local_map_batch_dev(h, 1, n, d_f, d_n, d_mo, d_lk, d_nlk, d_ref, d_rt, mcap, d_pts, d_obs, d_np, d_rep, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    sgx_covis_report R;
+    SGX_CHECK_HIP(hipMemcpy(&R, d_rep, sizeof(R), hipMemcpyDeviceToHost));
+    if (report) *report = R;
+    if (R.status == SGX_ERR_INVALID) return R.status;                              // nothing of the query was written
+    int32_t np = 0;
+    SGX_CHECK_HIP(hipMemcpy(&np, d_np, 4, hipMemcpyDeviceToHost));
+    SGX_CHECK_HIP(hipMemcpy(n_local_kf, d_nlk, 4, hipMemcpyDeviceToHost));
+    SGX_CHECK_HIP(hipMemcpy(ref_kf, d_ref, 4, hipMemcpyDeviceToHost));
+    if (ref_tracked) SGX_CHECK_HIP(hipMemcpy(ref_tracked, d_rt, 4, hipMemcpyDeviceToHost));
+    if (n) SGX_CHECK_HIP(hipMemcpy(frame_mp, d_f, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (*n_local_kf) SGX_CHECK_HIP(hipMemcpy(local_kf, d_lk, (size_t)*n_local_kf * 4, hipMemcpyDeviceToHost));
+    const size_t w = (size_t)std::min(np, mcap);
+    if (w) { SGX_CHECK_HIP(hipMemcpy(local_points, d_pts, w * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(local_obs, d_obs, w * 4, hipMemcpyDeviceToHost)); }
+    *n_local_points = np;
+    return R.status;                                                               // SGX_OK, or SGX_ERR_NOMEM with the first mcap points written
+}
+
+extern "C" int sgx_covis_keyframe_culling(sgx_covis *h, int32_t kf_id, int max_cand, int32_t *cand, int32_t *n_cand, int32_t *n_redundant, int32_t *n_mps, int32_t *cull)
+{
+    if (!h || max_cand < 1 || !cand || !n_cand || !n_redundant || !n_mps || !cull) return SGX_ERR_INVALID;
+    SgxDevMem m; int rc;
+    int32_t *d_id = nullptr, *d_c = nullptr, *d_nc = nullptr, *d_r = nullptr, *d_m = nullptr, *d_v = nullptr;
+    if ((rc = covis_stage(m, &d_id, &kf_id, 1, 1)) || (rc = m.alloc(&d_c, (size_t)max_cand)) || (rc = m.alloc(&d_nc, 1)) || (rc = m.alloc(&d_r, (size_t)max_cand)) ||
+        (rc = m.alloc(&d_m, (size_t)max_cand)) || (rc = m.alloc(&d_v, (size_t)max_cand))) return rc;
+    if ((rc = sgx_covis_keyframe_culling_batch_dev(h, 1, d_id, max_cand, d_c, d_nc, d_r, d_m, d_v, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    int32_t nc = 0;
+    SGX_CHECK_HIP(hipMemcpy(&nc, d_nc, 4, hipMemcpyDeviceToHost));
+    if (nc < 0) return nc;
+    const size_t w = (size_t)std::min(nc, max_cand);
+    if (w) {
+        SGX_CHECK_HIP(hipMemcpy(cand, d_c, w * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(n_redundant, d_r, w * 4, hipMemcpyDeviceToHost));
+        SGX_CHECK_HIP(hipMemcpy(n_mps, d_m, w * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(cull, d_v, w * 4, hipMemcpyDeviceToHost));
+    }
+    *n_cand = nc;
+    return SGX_OK;
+}

@@ -5,6 +5,8 @@
 //   example_backend flow cur.raw prev.raw pts.bin          two 480 x 640 u8 frames, pts.bin = int32 n | n x 2 f32: calcOpticalFlowPyrLK + findFundamentalMat (Frame.cc:445, :469-472)
 //   example_backend sim3 pairs.bin                        int32 n, fix_scale | p1c p2c (n x 3 f32) obs1 obs2 (n x 2 f32) info1 info2 (n f32) | K1 K2 (4 f32) | S12 (8 f64): OptimizeSim3
 //   example_backend stereo left.raw right.raw width height nfeatures scale nlevels fx bf   two rectified gray images: the stereo Frame constructor up to ComputeStereoMatches (Frame.cc:70-99, :716-890)
+//   example_backend covis map.bin                        int32 monocular, nkf | per keyframe: int32 id, n, octave[n], f32 uright[n], depth[n], int32 points[n] (-1 none) | int32 nuc, ids |
+//                                                        int32 nframe, frame | int32 current keyframe: UpdateConnections, the lists, UpdateLocalMap, the culling votes and loop
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -107,6 +109,40 @@ int main(int argc, char **argv)
         printf("T12"); for (int i = 0; i < 16; i++) printf(" %.9g", found ? T12[i] : 0.f); printf("\n");
         return 0;
     }
+    if (argc >= 3 && !strcmp(argv[1], "covis")) {
+        const std::vector<uint8_t> b = slurp(argv[2]);
+        const int32_t *p = (const int32_t *)b.data();
+        const int mono = *p++, nkf = *p++;
+        sgx::CovisibilityGraph G(nkf + 1, 256, 1 << 14, nkf * 256, 4, mono != 0, 40.0f);
+        for (int k = 0; k < nkf; k++) {
+            const int32_t id = *p++, n = *p++;
+            const std::vector<int32_t> oct(p, p + n); p += n;
+            const float *f = (const float *)p; const std::vector<float> ur(f, f + n), dp(f + n, f + 2 * n); p += 2 * n;
+            G.AddKeyFrame(id, oct, ur, dp);
+            std::vector<int32_t> idx, pts;
+            for (int i = 0; i < n; i++) if (p[i] >= 0) { idx.push_back(i); pts.push_back(p[i]); }
+            p += n;
+            G.SetObservations(id, idx, pts);
+        }
+        const int nuc = *p++;
+        for (int k = 0; k < nuc; k++) {
+            const int32_t id = *p++; const sgx_covis_report r = G.UpdateConnections(id);
+            printf("uc %d: %d %d %d %d %d %d |", id, r.status, r.n_counter, r.max_weight, r.max_kf, r.n_ordered, r.parent);
+            for (auto &e : G.GetOrderedConnectedKeyFrames(id)) printf(" %d:%d", e.first, e.second);
+            printf(" |"); for (int32_t c : G.GetBestCovisibilityKeyFrames(id, 10)) printf(" %d", c);
+            printf("\n");
+        }
+        const int nf = *p++; const std::vector<int32_t> frame(p, p + nf); p += nf;
+        const sgx::CovisibilityGraph::LocalMap L = G.UpdateLocalMap(frame, 3, {}, -1, 1 << 14);
+        printf("local_kf %d ref %d tracked %d:", (int)L.mvpLocalKeyFrames.size(), L.mpReferenceKF, L.trackedMapPoints); for (int32_t k : L.mvpLocalKeyFrames) printf(" %d", k);
+        printf("\nlocal_points %d:", (int)L.mvpLocalMapPoints.size()); for (size_t i = 0; i < L.mvpLocalMapPoints.size(); i++) printf(" %d/%d", L.mvpLocalMapPoints[i], L.observations[i]);
+        const int32_t cur = *p++;
+        printf("\nvotes:"); for (auto &v : G.KeyFrameCullingVotes(cur)) printf(" %d:%d/%d/%d", v.mnId, v.nRedundantObservations, v.nMPs, v.cull);
+        printf("\nculled:"); for (int32_t k : G.KeyFrameCulling(cur)) printf(" %d", k);
+        printf("\nparent of %d: %d, children:", cur, G.GetParent(cur)); for (int32_t c : G.GetChilds(cur)) printf(" %d", c);
+        printf("\n");
+        return 0;
+    }
     if (argc >= 11 && !strcmp(argv[1], "stereo")) {                 // the stereo Frame constructor up to ComputeStereoMatches (Frame.cc:70-99): left.raw right.raw width height nfeatures scale nlevels fx bf
         const int W = atoi(argv[4]), H = atoi(argv[5]);
         const std::vector<uint8_t> l = slurp(argv[2]), r = slurp(argv[3]);
@@ -120,6 +156,6 @@ int main(int argc, char **argv)
         return 0;
     }
     fprintf(stderr, "usage: %s ba graph.bin | det model.param model.bin frame.raw | flow cur.raw prev.raw pts.bin | sim3 pairs.bin | voc voc.txt desc.bin | s3solver pairs.bin |"
-                    " stereo left.raw right.raw width height nfeatures scale nlevels fx bf\n", argv[0]);
+                    " stereo left.raw right.raw width height nfeatures scale nlevels fx bf | covis map.bin\n", argv[0]);
     return 2;
 }

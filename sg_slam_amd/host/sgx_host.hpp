@@ -466,6 +466,102 @@ private:
     sgx_kfdb *h_ = nullptr; int cap_;
 };
 
+// The covisibility graph over sgx_covis_*: what KeyFrame / MapPoint keep of the relation "keyframe observes map point at keypoint index" (mvpMapPoints, mObservations,
+// nObs, mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames, the spanning tree) on the device.  Where the reference passes KeyFrame* / MapPoint*, this mirror takes
+// the keyframe's mnId and the point's dense handle.  The host-array queries below run a batch of one; the *_batch_dev entries take device arrays through handle().
+class CovisibilityGraph {
+public:
+    struct LocalMap { std::vector<int32_t> mvpMapPoints, mvpLocalKeyFrames, mvpLocalMapPoints, observations; int32_t mpReferenceKF = -1, trackedMapPoints = 0; sgx_covis_report report{}; };
+    struct CullingVote { int32_t mnId, nRedundantObservations, nMPs, cull; };
+    CovisibilityGraph(int maxKeyFrames, int cap, int maxPoints, int maxObservations, int maxQueries = 64, bool mbMonocular = false, float mThDepth = 40.0f)
+        : maxkf_(maxKeyFrames), cap_(cap)
+    { check(sgx_covis_create(maxKeyFrames, cap, maxPoints, maxObservations, maxQueries, mbMonocular ? 1 : 0, mThDepth, &h_), "sgx_covis_create"); }
+    ~CovisibilityGraph() { if (h_) sgx_covis_destroy(h_); }
+    CovisibilityGraph(const CovisibilityGraph &) = delete; CovisibilityGraph &operator=(const CovisibilityGraph &) = delete;
+    // ---- mutations
+    void AddKeyFrame(int32_t mnId, const std::vector<int32_t> &octave, const std::vector<float> &mvuRight, const std::vector<float> &mvDepth)
+    { check(sgx_covis_add_keyframe(h_, mnId, (int)octave.size(), octave.data(), mvuRight.data(), mvDepth.data()), "sgx_covis_add_keyframe"); }
+    void AddMapPoint(int32_t mnId, int32_t idx, int32_t point) { check(sgx_covis_set_observations(h_, mnId, 1, &idx, &point), "sgx_covis_set_observations"); }      // KeyFrame::AddMapPoint + MapPoint::AddObservation
+    void EraseMapPointMatch(int32_t mnId, int32_t idx) { const int32_t none = -1; check(sgx_covis_set_observations(h_, mnId, 1, &idx, &none), "sgx_covis_set_observations"); }
+    void SetObservations(int32_t mnId, const std::vector<int32_t> &idx, const std::vector<int32_t> &points)
+    { check(idx.size() == points.size() ? sgx_covis_set_observations(h_, mnId, (int)idx.size(), idx.data(), points.data()) : SGX_ERR_INVALID, "sgx_covis_set_observations"); }
+    void SetBadFlag(const std::vector<int32_t> &points) { check(sgx_covis_set_points_bad(h_, (int)points.size(), points.data()), "sgx_covis_set_points_bad"); }      // MapPoint::SetBadFlag
+    void Replace(int32_t oldPoint, int32_t newPoint) { check(sgx_covis_replace_point(h_, oldPoint, newPoint), "sgx_covis_replace_point"); }                          // MapPoint::Replace
+    void EraseKeyFrame(int32_t mnId) { check(sgx_covis_erase_keyframe(h_, mnId), "sgx_covis_erase_keyframe"); }                                                      // KeyFrame::SetBadFlag
+    void clear() { check(sgx_covis_clear(h_), "sgx_covis_clear"); }
+    int size() const { return sgx_covis_size(h_); }
+    // ---- getters
+    std::vector<std::pair<int32_t, int32_t>> GetConnectedKeyFrameWeights(int32_t mnId) { return pairs(sgx_covis_get_weights, mnId, "sgx_covis_get_weights"); }
+    std::vector<std::pair<int32_t, int32_t>> GetOrderedConnectedKeyFrames(int32_t mnId) { return pairs(sgx_covis_get_ordered, mnId, "sgx_covis_get_ordered"); }      // (keyframe, weight)
+    std::vector<int32_t> GetBestCovisibilityKeyFrames(int32_t mnId, int N)
+    {
+        std::vector<int32_t> v((size_t)(N > 0 ? N : 1)); int32_t n = 0;
+        check(sgx_covis_best_covisibles(h_, mnId, N, v.data(), &n), "sgx_covis_best_covisibles");
+        v.resize((size_t)n); return v;
+    }
+    int32_t GetParent(int32_t mnId) { int32_t p = -1; check(sgx_covis_get_tree(h_, mnId, &p, nullptr, nullptr, nullptr), "sgx_covis_get_tree"); return p; }
+    std::vector<int32_t> GetChilds(int32_t mnId)
+    {
+        std::vector<int32_t> c((size_t)maxkf_); int32_t n = 0;
+        check(sgx_covis_get_tree(h_, mnId, nullptr, nullptr, c.data(), &n), "sgx_covis_get_tree");
+        c.resize((size_t)n); return c;
+    }
+    std::vector<std::pair<int32_t, int32_t>> GetObservations(int32_t point, int32_t *nObs = nullptr)                                                              // (keyframe, index)
+    {
+        std::vector<int32_t> a((size_t)maxkf_), b((size_t)maxkf_); int32_t n = 0;
+        check(sgx_covis_get_observations(h_, point, a.data(), b.data(), &n, nObs), "sgx_covis_get_observations");
+        std::vector<std::pair<int32_t, int32_t>> v; for (int32_t j = 0; j < n; j++) v.emplace_back(a[(size_t)j], b[(size_t)j]);
+        return v;
+    }
+    // ---- the queries, a batch of one from host arrays (device arrays: the sgx_covis_*_batch_dev entries on handle())
+    sgx_covis_report UpdateConnections(int32_t mnId)                            // KeyFrame::UpdateConnections (KeyFrame.cc:290-380)
+    { sgx_covis_report r{}; check(sgx_covis_update_connections(h_, mnId, &r), "sgx_covis_update_connections"); return r; }
+    // Tracking::UpdateLocalMap (Tracking.cc:1314-1458): the frame's mvpMapPoints, mvpLocalKeyFrames and mpReferenceKF go in and come back; more than mcap local points throw
+    LocalMap UpdateLocalMap(const std::vector<int32_t> &mvpMapPoints, int minObs, const std::vector<int32_t> &mvpLocalKeyFrames, int32_t mpReferenceKF, int mcap = 4096)
+    {
+        LocalMap L; L.mvpMapPoints = mvpMapPoints; L.mvpLocalKeyFrames = mvpLocalKeyFrames; L.mpReferenceKF = mpReferenceKF;
+        int32_t nk = (int32_t)mvpLocalKeyFrames.size(), np = 0;
+        if (nk > maxkf_ || mcap < 1) check(SGX_ERR_INVALID, "UpdateLocalMap");
+        L.mvpLocalKeyFrames.resize((size_t)maxkf_); L.mvpLocalMapPoints.resize((size_t)mcap); L.observations.resize((size_t)mcap);
+        check(sgx_covis_local_map(h_, (int)L.mvpMapPoints.size(), L.mvpMapPoints.data(), minObs, L.mvpLocalKeyFrames.data(), &nk, &L.mpReferenceKF, &L.trackedMapPoints, mcap,
+                                  L.mvpLocalMapPoints.data(), L.observations.data(), &np, &L.report), "sgx_covis_local_map");
+        L.mvpLocalKeyFrames.resize((size_t)nk); L.mvpLocalMapPoints.resize((size_t)np); L.observations.resize((size_t)np);
+        return L;
+    }
+    // the votes of LocalMapping::KeyFrameCulling (LocalMapping.cc:632-696) for the current keyframe against the map as it stands
+    std::vector<CullingVote> KeyFrameCullingVotes(int32_t mnId)
+    {
+        std::vector<int32_t> a((size_t)maxkf_), b((size_t)maxkf_), c((size_t)maxkf_), d((size_t)maxkf_); int32_t n = 0;
+        check(sgx_covis_keyframe_culling(h_, mnId, maxkf_, a.data(), &n, b.data(), c.data(), d.data()), "sgx_covis_keyframe_culling");
+        std::vector<CullingVote> v; for (int32_t j = 0; j < n; j++) v.push_back(CullingVote{a[(size_t)j], b[(size_t)j], c[(size_t)j], d[(size_t)j]});
+        return v;
+    }
+    // LocalMapping::KeyFrameCulling with its SetBadFlag between the candidates: query, erase the first voted candidate, query again, go on behind it in the first list
+    std::vector<int32_t> KeyFrameCulling(int32_t mnId)
+    {
+        std::vector<CullingVote> votes = KeyFrameCullingVotes(mnId);
+        std::vector<int32_t> first, erased; for (const CullingVote &v : votes) first.push_back(v.mnId);
+        for (size_t pos = 0; pos < first.size(); pos++) {
+            bool voted = false;
+            for (const CullingVote &v : votes) if (v.mnId == first[pos] && v.cull) voted = true;
+            if (!voted) continue;
+            EraseKeyFrame(first[pos]); erased.push_back(first[pos]);
+            votes = KeyFrameCullingVotes(mnId);
+        }
+        return erased;
+    }
+    sgx_covis *handle() const { return h_; }
+private:
+    template <class F> std::vector<std::pair<int32_t, int32_t>> pairs(F fn, int32_t mnId, const char *what)
+    {
+        std::vector<int32_t> a((size_t)maxkf_), b((size_t)maxkf_); int32_t n = 0;
+        check(fn(h_, mnId, a.data(), b.data(), &n), what);
+        std::vector<std::pair<int32_t, int32_t>> v; for (int32_t j = 0; j < n; j++) v.emplace_back(a[(size_t)j], b[(size_t)j]);
+        return v;
+    }
+    sgx_covis *h_ = nullptr; int maxkf_, cap_;
+};
+
 // the two OpenCV calls of Frame::RmDynamicPointWithSemanticAndGeometry (Frame.cc:445, :469-472)
 class OpticalFlowLK {                                                // cv::calcOpticalFlowPyrLK(cur, prev, pts, nextPts, status, err, Size(21,21), 3, TermCriteria(ITER|EPS, 30, 0.01))
 public:
