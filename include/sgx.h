@@ -494,6 +494,75 @@ int sgx_cloud_build(sgx_cloud *h, const float *depth, const uint8_t *color, cons
  * from a double product (cv::gemm); Q = Eigen::Quaterniond(Rwc as double); origin = (twc[2], -twc[0], -twc[1]); rotation = (Q.z, -Q.x, -Q.y, Q.w) in tf's x, y, z, w. */
 int sgx_cloud_camera_to_map_tf(const float *tcw, double origin[3], double rotation[4]);
 
+/* ---- OctomapServer (src/octomap_server/src/OctomapServer.cpp) -----------------------------------------------------------------------------------------------------
+ * The occupancy map that consumes the keyframe cloud: insertCloudCallback's non-ground branch (:261-354: transformPointCloud, three PassThrough filters), insertScan
+ * (:356-480: one ray per point, free cells on the rays, occupied end cells, one update per cell and scan) and the tree queries of publishAll (:484-: the occupied /
+ * free cell centres, the projected 2-D grid of handlePreNodeTraversal / update2DMap with m_projectCompleteMap, :934-1107).  Occupancy only: no colour, no ground
+ * filter, no speckle filter, no serialisation, max_depth 16.  octomap is restated from its published algorithm (tests/octomap_ref.py), unpinned.
+ * The map is kept as depth-16 cells; octomap's maximally pruned tree gives every cell the same log-odds (tests/test_octomap_emu.py holds the equivalence).
+ * Keys: coordToKeyChecked(c) = (int)floor((1.0 / res) * (double)c) + 32768, valid in [0, 65536); keyToCoord(k) = ((double)(k - 32768) + 0.5) * res.
+ * Defaults are octomap_server's: res 0.05, prob_hit 0.7, prob_miss 0.4, thres_min 0.12, thres_max 0.97, max_range -1 (none), bounds -/+DBL_MAX, min_size 0.
+ * sgx_octomap_create: SGX_ERR_INVALID for a res that is not finite or <= 0, a probability or clamp outside (0, 1), thres_min >= thres_max, a NaN bound,
+ * max_bricks outside [1, 2^17] (the cells query ranks the B bricks by counting, B^2 comparisons), max_points_per_scan outside [1, 2^24].  Device memory: 2 072 bytes per brick of 8 x 8 x 8 cells, 144 per table slot (the next
+ * power of two >= 2 * max_bricks slots) and 32 per point. */
+typedef struct sgx_octomap_params {
+    double res, prob_hit, prob_miss, thres_min, thres_max;
+    double max_range;                                            /* < 0: none */
+    double pointcloud_min_x, pointcloud_max_x, pointcloud_min_y, pointcloud_max_y, pointcloud_min_z, pointcloud_max_z;       /* PassThrough limits, taken as float */
+    double occupancy_min_z, occupancy_max_z;                     /* the z window of the cell lists and the grid */
+    double min_size_x, min_size_y;                               /* padding of the 2-D grid */
+} sgx_octomap_params;
+#define SGX_OCTOMAP_ORIGIN_OUT_OF_RANGE 1   /* the sensor origin has no key: every ray is invalid, end cells are still inserted (:359-363, :400-410) */
+#define SGX_OCTOMAP_RAY_LEFT_KEYSPACE 2     /* a ray would have stepped outside [0, 65535] (octomap only asserts): the ray ends there */
+#define SGX_OCTOMAP_MAP_FULL 4              /* the scan needs more than max_bricks bricks: the map is unchanged; RAY_LEFT_KEYSPACE is not reported for such a scan */
+#define SGX_OCTOMAP_TOO_MANY_POINTS 8       /* more than max_points_per_scan points: the map is unchanged, only n_in and flags are set */
+typedef struct sgx_octomap_record {
+    int32_t n_in, n_passed;                 /* points of the scan, points behind the PassThrough filters */
+    int32_t n_truncated;                    /* beyond max_range: the ray ends at new_end, which is free */
+    int32_t n_bad_end_key, n_invalid_rays;  /* end points without a key; rays computeRayKeys refuses */
+    int32_t n_free_updates, n_occupied_updates, n_new_cells;    /* cells that got a miss (free set minus occupied set) / a hit; cells unknown before; 0 when MAP_FULL */
+    int32_t bbx_min[3], bbx_max[3];         /* m_updateBBXMin / Max: the origin key (when valid) and every inserted end key; 65535 / 0 when there is none */
+    int32_t flags, reserved;
+} sgx_octomap_record;
+typedef struct sgx_octomap_cell { uint16_t key[3], reserved; float x, y, z, logodds; } sgx_octomap_cell;   /* the centre is (float)keyToCoord per axis */
+typedef struct sgx_octomap_bounds_t { int32_t n_known, n_occupied, n_free, n_bricks, key_min[3], key_max[3]; } sgx_octomap_bounds_t;   /* occupied: logodds >= 0.0f; 65535 / 0 when empty */
+#define SGX_OCTOMAP_GRID_EMPTY 1             /* no known cell: width = height = 0 */
+#define SGX_OCTOMAP_GRID_KEY_OUT_OF_RANGE 2  /* a padded corner has no key (the reference logs an error and publishes nothing): width = height = 0 */
+typedef struct sgx_octomap_grid_header_t {
+    int32_t width, height, flags, reserved;
+    int32_t pad_min_key[2], pad_max_key[2], key_min_z, key_max_z;
+    double resolution, origin_x, origin_y;  /* nav_msgs::MapMetaData: origin = (float)keyToCoord(pad_min_key) - res * 0.5 */
+} sgx_octomap_grid_header_t;
+typedef struct sgx_octomap sgx_octomap;
+int sgx_octomap_create(const sgx_octomap_params *params, int max_bricks, int max_points_per_scan, sgx_octomap **out);      /* *out is NULL after a failed call */
+void sgx_octomap_destroy(sgx_octomap *h);
+/* The synchronous entries (reset, insert, bounds, cells, project) run on the null stream and wait for it only: after sgx_octomap_insert_batch_dev or a _dev query on a
+ * non-blocking stream the caller synchronises that stream first. */
+int sgx_octomap_reset(sgx_octomap *h);                                                                    /* the map becomes empty, its capacity stays; synchronous */
+/* n_scans scans in order, one asynchronous launch sequence on `stream`, nothing read back.  Scan i: *(int32_t *)((char *)n_points_dev + i * n_points_stride_bytes)
+ * points at points_dev + i * point_stride (rgba ignored), the row-major 4 x 4 float sensorToWorld at sensor_to_world_dev + 16 * i, its record at records_dev + i.
+ * n_points_dev may point at sgx_cloud_result.n_points (stride sizeof(sgx_cloud_result)) and points_dev at the output of sgx_cloud_build_batch_dev (stride
+ * width * height): the chain needs no copy.  A scan that sets MAP_FULL or TOO_MANY_POINTS leaves the map as every query sees it; the later scans are applied. */
+int sgx_octomap_insert_batch_dev(sgx_octomap *h, const sgx_cloud_point *points_dev, int64_t point_stride, const int32_t *n_points_dev, int64_t n_points_stride_bytes,
+                                 const float *sensor_to_world_dev, int n_scans, sgx_octomap_record *records_dev, void *stream);
+int sgx_octomap_insert(sgx_octomap *h, const sgx_cloud_point *points, int n_points, const float *sensor_to_world, sgx_octomap_record *record);   /* host pointers, synchronous */
+int sgx_octomap_bounds(sgx_octomap *h, sgx_octomap_bounds_t *out);                                        /* synchronous */
+/* the occupied (occupied != 0) or free cells with z + res / 2 > occupancy_min_z && z - res / 2 < occupancy_max_z in ascending Morton code of the key (bit 3i = x bit i,
+ * 3i + 1 = y, 3i + 2 = z): the order of octomap's leaf iterator.  *n_cells is the true count; the first cap are written; sgx_octomap_cells answers SGX_ERR_OVERFLOW
+ * beyond cap.  One cells query of a handle at a time. */
+int sgx_octomap_cells_dev(sgx_octomap *h, int occupied, sgx_octomap_cell *cells_dev, int cap, int32_t *n_cells_dev, void *stream);
+int sgx_octomap_cells(sgx_octomap *h, int occupied, sgx_octomap_cell *cells, int cap, int32_t *n_cells);
+/* OcTree::search at depth 16 for m keys (3 uint16 each) or m points (3 floats each), exactly one of the two pointers: the log-odds, a quiet NaN for unknown */
+int sgx_octomap_search_dev(sgx_octomap *h, const uint16_t *keys_dev, const float *points_dev, int m, float *logodds_dev, void *stream);
+/* the grid's header from the bounds (host code) and the grid: width x height int8, index x + y * width, -1 unknown, 100 when a passing occupied cell lies in the
+ * column, 0 when only free ones do.  sgx_octomap_project = bounds + header + grid from host memory (SGX_ERR_OVERFLOW when width * height > cap). */
+int sgx_octomap_grid_header(const sgx_octomap *h, const sgx_octomap_bounds_t *bounds, sgx_octomap_grid_header_t *out);
+int sgx_octomap_project_dev(sgx_octomap *h, const sgx_octomap_grid_header_t *header, int8_t *grid_dev, void *stream);
+int sgx_octomap_project(sgx_octomap *h, sgx_octomap_grid_header_t *header, int8_t *grid, int64_t cap);
+/* sensorToWorld from the (origin, rotation = x, y, z, w) of sgx_cloud_camera_to_map_tf as tf + pcl_ros::transformAsMatrix form it: tf::Matrix3x3::setRotation in
+ * double (s = 2 / |q|^2), every entry and the origin cast to float; row-major 4 x 4 */
+int sgx_octomap_sensor_to_world(const double origin[3], const double rotation[4], float out[16]);
+
 /* ---- ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (src/sg-slam/include/ORBVocabulary.h:31-32) ----------------------------------------------
  * The bag-of-words transform behind Frame::ComputeBoW (src/sg-slam/src/Frame.cc:422-429) and KeyFrame::ComputeBoW (src/sg-slam/src/KeyFrame.cc:60-69):
  *     mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4)          src/sg-slam/Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1139-1206

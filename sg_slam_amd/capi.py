@@ -85,6 +85,24 @@ SGX_CLOUD_FEW_POINTS, SGX_CLOUD_LEAF_TOO_SMALL = 1, 2
 SGX_CLOUD_MAX_BOXES = 128
 
 
+class OctomapParams(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ('res', 'prob_hit', 'prob_miss', 'thres_min', 'thres_max', 'max_range', 'pointcloud_min_x', 'pointcloud_max_x', 'pointcloud_min_y',
+                                          'pointcloud_max_y', 'pointcloud_min_z', 'pointcloud_max_z', 'occupancy_min_z', 'occupancy_max_z', 'min_size_x', 'min_size_y')]
+
+
+class OctomapGridHeader(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('width', 'height', 'flags', 'reserved')] + [('pad_min_key', C.c_int32 * 2), ('pad_max_key', C.c_int32 * 2), ('key_min_z', C.c_int32),
+                                                                                     ('key_max_z', C.c_int32)] + [(k, C.c_double) for k in ('resolution', 'origin_x', 'origin_y')]
+
+
+OCTOMAP_RECORD_DTYPE = np.dtype([(k, 'i4') for k in ('n_in', 'n_passed', 'n_truncated', 'n_bad_end_key', 'n_invalid_rays', 'n_free_updates', 'n_occupied_updates',
+                                                     'n_new_cells')] + [('bbx_min', 'i4', 3), ('bbx_max', 'i4', 3), ('flags', 'i4'), ('reserved', 'i4')])   # sgx_octomap_record, 64 B
+OCTOMAP_CELL_DTYPE = np.dtype([('key', 'u2', 3), ('reserved', 'u2'), ('x', 'f4'), ('y', 'f4'), ('z', 'f4'), ('logodds', 'f4')])   # sgx_octomap_cell, 24 B
+OCTOMAP_BOUNDS_DTYPE = np.dtype([('n_known', 'i4'), ('n_occupied', 'i4'), ('n_free', 'i4'), ('n_bricks', 'i4'), ('key_min', 'i4', 3), ('key_max', 'i4', 3)])   # sgx_octomap_bounds_t, 40 B
+SGX_OCTOMAP_ORIGIN_OUT_OF_RANGE, SGX_OCTOMAP_RAY_LEFT_KEYSPACE, SGX_OCTOMAP_MAP_FULL, SGX_OCTOMAP_TOO_MANY_POINTS = 1, 2, 4, 8
+SGX_OCTOMAP_GRID_EMPTY, SGX_OCTOMAP_GRID_KEY_OUT_OF_RANGE = 1, 2
+
+
 class InitReport(C.Structure):
     _fields_ = [('SH', C.c_float), ('SF', C.c_float), ('RH', C.c_float), ('model', C.c_int32), ('n_matches', C.c_int32), ('n_inliers_h', C.c_int32),
                 ('n_inliers_f', C.c_int32), ('n_hyp', C.c_int32), ('best_hyp', C.c_int32), ('n_good', C.c_int32 * 8), ('cos_parallax', C.c_float * 8),
@@ -145,6 +163,8 @@ SYMBOLS = [
     'sgx_covis_set_points_bad', 'sgx_covis_replace_point', 'sgx_covis_erase_keyframe', 'sgx_covis_get_weights', 'sgx_covis_get_ordered', 'sgx_covis_best_covisibles',
     'sgx_covis_get_tree', 'sgx_covis_get_observations', 'sgx_covis_get_keyframe_points', 'sgx_covis_update_connections_batch_dev', 'sgx_covis_local_map_batch_dev',
     'sgx_covis_keyframe_culling_batch_dev', 'sgx_covis_update_connections', 'sgx_covis_local_map', 'sgx_covis_keyframe_culling',
+    'sgx_octomap_create', 'sgx_octomap_destroy', 'sgx_octomap_reset', 'sgx_octomap_insert_batch_dev', 'sgx_octomap_insert', 'sgx_octomap_bounds', 'sgx_octomap_cells_dev',
+    'sgx_octomap_cells', 'sgx_octomap_search_dev', 'sgx_octomap_grid_header', 'sgx_octomap_project_dev', 'sgx_octomap_project', 'sgx_octomap_sensor_to_world',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -347,6 +367,19 @@ class SgxLib:
         d.sgx_covis_update_connections.argtypes = [vp, C.c_int32, vp]
         d.sgx_covis_local_map.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
         d.sgx_covis_keyframe_culling.argtypes = [vp, C.c_int32, C.c_int, vp, vp, vp, vp, vp]
+        d.sgx_octomap_create.argtypes = [C.POINTER(OctomapParams), C.c_int, C.c_int, C.POINTER(vp)]
+        d.sgx_octomap_destroy.argtypes = [vp]; d.sgx_octomap_destroy.restype = None
+        d.sgx_octomap_reset.argtypes = [vp]
+        d.sgx_octomap_insert_batch_dev.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int, vp, vp]
+        d.sgx_octomap_insert.argtypes = [vp, vp, C.c_int, vp, vp]
+        d.sgx_octomap_bounds.argtypes = [vp, vp]
+        d.sgx_octomap_cells_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
+        d.sgx_octomap_cells.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+        d.sgx_octomap_search_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+        d.sgx_octomap_grid_header.argtypes = [vp, vp, C.POINTER(OctomapGridHeader)]
+        d.sgx_octomap_project_dev.argtypes = [vp, C.POINTER(OctomapGridHeader), vp, vp]
+        d.sgx_octomap_project.argtypes = [vp, C.POINTER(OctomapGridHeader), vp, C.c_int64]
+        d.sgx_octomap_sensor_to_world.argtypes = [vp, vp, vp]
         d.sgx_match_search_by_bow_kf.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 4 + [C.c_float, C.c_int, vp, vp]
         d.sgx_match_fuse_search.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 6 + [C.POINTER(Camera), vp, vp, C.c_int, C.c_float, C.c_float, vp, vp, vp]
         d.sgx_hamming_matrix_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]

@@ -5,6 +5,7 @@
 // cv::Mat / Frame* so this header has no OpenCV dependency.  INTEGRATION.md shows the three-line glue that
 // adapts cv::Mat / Frame to these views inside the reference tree.  Header-only; link with -lsgx.
 #pragma once
+#include <cfloat>
 #include <cstdint>
 #include <cstring>
 #include <cmath>
@@ -785,6 +786,59 @@ public:
     sgx_cloud *handle() { return h_; }
 private:
     sgx_cloud *h_ = nullptr; int N_; float cam_[4];
+};
+
+// octomap_server's OctomapServer (src/octomap_server/src/OctomapServer.cpp) over sgx_octomap_*: insertCloudCallback for the local map of a keyframe (:261-354, the
+// non-ground branch, and insertScan :356-480) and what publishAll derives from the tree (:484-): the occupied / free cell centres in the order of octomap's leaf
+// iterator and the projected nav_msgs::OccupancyGrid.  Occupancy only; the parameters are octomap_server's, with its defaults.
+struct OccupancyGrid { sgx_octomap_grid_header_t info; std::vector<int8_t> data; };       // data: row-major x + y * width, -1 / 0 / 100
+class OctomapServer {
+public:
+    static sgx_octomap_params defaults()
+    {
+        sgx_octomap_params p; std::memset(&p, 0, sizeof p);
+        p.res = 0.05; p.prob_hit = 0.7; p.prob_miss = 0.4; p.thres_min = 0.12; p.thres_max = 0.97; p.max_range = -1.0;
+        p.pointcloud_min_x = p.pointcloud_min_y = p.pointcloud_min_z = p.occupancy_min_z = -DBL_MAX;
+        p.pointcloud_max_x = p.pointcloud_max_y = p.pointcloud_max_z = p.occupancy_max_z = DBL_MAX;
+        return p;
+    }
+    explicit OctomapServer(const sgx_octomap_params &p = defaults(), int max_bricks = 1 << 14, int max_points_per_scan = 1 << 16)
+    { check(sgx_octomap_create(&p, max_bricks, max_points_per_scan, &h_), "sgx_octomap_create"); }
+    ~OctomapServer() { if (h_) sgx_octomap_destroy(h_); }
+    OctomapServer(const OctomapServer &) = delete; OctomapServer &operator=(const OctomapServer &) = delete;
+    // one cloud in the sensor frame with the transform camera_to_map_tf gave for its keyframe (tf + pcl_ros::transformAsMatrix)
+    sgx_octomap_record insertCloud(const std::vector<sgx_cloud_point> &cloud, const double origin[3], const double rotation[4])
+    {
+        float m[16]; sgx_octomap_record rec;
+        check(sgx_octomap_sensor_to_world(origin, rotation, m), "sgx_octomap_sensor_to_world");
+        check(sgx_octomap_insert(h_, cloud.data(), (int)cloud.size(), m, &rec), "sgx_octomap_insert");
+        return rec;
+    }
+    sgx_octomap_record insertCloud(const LocalMap &m) { return insertCloud(m.points, m.origin, m.rotation); }
+    sgx_octomap_bounds_t bounds() { sgx_octomap_bounds_t b; check(sgx_octomap_bounds(h_, &b), "sgx_octomap_bounds"); return b; }
+    std::vector<sgx_octomap_cell> cells(bool occupied)
+    {
+        const sgx_octomap_bounds_t b = bounds();
+        std::vector<sgx_octomap_cell> out((size_t)(occupied ? b.n_occupied : b.n_free)); int32_t n = 0;
+        check(sgx_octomap_cells(h_, occupied ? 1 : 0, out.data(), (int)out.size(), &n), "sgx_octomap_cells");
+        out.resize((size_t)n);
+        return out;
+    }
+    OccupancyGrid projectedMap()
+    {
+        OccupancyGrid g;                                                                     // one call when the grid still fits the last size, two when it has grown
+        g.data.resize(grid_cells_);
+        int rc = sgx_octomap_project(h_, &g.info, g.data.data(), (int64_t)g.data.size());
+        grid_cells_ = (size_t)g.info.width * (size_t)g.info.height;
+        if (rc == SGX_ERR_OVERFLOW) { g.data.resize(grid_cells_); rc = sgx_octomap_project(h_, &g.info, g.data.data(), (int64_t)g.data.size()); }
+        check(rc, "sgx_octomap_project");
+        g.data.resize(grid_cells_);
+        return g;
+    }
+    void reset() { check(sgx_octomap_reset(h_), "sgx_octomap_reset"); }
+    sgx_octomap *handle() { return h_; }
+private:
+    sgx_octomap *h_ = nullptr; size_t grid_cells_ = 0;
 };
 
 // Frame::ComputeStereoMatches (Frame.cc:716-890) as the stereo constructor Frame::Frame(imLeft, imRight, ...) calls it (:70-99): the two extractors of the reference
