@@ -563,6 +563,71 @@ int sgx_octomap_project(sgx_octomap *h, sgx_octomap_grid_header_t *header, int8_
  * double (s = 2 / |q|^2), every entry and the origin cast to float; row-major 4 x 4 */
 int sgx_octomap_sensor_to_world(const double origin[3], const double rotation[4], float out[16]);
 
+/* ---- The global map (src/sg-slam/src/PointcloudMapping.cc:332-360) --------------------------------------------------------------------------------------------------
+ * MapViewer's accumulating dense cloud (/SG_SLAM/Global_Point_Clouds, is_global_pc_reconstruction): `*globalMap += *temp_globalMap` for every keyframe, and
+ * voxel_global + sor_global over the WHOLE accumulated map when no keyframe is waiting or count > global_pc_update_kf_threshold.  The map is a device-resident list
+ * of sgx_cloud_point in ROS axes (what SGX_CLOUD_WORLD builds).  PCL is restated as for sgx_cloud (tests/globalmap_ref.py), unpinned.
+ * Append: the cloud's points go behind the points already there, in order; a point that is not finite is stored, as PCL's operator+= does.
+ * Consolidate: pcl::VoxelGrid (leaf) then pcl::StatisticalOutlierRemoval (mean_k, stddev_mul) over the whole map, exactly as stated for sgx_cloud (header, ijk,
+ * ascending idx, float running sums in ascending point index, so an old map point comes before the points appended after it; colour truncation; distances, K-th
+ * smallest, tie rule, mean / threshold); a point that is not finite joins no voxel and is gone afterwards; the survivors, in ascending idx, replace the map.  There
+ * is no axis map: the cloud is in ROS axes already.
+ * Defined cases:
+ *  1. a consolidation that sgx_cloud would answer with LEAF_TOO_SMALL or FEW_POINTS (<= mean_k voxel points, an empty map included) leaves the map exactly as it
+ *     was and sets SGX_GMAP_LEAF_TOO_SMALL / SGX_GMAP_FEW_POINTS in the record: a refused call does not wipe an accumulated map;
+ *  2. an appended cloud that does not fit into max_points is refused whole: SGX_GMAP_FULL in its record, offset -1, nothing appended; the later clouds of the same
+ *     batch are still tried, in order, against the running size: the outcome is a function of the sizes alone.  A negative count is an empty cloud;
+ *  3. sgx_globalmap_create: SGX_ERR_INVALID for mean_k < 1, a leaf that is not finite or <= 0, a NaN stddev_mul, max_points < 1 or > SGX_GMAP_MAX_POINTS.
+ * SGX_GMAP_MAX_POINTS = 2^22: the sort's one-workgroup scan (k_cloud_scan) then walks 16 * 2048 tile counts, 128 a lane, and every index is far inside an int.
+ * Device memory: 77 bytes per point of capacity.
+ * The schedule is host code and the caller's (sg_slam_amd/globalmap.py: GlobalMapSchedule; sgx::GlobalMap::update): count starts at 0; after every appended
+ * keyframe `if (!pending || count > threshold)` consolidate, publish, and count = 0 only when the published cloud is not empty; then count++ in every case.
+ * The consolidation record: n_points_in (the map before), n_voxels (voxel points before the outlier filter), n_points (the map after the call: n_points_in when a
+ * flag is set), flags, mean and thr of the outlier filter, and two implementation figures that are equal between the device and the emulator:
+ * wider_window_points (voxel points whose first cell window was not proven and that searched windows of doubled radius, up to SGX_GMAP_MAX_RADIUS cells) and
+ * whole_cloud_points (voxel points that searched the whole voxel cloud: those that the widest window did not prove, and every point when there is no search grid). */
+#define SGX_GMAP_FEW_POINTS 1
+#define SGX_GMAP_LEAF_TOO_SMALL 2
+#define SGX_GMAP_FULL 4
+#define SGX_GMAP_MAX_POINTS (1 << 22)
+#define SGX_GMAP_MAX_RADIUS 16
+typedef struct sgx_globalmap_params {
+    double sor_stddev_mul;                                  /* PointCloudMapping.Sor_Global_StddevMulThresh */
+    int32_t sor_mean_k;                                     /* PointCloudMapping.Sor_Global_MeanK */
+    float voxel_leaf_size;                                  /* PointCloudMapping.Voxel_Global_LeafSize */
+} sgx_globalmap_params;
+typedef struct sgx_globalmap_append_record {
+    int32_t n_in;                                           /* points of the cloud */
+    int32_t offset;                                         /* where its first point went; -1 when refused */
+    int32_t map_size;                                       /* the map's size after this cloud */
+    int32_t flags;                                          /* SGX_GMAP_FULL */
+} sgx_globalmap_append_record;
+typedef struct sgx_globalmap_result {
+    int32_t n_points_in, n_voxels, n_points, flags, wider_window_points, whole_cloud_points;
+    double mean, thr;
+} sgx_globalmap_result;
+typedef struct sgx_globalmap sgx_globalmap;
+int sgx_globalmap_create(int max_points, const sgx_globalmap_params *params, sgx_globalmap **out);       /* *out is NULL after a failed call */
+void sgx_globalmap_destroy(sgx_globalmap *h);
+/* The synchronous entries (reset, append, consolidate, size, read) run on the null stream and wait for it only: after a _dev entry on a non-blocking stream the
+ * caller synchronises that stream first. */
+int sgx_globalmap_reset(sgx_globalmap *h);                                                               /* the map becomes empty, its capacity stays; synchronous */
+/* n_clouds (at most 65535) clouds in order, one asynchronous launch sequence on `stream`, nothing read back.  Cloud i: *(int32_t *)((char *)n_points_dev + i *
+ * n_points_stride_bytes) points at points_dev + i * point_stride, its record at records_dev + i.  n_points_dev may point at sgx_cloud_result.n_points (stride
+ * sizeof(sgx_cloud_result)) and points_dev at the output of sgx_cloud_build_batch_dev (stride width * height): the chain depth image -> world cloud -> global map
+ * needs no copy.  The clouds must not overlap the map. */
+int sgx_globalmap_append_batch_dev(sgx_globalmap *h, const sgx_cloud_point *points_dev, int64_t point_stride, const int32_t *n_points_dev, int64_t n_points_stride_bytes,
+                                   int n_clouds, sgx_globalmap_append_record *records_dev, void *stream);
+int sgx_globalmap_append(sgx_globalmap *h, const sgx_cloud_point *points, int n_points, sgx_globalmap_append_record *record);     /* host pointers, synchronous */
+/* voxel_global + sor_global over the whole map; one asynchronous launch sequence on `stream`, the record goes to result_dev.  One consolidation of a handle at a time. */
+int sgx_globalmap_consolidate_dev(sgx_globalmap *h, sgx_globalmap_result *result_dev, void *stream);
+int sgx_globalmap_consolidate(sgx_globalmap *h, sgx_globalmap_result *result);                           /* synchronous */
+int sgx_globalmap_size(sgx_globalmap *h, int32_t *n_points);                                             /* synchronous */
+/* *n_points is the true size; the first cap points are written; SGX_ERR_OVERFLOW beyond cap.  Synchronous. */
+int sgx_globalmap_read(sgx_globalmap *h, sgx_cloud_point *points, int cap, int32_t *n_points);
+/* the map and its size on the device, for a consumer on the same stream (both stay valid, at fixed addresses, for the life of the handle) */
+int sgx_globalmap_points_dev(sgx_globalmap *h, const sgx_cloud_point **points_dev, const int32_t **n_points_dev);
+
 /* ---- ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (src/sg-slam/include/ORBVocabulary.h:31-32) ----------------------------------------------
  * The bag-of-words transform behind Frame::ComputeBoW (src/sg-slam/src/Frame.cc:422-429) and KeyFrame::ComputeBoW (src/sg-slam/src/KeyFrame.cc:60-69):
  *     mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4)          src/sg-slam/Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1139-1206

@@ -42,6 +42,13 @@ int sgx_obj3d_debug_read(sgx_obj3d *h, int job, uint8_t *kept, int32_t *labels, 
  * ROS axes in SGX_CLOUD_WORLD), dist[i] = the mean distance of point i to its mean_k nearest neighbours, kept[i] = the filter kept it (each destination may be NULL).
  * Synchronises; SGX_ERR_OVERFLOW when *n > cap. */
 int sgx_cloud_debug_read(sgx_cloud *h, int image, sgx_cloud_point *voxels, float *dist, uint8_t *kept, int cap, int *n);
+/* test tap: the handle's last consolidation before the outlier filter: its *n voxel points in ascending idx, dist and kept as above, tier[i] = the cell radius of the
+ * window that was proven for point i (the first window's radius, or a doubled one up to SGX_GMAP_MAX_RADIUS), 0 when the point searched the whole voxel cloud (each
+ * destination may be NULL).  Synchronises; SGX_ERR_OVERFLOW when *n > cap. */
+int sgx_globalmap_debug_read(sgx_globalmap *h, sgx_cloud_point *voxels, float *dist, uint8_t *kept, uint8_t *tier, int cap, int *n);
+/* test / tuning tap: the widest window the second search tier may try, 0 .. SGX_GMAP_MAX_RADIUS (the default).  At or below the first window's radius every point
+ * that the first window does not prove searches the whole voxel cloud, as the keyframe path does: the A/B of DESIGN.md 9j, and the tests of that path. */
+int sgx_globalmap_debug_max_radius(sgx_globalmap *h, int max_radius);
 int sgx_debug_corun_bf16(int blocks, int iters, int launches, void *stream);      /* test tap: `launches` launches of a kernel that only issues bf16 matrix products, asynchronous on `stream` (co-runner of the packed-fp32 regression test) */
 /* test tap: DetectionOutput + detect() filtering alone on caller-supplied head outputs (host arrays: loc batch x num_priors x 4, conf batch x num_priors x num_class) */
 int sgx_det_debug_detection_output(sgx_det *h, const float *loc, const float *conf, int batch, sgx_det_result *results);

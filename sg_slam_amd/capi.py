@@ -103,6 +103,17 @@ SGX_OCTOMAP_ORIGIN_OUT_OF_RANGE, SGX_OCTOMAP_RAY_LEFT_KEYSPACE, SGX_OCTOMAP_MAP_
 SGX_OCTOMAP_GRID_EMPTY, SGX_OCTOMAP_GRID_KEY_OUT_OF_RANGE = 1, 2
 
 
+class GlobalMapParams(C.Structure):
+    _fields_ = [('sor_stddev_mul', C.c_double), ('sor_mean_k', C.c_int32), ('voxel_leaf_size', C.c_float)]
+
+
+GMAP_APPEND_DTYPE = np.dtype([('n_in', 'i4'), ('offset', 'i4'), ('map_size', 'i4'), ('flags', 'i4')])   # sgx_globalmap_append_record, 16 B
+GMAP_RESULT_DTYPE = np.dtype([('n_points_in', 'i4'), ('n_voxels', 'i4'), ('n_points', 'i4'), ('flags', 'i4'), ('wider_window_points', 'i4'), ('whole_cloud_points', 'i4'),
+                              ('mean', 'f8'), ('thr', 'f8')])   # sgx_globalmap_result, 40 B
+SGX_GMAP_FEW_POINTS, SGX_GMAP_LEAF_TOO_SMALL, SGX_GMAP_FULL = 1, 2, 4
+SGX_GMAP_MAX_POINTS, SGX_GMAP_MAX_RADIUS = 1 << 22, 16
+
+
 class InitReport(C.Structure):
     _fields_ = [('SH', C.c_float), ('SF', C.c_float), ('RH', C.c_float), ('model', C.c_int32), ('n_matches', C.c_int32), ('n_inliers_h', C.c_int32),
                 ('n_inliers_f', C.c_int32), ('n_hyp', C.c_int32), ('best_hyp', C.c_int32), ('n_good', C.c_int32 * 8), ('cos_parallax', C.c_float * 8),
@@ -165,6 +176,8 @@ SYMBOLS = [
     'sgx_covis_keyframe_culling_batch_dev', 'sgx_covis_update_connections', 'sgx_covis_local_map', 'sgx_covis_keyframe_culling',
     'sgx_octomap_create', 'sgx_octomap_destroy', 'sgx_octomap_reset', 'sgx_octomap_insert_batch_dev', 'sgx_octomap_insert', 'sgx_octomap_bounds', 'sgx_octomap_cells_dev',
     'sgx_octomap_cells', 'sgx_octomap_search_dev', 'sgx_octomap_grid_header', 'sgx_octomap_project_dev', 'sgx_octomap_project', 'sgx_octomap_sensor_to_world',
+    'sgx_globalmap_create', 'sgx_globalmap_destroy', 'sgx_globalmap_reset', 'sgx_globalmap_append_batch_dev', 'sgx_globalmap_append', 'sgx_globalmap_consolidate_dev',
+    'sgx_globalmap_consolidate', 'sgx_globalmap_size', 'sgx_globalmap_read', 'sgx_globalmap_points_dev',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -174,7 +187,7 @@ TAP_SYMBOLS = [
     'sgx_det_debug_set_block_fusion', 'sgx_det_debug_set_irb', 'sgx_det_debug_set_gemm', 'sgx_det_debug_time_ops', 'sgx_det_debug_run_step', 'sgx_flow_debug_read_level',
     'sgx_flow_debug_level_size', 'sgx_flow_debug_read_slot', 'sgx_debug_corun_bf16', 'sgx_pnp_debug_betas', 'sgx_obj3d_debug_read',
     'sgx_tracker_debug_set_describe_early', 'sgx_tracker_debug_set_boxes', 'sgx_tracker_debug_sync_trace', 'sgx_tracker_debug_fail_after',
-    'sgx_debug_devmem_fail_after', 'sgx_cloud_debug_read', 'sgx_stereo_debug_read',
+    'sgx_debug_devmem_fail_after', 'sgx_cloud_debug_read', 'sgx_stereo_debug_read', 'sgx_globalmap_debug_read', 'sgx_globalmap_debug_max_radius',
 ]
 
 
@@ -380,6 +393,16 @@ class SgxLib:
         d.sgx_octomap_project_dev.argtypes = [vp, C.POINTER(OctomapGridHeader), vp, vp]
         d.sgx_octomap_project.argtypes = [vp, C.POINTER(OctomapGridHeader), vp, C.c_int64]
         d.sgx_octomap_sensor_to_world.argtypes = [vp, vp, vp]
+        d.sgx_globalmap_create.argtypes = [C.c_int, C.POINTER(GlobalMapParams), C.POINTER(vp)]
+        d.sgx_globalmap_destroy.argtypes = [vp]; d.sgx_globalmap_destroy.restype = None
+        d.sgx_globalmap_reset.argtypes = [vp]
+        d.sgx_globalmap_append_batch_dev.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, vp]
+        d.sgx_globalmap_append.argtypes = [vp, vp, C.c_int, vp]
+        d.sgx_globalmap_consolidate_dev.argtypes = [vp, vp, vp]
+        d.sgx_globalmap_consolidate.argtypes = [vp, vp]
+        d.sgx_globalmap_size.argtypes = [vp, vp]
+        d.sgx_globalmap_read.argtypes = [vp, vp, C.c_int, vp]
+        d.sgx_globalmap_points_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         d.sgx_match_search_by_bow_kf.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 4 + [C.c_float, C.c_int, vp, vp]
         d.sgx_match_fuse_search.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 6 + [C.POINTER(Camera), vp, vp, C.c_int, C.c_float, C.c_float, vp, vp, vp]
         d.sgx_hamming_matrix_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
@@ -426,6 +449,9 @@ class SgxLib:
                 d.sgx_cloud_debug_read.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
             if hasattr(d, 'sgx_stereo_debug_read'):
                 d.sgx_stereo_debug_read.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+            if hasattr(d, 'sgx_globalmap_debug_read'):
+                d.sgx_globalmap_debug_read.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
+                d.sgx_globalmap_debug_max_radius.argtypes = [vp, C.c_int]
 
     def tap(self, name):
         """a test / tuning tap entry (include/sgx_debug.h); the product library has none"""

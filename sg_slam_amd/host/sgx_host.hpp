@@ -841,6 +841,57 @@ private:
     sgx_octomap *h_ = nullptr; size_t grid_cells_ = 0;
 };
 
+// MapViewer's globalMap (PointcloudMapping.cc:332-360, /SG_SLAM/Global_Point_Clouds) over sgx_globalmap_*: `*globalMap += *temp_globalMap` for every keyframe and
+// voxel_global + sor_global over the whole accumulated map on the reference's schedule.  temp_globalMap is the cloud sgx_cloud builds in SGX_CLOUD_WORLD mode.
+class GlobalMap {
+public:
+    // Voxel_Global_LeafSize, Sor_Global_MeanK, Sor_Global_StddevMulThresh, global_pc_update_kf_threshold of the reference's settings, and the map's capacity
+    GlobalMap(float Voxel_Global_LeafSize_, int Sor_Global_MeanK_, double Sor_Global_StddevMulThresh_, int global_pc_update_kf_threshold_, int max_points = 1 << 20)
+        : threshold_(global_pc_update_kf_threshold_)
+    {
+        sgx_globalmap_params p; std::memset(&p, 0, sizeof p);
+        p.sor_stddev_mul = Sor_Global_StddevMulThresh_; p.sor_mean_k = Sor_Global_MeanK_; p.voxel_leaf_size = Voxel_Global_LeafSize_;
+        check(sgx_globalmap_create(max_points, &p, &h_), "sgx_globalmap_create");
+    }
+    ~GlobalMap() { if (h_) sgx_globalmap_destroy(h_); }
+    GlobalMap(const GlobalMap &) = delete; GlobalMap &operator=(const GlobalMap &) = delete;
+    // *globalMap += *temp_globalMap (:339); a cloud that does not fit is refused whole (SGX_GMAP_FULL in the record)
+    sgx_globalmap_append_record append(const std::vector<sgx_cloud_point> &temp_globalMap)
+    {
+        sgx_globalmap_append_record r;
+        check(sgx_globalmap_append(h_, temp_globalMap.data(), (int)temp_globalMap.size(), &r), "sgx_globalmap_append");
+        return r;
+    }
+    sgx_globalmap_result consolidate() { sgx_globalmap_result r; check(sgx_globalmap_consolidate(h_, &r), "sgx_globalmap_consolidate"); return r; }
+    int size() { int32_t n = 0; check(sgx_globalmap_size(h_, &n), "sgx_globalmap_size"); return n; }
+    std::vector<sgx_cloud_point> points()
+    {
+        std::vector<sgx_cloud_point> out((size_t)size()); int32_t n = 0;
+        check(sgx_globalmap_read(h_, out.data(), (int)out.size(), &n), "sgx_globalmap_read");
+        out.resize((size_t)n);
+        return out;
+    }
+    // :340-359 after append: pending = CheckNewKeyFrames().  True when the map was consolidated and published into `published` (which may be empty: count is then
+    // not reset); count++ in every case
+    bool update(bool pending, std::vector<sgx_cloud_point> &published, sgx_globalmap_result *record = nullptr)
+    {
+        bool pub = false;
+        if (!pending || count_ > threshold_) {
+            const sgx_globalmap_result r = consolidate();
+            if (record) *record = r;
+            published = points(); pub = true;
+            if (!published.empty()) count_ = 0;
+        }
+        count_++;
+        return pub;
+    }
+    int count() const { return count_; }
+    void reset() { check(sgx_globalmap_reset(h_), "sgx_globalmap_reset"); count_ = 0; }
+    sgx_globalmap *handle() { return h_; }
+private:
+    sgx_globalmap *h_ = nullptr; int threshold_, count_ = 0;
+};
+
 // Frame::ComputeStereoMatches (Frame.cc:716-890) as the stereo constructor Frame::Frame(imLeft, imRight, ...) calls it (:70-99): the two extractors of the reference
 // (mpORBextractorLeft / Right, of one geometry) run on the two images, then mvuRight / mvDepth come from their keys, descriptors and pyramids; thin over sgx_stereo_*.
 // mvuRight is computed from the raw keypoints, as in the reference.

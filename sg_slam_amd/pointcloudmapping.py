@@ -87,7 +87,9 @@ class PointCloudMapping:
     """The reference class for one keyframe at a time: insertKeyFrame returns what MapViewer publishes for it.  params: settings.load_pointcloud_mapping;
     detector3d_params: settings.load_mapping (needed when is_octo_semantic_map_construction is set and objects are passed)"""
 
-    def __init__(self, params, width, height, cam, detector3d_params=None, lib=None, max_boxes=SGX_CLOUD_MAX_BOXES):
+    def __init__(self, params, width, height, cam, detector3d_params=None, lib=None, max_boxes=SGX_CLOUD_MAX_BOXES, global_map=None, global_map_max_points=1 << 20):
+        """global_map: settings.load_global_map's dict (default: the *_Global_* keys of params and a global_pc_update_kf_threshold of 25, the value of the reference's
+        example settings); global_map_max_points: the capacity of self.globalMap"""
         self.lib = lib or load(); self.params = dict(params); self.width = int(width); self.height = int(height); self.cam = np.ascontiguousarray(cam, 'f4').reshape(4)
         self.is_octo_semantic_map_construction = bool(params.get('is_octo_semantic_map_construction', 1))
         self.is_global_pc_reconstruction = bool(params.get('is_global_pc_reconstruction', 0))
@@ -98,13 +100,19 @@ class PointCloudMapping:
         if self.is_octo_semantic_map_construction and detector3d_params is not None:
             from .detector3d import Detector3D
             self.mpDetector3D = Detector3D(detector3d_params, width, height, cam, lib=self.lib)
-        self.last_record = None; self.temp_globalMap = None
+        self.last_record = None; self.temp_globalMap = None; self.globalMap = None; self.global_schedule = None; self.last_append_record = None
+        if self.is_global_pc_reconstruction:
+            from .globalmap import GlobalMap, GlobalMapSchedule
+            g = dict(global_map) if global_map is not None else dict(params)
+            self.globalMap = GlobalMap(g, global_map_max_points, lib=self.lib)
+            self.global_schedule = GlobalMapSchedule(self.globalMap, g.get('global_pc_update_kf_threshold', 25))
 
     def insertKeyFrame(self, color, depth, Tcw, objects2d=(), map_boxes=(), have_dynamic=False):
         """color: height x width x 3 bytes as mImRGB, depth: float metres, Tcw: the keyframe's float pose, objects2d: mvObjects2D (the tuples of
         detector.Detector2D.detect), map_boxes / have_dynamic: mvPotentialDynamicBorderForMapping / mbHaveDynamicObjectForMapping.  Returns (localMap as
         CLOUD_POINT_DTYPE records in ROS axes, (origin, rotation) of camera_to_map_tf).  Objects found go into mpDetector3D.mpObjectDatabase (:145-151, :189-190); with
-        is_global_pc_reconstruction the keyframe's filtered temp_globalMap is left in self.temp_globalMap."""
+        is_global_pc_reconstruction the keyframe's filtered temp_globalMap is left in self.temp_globalMap and appended to self.globalMap (:339; its record in
+        self.last_append_record); update_global runs the rest of :332-360."""
         Twc = pose_inverse(Tcw)
         if self.mpDetector3D is not None and len(objects2d) > 0:
             self.mpDetector3D.Detect(list(objects2d), depth, Twc)
@@ -112,10 +120,18 @@ class PointCloudMapping:
         self.last_record = rec
         if self.world is not None:
             self.temp_globalMap, self.last_world_record = self.world.build(depth, color, Twc, map_boxes, have_dynamic)
+            self.last_append_record = self.globalMap.append(self.temp_globalMap)
         return pts, camera_to_map_tf(Tcw, lib=self.lib)
 
+    def update_global(self, pending):
+        """the schedule of :340-359 after insertKeyFrame: pending = CheckNewKeyFrames().  When no keyframe is waiting or more than global_pc_update_kf_threshold
+        keyframes went by since the last publication, voxel_global + sor_global run over the whole of self.globalMap and the map is returned (CLOUD_POINT_DTYPE
+        records in ROS axes, what /SG_SLAM/Global_Point_Clouds carries); otherwise None"""
+        if self.global_schedule is None: return None
+        return self.global_schedule.update(pending)
+
     def close(self):
-        for o in (self.local, self.world, self.mpDetector3D):
+        for o in (self.local, self.world, self.mpDetector3D, self.globalMap):
             if o is not None: o.close()
 
     def __del__(self):

@@ -67,3 +67,13 @@ def load_pointcloud_mapping(path):
         out['Sor_%s_MeanK' % w] = int(d('Sor_%s_MeanK' % w)); out['Sor_%s_StddevMulThresh' % w] = d('Sor_%s_StddevMulThresh' % w)
         out['Voxel_%s_LeafSize' % w] = float(np.float32(d('Voxel_%s_LeafSize' % w)))
     return out
+
+
+def load_global_map(path):
+    """The parameters of MapViewer's global cloud (src/sg-slam/src/PointcloudMapping.cc:332-360): Voxel_Global_LeafSize (float), Sor_Global_MeanK,
+    Sor_Global_StddevMulThresh (double) of PointCloudMapping.*, and global_pc_update_kf_threshold, which the reference reads as
+    Detector3D.global_pc_update_kf_threshold (System.cc:114).  A missing key raises KeyError: the reference has no defaults for them."""
+    kv = parse(path)
+    d = lambda k: float(kv['PointCloudMapping.' + k])
+    return dict(Voxel_Global_LeafSize=float(np.float32(d('Voxel_Global_LeafSize'))), Sor_Global_MeanK=int(d('Sor_Global_MeanK')),
+                Sor_Global_StddevMulThresh=d('Sor_Global_StddevMulThresh'), global_pc_update_kf_threshold=int(float(kv['Detector3D.global_pc_update_kf_threshold'])))
