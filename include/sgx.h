@@ -814,6 +814,57 @@ int sgx_covis_local_map(sgx_covis *h, int n, int32_t *frame_mp, int min_obs, int
                         int mcap, int32_t *local_points, int32_t *local_obs, int32_t *n_local_points, sgx_covis_report *report);
 int sgx_covis_keyframe_culling(sgx_covis *h, int32_t kf_id, int max_cand, int32_t *cand, int32_t *n_cand, int32_t *n_redundant, int32_t *n_mps, int32_t *cull);
 
+/* The bundle-adjustment graph from the relation: the set selection at the top of Optimizer::LocalBundleAdjustment (src/sg-slam/src/Optimizer.cc:453-504) and its edge loop
+ * (:572-653), and the same edge loop over the whole map for Optimizer::BundleAdjustment (:49-150), as the index arrays of sgx_ba_problem.  A query of the handle like the
+ * three above: device pointers, asynchronous on `stream`, one launch sequence for the Q queries, nothing read back, integers only, two runs byte-identical, a batch of Q
+ * equal to Q single calls.  The handle is not changed, and no memory beyond the workspace of sgx_covis_create is used.
+ * mode = SGX_COVIS_BA_LOCAL, query q = keyframe kf_ids_dev[q]:
+ *   lLocalKeyFrames  = the keyframe, then GetVectorCovisibleKeyFrames() = its ordered list as its mode defines it (state, not a function of the weights), in list order,
+ *                      without the entries that are isBad() (erased keyframes a list still names, :461-468).
+ *   lLocalMapPoints  = the local keyframes in that order, each one's mvpMapPoints in index order, the first occurrence of every existing point (:472-486): the order of
+ *                      UpdateLocalPoints.  point_id_dev (rows of pcap) holds the ids in this order.
+ *   lFixedCameras    = every live keyframe that observes a local point and is not a local keyframe (:489-504).
+ *   poses            = local keyframes and fixed cameras together in ascending keyframe id (what sgx_ba_problem.poses wants): pose_id_dev (rows of max_keyframes) the ids,
+ *                      pose_fixed_dev 0 for a local keyframe, 1 for a fixed camera, 2 for a local keyframe whose id is 0 (:529, :762-768).  The order in which the
+ *                      reference first meets a fixed camera decides nothing and is not reported.
+ *   edges            = outer loop over the local points in their order, inner loop over the point's mObservations in ascending keyframe id (rule 1), one edge per
+ *                      observation: edge_pose_dev the index into the pose row, edge_point_dev the index into the point row, edge_kp_dev the keypoint index in that
+ *                      keyframe, edge_attr_dev the handle's attribute byte of that keypoint: the octave in bits 0-4 (SGX_COVIS_ATTR_OCTAVE), SGX_COVIS_ATTR_RIGHT for a
+ *                      stereo edge (mvuRight >= 0), SGX_COVIS_ATTR_CLOSE as add_keyframe defined it.  point_edge_begin_dev (rows of pcap + 1): point i's edges are
+ *                      [begin[i], begin[i + 1]), and begin[n_points] = n_edges.  An erased keyframe has no observations in the handle (rule 4), so the isBad() test
+ *                      of :589 never fires here: every observation of a local point is an edge.
+ * mode = SGX_COVIS_BA_GLOBAL (Q must be 1, kf_ids_dev is not read): poses = all live keyframes in ascending id, pose_fixed 2 for id 0 and 0 otherwise, n_fixed_kf = 0;
+ *   points = all existing points; edges as above.
+ * Defined where the reference is not:
+ *   8. the reference walks GetAllMapPoints(), a set<MapPoint*> in pointer order: the points of the global mode run in ascending point id.
+ *   9. the marks mnBALocalForKF / mnBAFixedForKF behave as fresh for every query: a query for keyframe 0 is one like any other (the reference initialises the marks to 0
+ *      and never runs local bundle adjustment for keyframe 0), and two queries for one keyframe give the same.
+ * Defined cases: a dead list entry is marked (:465) but not local, and having no observations it cannot come back as a fixed camera; a keyframe without points and
+ *   neighbours gives one pose, no points, no edges and point_edge_begin[0] = 0; keyframe 0 is pose_fixed 2 as a local keyframe (the queried one included) and 1 as a
+ *   fixed camera; a point met through several local keyframes keeps the place of its first occurrence; a stereo observation is one edge.
+ * Statuses: Q > max_queries, Q != 1 in global mode, an unknown mode or a missing array: SGX_ERR_INVALID for the call.  An unknown or erased keyframe id, a negative pcap or
+ *   ecap: SGX_ERR_INVALID as that query's status with nothing else of the query written.  More than pcap points or more than ecap edges: SGX_ERR_NOMEM as the query's
+ *   status; the report and the pose rows are whole, the first pcap points are written with point_edge_begin over them (begin[pcap] = the edges of those points), and the
+ *   edges of the points i with begin[i + 1] <= ecap, which fit wholly, are written; nothing is written past a row. */
+#ifndef SGX_COVIS_ATTR_BITS
+#define SGX_COVIS_ATTR_BITS
+enum { SGX_COVIS_ATTR_OCTAVE = 31, SGX_COVIS_ATTR_RIGHT = 32, SGX_COVIS_ATTR_CLOSE = 64 };
+#endif
+enum { SGX_COVIS_BA_LOCAL = 0, SGX_COVIS_BA_GLOBAL = 1 };
+typedef struct sgx_covis_ba_report {
+    int32_t status;                         /* SGX_OK, SGX_ERR_INVALID, SGX_ERR_NOMEM */
+    int32_t n_local_kf, n_fixed_kf;         /* lLocalKeyFrames.size(), lFixedCameras.size() */
+    int32_t n_poses, n_points, n_edges;     /* the true counts, also beyond pcap / ecap */
+    int32_t n_mono_edges, n_stereo_edges;   /* vpEdgesMono.size(), vpEdgesStereo.size() */
+} sgx_covis_ba_report;
+int sgx_covis_ba_graph_batch_dev(sgx_covis *h, int Q, int mode, const int32_t *kf_ids_dev, int32_t *pose_id_dev, uint8_t *pose_fixed_dev, int pcap,
+                                 int32_t *point_id_dev, int32_t *point_edge_begin_dev, int ecap, int32_t *edge_pose_dev, int32_t *edge_point_dev,
+                                 int32_t *edge_kp_dev, uint8_t *edge_attr_dev, sgx_covis_ba_report *report_dev, void *stream);
+/* One query from host memory, synchronous (kf_id is not read in global mode).  Written: the first n_poses of the pose rows (capacity max_keyframes), the first
+ * min(n_points, pcap) points and one more entry of point_edge_begin, and the edges that fit wholly.  The return value is the query's status. */
+int sgx_covis_ba_graph(sgx_covis *h, int mode, int32_t kf_id, int32_t *pose_id, uint8_t *pose_fixed, int pcap, int32_t *point_id, int32_t *point_edge_begin,
+                       int ecap, int32_t *edge_pose, int32_t *edge_point, int32_t *edge_kp, uint8_t *edge_attr, sgx_covis_ba_report *report);
+
 /* The colour conversion at the top of Tracking::GrabImageRGBD (src/sg-slam/src/Tracking.cc:214-227): cvtColor(CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) on
  * 8-bit images, OpenCV's fixed point (R*4899 + G*9617 + B*1868 + 8192) >> 14.  blue_first = !mbRGB.  Pitches in bytes, multiples of 4; pointers 4-byte aligned. */
 int sgx_frame_gray_from_color_batch_dev(int batch, int width, int height, const uint8_t *d_src, int src_pitch, int channels, int blue_first,

@@ -131,6 +131,8 @@ KFDB_REPORT_DTYPE = np.dtype([('n_sharing', 'i4'), ('max_common_words', 'i4'), (
 
 COVIS_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_counter', 'max_weight', 'max_kf', 'n_ordered', 'parent', 'n_stage1', 'n_local_kf', 'n_local_points',
                                                    'ref_tracked')])   # sgx_covis_report, 40 B
+COVIS_BA_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_local_kf', 'n_fixed_kf', 'n_poses', 'n_points', 'n_edges', 'n_mono_edges',
+                                                      'n_stereo_edges')])   # sgx_covis_ba_report, 32 B
 
 
 class OrbConfig(C.Structure):
@@ -173,7 +175,8 @@ SYMBOLS = [
     'sgx_covis_create', 'sgx_covis_destroy', 'sgx_covis_size', 'sgx_covis_info', 'sgx_covis_clear', 'sgx_covis_add_keyframe', 'sgx_covis_set_observations',
     'sgx_covis_set_points_bad', 'sgx_covis_replace_point', 'sgx_covis_erase_keyframe', 'sgx_covis_get_weights', 'sgx_covis_get_ordered', 'sgx_covis_best_covisibles',
     'sgx_covis_get_tree', 'sgx_covis_get_observations', 'sgx_covis_get_keyframe_points', 'sgx_covis_update_connections_batch_dev', 'sgx_covis_local_map_batch_dev',
-    'sgx_covis_keyframe_culling_batch_dev', 'sgx_covis_update_connections', 'sgx_covis_local_map', 'sgx_covis_keyframe_culling',
+    'sgx_covis_keyframe_culling_batch_dev', 'sgx_covis_update_connections', 'sgx_covis_local_map', 'sgx_covis_keyframe_culling', 'sgx_covis_ba_graph_batch_dev',
+    'sgx_covis_ba_graph',
     'sgx_octomap_create', 'sgx_octomap_destroy', 'sgx_octomap_reset', 'sgx_octomap_insert_batch_dev', 'sgx_octomap_insert', 'sgx_octomap_bounds', 'sgx_octomap_cells_dev',
     'sgx_octomap_cells', 'sgx_octomap_search_dev', 'sgx_octomap_grid_header', 'sgx_octomap_project_dev', 'sgx_octomap_project', 'sgx_octomap_sensor_to_world',
     'sgx_globalmap_create', 'sgx_globalmap_destroy', 'sgx_globalmap_reset', 'sgx_globalmap_append_batch_dev', 'sgx_globalmap_append', 'sgx_globalmap_consolidate_dev',
@@ -380,6 +383,8 @@ class SgxLib:
         d.sgx_covis_update_connections.argtypes = [vp, C.c_int32, vp]
         d.sgx_covis_local_map.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
         d.sgx_covis_keyframe_culling.argtypes = [vp, C.c_int32, C.c_int, vp, vp, vp, vp, vp]
+        d.sgx_covis_ba_graph_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 6
+        d.sgx_covis_ba_graph.argtypes = [vp, C.c_int, C.c_int32, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 5
         d.sgx_octomap_create.argtypes = [C.POINTER(OctomapParams), C.c_int, C.c_int, C.POINTER(vp)]
         d.sgx_octomap_destroy.argtypes = [vp]; d.sgx_octomap_destroy.restype = None
         d.sgx_octomap_reset.argtypes = [vp]

@@ -3,10 +3,11 @@
 The relation "keyframe k observes map point p at keypoint index i" lives on the device with what the reference derives from it (mConnectedKeyFrameWeights, the ordered
 lists, the spanning tree, every point's observations and nObs).  Mutations take host arrays and are synchronous; the three walks — KeyFrame::UpdateConnections
 (KeyFrame.cc:290-380), Tracking::UpdateLocalMap (Tracking.cc:1314-1458) and the votes of LocalMapping::KeyFrameCulling (LocalMapping.cc:632-696) — are batched launch
-sequences on a stream.  Keyframes are named by the caller's mnId, points by dense handles in [0, max_points)."""
+sequences on a stream, and so is the graph of Optimizer::LocalBundleAdjustment / BundleAdjustment (Optimizer.cc:453-504, :572-653, :49-150): local_ba_graph,
+global_ba_graph, ba_graph_batch, with apply_ba_erase for the vToErase loop (:745-757).  Keyframes are named by the caller's mnId, points by dense handles in [0, max_points)."""
 import ctypes as C
 import numpy as np
-from .capi import _vp, COVIS_REPORT_DTYPE
+from .capi import _vp, COVIS_REPORT_DTYPE, COVIS_BA_REPORT_DTYPE
 
 
 def _i4(v):
@@ -178,6 +179,63 @@ class CovisibilityGraph:
         self._sync(stream)
         _, cand, nc, red, mps, cull = [self._host(x) for x in d]
         return [None if nc[q] < 0 else [(int(cand[q, r]), int(red[q, r]), int(mps[q, r]), int(cull[q, r])) for r in range(min(int(nc[q]), M))] for q in range(Q)]
+
+    # ---- the bundle-adjustment graph
+    BA_LOCAL = 0; BA_GLOBAL = 1; ATTR_OCTAVE = 31; ATTR_RIGHT = 32; ATTR_CLOSE = 64
+
+    def ba_graph_batch_dev(self, Q, mode, kf_ids_dev, pose_id_dev, pose_fixed_dev, pcap, point_id_dev, point_edge_begin_dev, ecap, edge_pose_dev, edge_point_dev, edge_kp_dev,
+                           edge_attr_dev, report_dev, stream=None):
+        self._keep = (kf_ids_dev, pose_id_dev, pose_fixed_dev, point_id_dev, point_edge_begin_dev, edge_pose_dev, edge_point_dev, edge_kp_dev, edge_attr_dev, report_dev)
+        self.lib.check(self.lib.dll.sgx_covis_ba_graph_batch_dev(self.h, int(Q), int(mode), _vp(kf_ids_dev), _vp(pose_id_dev), _vp(pose_fixed_dev), int(pcap), _vp(point_id_dev),
+                                                                 _vp(point_edge_begin_dev), int(ecap), _vp(edge_pose_dev), _vp(edge_point_dev), _vp(edge_kp_dev),
+                                                                 _vp(edge_attr_dev), _vp(report_dev), self._stream(stream)), 'sgx_covis_ba_graph_batch_dev')
+
+    def ba_graph_batch(self, kf_ids, mode=0, pcap=None, ecap=None, stream=None):
+        """The graph of Optimizer::LocalBundleAdjustment (Optimizer.cc:453-504, :572-653) for each listed keyframe as one batch, or with mode = BA_GLOBAL that of
+        Optimizer::BundleAdjustment (:49-150) for the whole map (one query; kf_ids is not read).  pcap / ecap: capacities of the point and edge rows; by default what the
+        map as it stands can need.  One dict per query, the rows trimmed to what was written: status, pose_id, pose_fixed, point_id, point_edge_begin, edge_pose,
+        edge_point, edge_kp, edge_attr and the report (the true counts)."""
+        k = _i4(kf_ids) if mode == self.BA_LOCAL else np.zeros(1, 'i4'); Q = len(k); N = self.max_keyframes
+        nobs = self.info()[2]
+        pcap = int(min(self.max_points, nobs) if pcap is None else pcap); ecap = int(nobs if ecap is None else ecap)
+        pc, ec = max(pcap, 0), max(ecap, 0)
+        d = [self._dev(x) for x in (k, np.full((Q, N), -1, 'i4'), np.full((Q, N), 255, 'u1'), np.full((Q, max(pc, 1)), -1, 'i4'), np.full((Q, pc + 1), -1, 'i4'),
+                                    np.full((Q, max(ec, 1)), -1, 'i4'), np.full((Q, max(ec, 1)), -1, 'i4'), np.full((Q, max(ec, 1)), -1, 'i4'), np.full((Q, max(ec, 1)), 255, 'u1'),
+                                    np.zeros(Q * COVIS_BA_REPORT_DTYPE.itemsize, 'u1'))]
+        self.ba_graph_batch_dev(Q, mode, d[0], d[1], d[2], pcap, d[3], d[4], ecap, d[5], d[6], d[7], d[8], d[9], stream)
+        self._sync(stream)
+        _, pid, pfx, pts, beg, ep, el, ek, ea, rep = [self._host(x) for x in d]
+        rep = rep.view(COVIS_BA_REPORT_DTYPE)
+        out = []
+        for q in range(Q):
+            r = rep[q].copy(); st = int(r['status'])
+            if st == -1:
+                out.append(dict(status=st, report=r)); continue
+            npo = int(r['n_poses']); npt = min(int(r['n_points']), pc); b = beg[q, :npt + 1]
+            ne = int(b[np.searchsorted(b, ec, side='right') - 1])                       # the edges of the leading points that fit wholly
+            out.append(dict(status=st, pose_id=pid[q, :npo].copy(), pose_fixed=pfx[q, :npo].copy(), point_id=pts[q, :npt].copy(), point_edge_begin=b.copy(),
+                            edge_pose=ep[q, :ne].copy(), edge_point=el[q, :ne].copy(), edge_kp=ek[q, :ne].copy(), edge_attr=ea[q, :ne].copy(), report=r))
+        return out
+
+    def local_ba_graph(self, kf_id, pcap=None, ecap=None, stream=None):
+        return self.ba_graph_batch([kf_id], self.BA_LOCAL, pcap, ecap, stream)[0]
+
+    def global_ba_graph(self, pcap=None, ecap=None, stream=None):
+        return self.ba_graph_batch([], self.BA_GLOBAL, pcap, ecap, stream)[0]
+
+    def apply_ba_erase(self, graph, erase):
+        """vToErase of Optimizer::LocalBundleAdjustment (Optimizer.cc:711-757) into the relation: every flagged monocular edge in edge order, then every flagged stereo
+        edge, each EraseMapPointMatch + EraseObservation with its SetBadFlag at nObs <= 2 (an edge whose point went that way before its turn finds nothing to erase).
+        Returns the (keyframe id, point id) pairs in the order applied."""
+        e = np.asarray(erase).reshape(-1) != 0
+        assert len(e) == len(graph['edge_pose'])
+        stereo = (graph['edge_attr'] & self.ATTR_RIGHT) != 0
+        done = []
+        for j in list(np.flatnonzero(e & ~stereo)) + list(np.flatnonzero(e & stereo)):
+            kf = int(graph['pose_id'][graph['edge_pose'][j]])
+            self.set_observations(kf, [int(graph['edge_kp'][j])], [-1])
+            done.append((kf, int(graph['point_id'][graph['edge_point'][j]])))
+        return done
 
     def close(self):
         if self.h: self.lib.dll.sgx_covis_destroy(self.h); self.h = C.c_void_p()

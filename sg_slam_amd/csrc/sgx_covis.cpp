@@ -1,6 +1,7 @@
 // sgx_covis.cpp — the covisibility graph behind the C ABI (sgx_covis_*): the relation keyframe x map point as a heap the host mirrors and patches on the device
 // (KeyFrame::AddMapPoint / EraseMapPointMatch, MapPoint::AddObservation / EraseObservation / SetBadFlag / Replace, src/sg-slam/src/MapPoint.cc:98-215), the graph
-// (weights, list modes, spanning tree) as device state, and the three walks of it as the launch sequences of sgx_covis_kernels.h.
+// (weights, list modes, spanning tree) as device state, and the walks of it (UpdateConnections, UpdateLocalMap, the culling votes, the bundle-adjustment graph) as the
+// launch sequences of sgx_covis_kernels.h.
 #include "sgx_covis_kernels.h"
 #include "sgx_devmem.h"
 #include "../../include/sgx.h"
@@ -13,6 +14,7 @@
 #include <vector>
 
 static_assert(sizeof(sgx_covis_report) == sizeof(SgxCovisReport), "the kernels write sgx_covis_report records");
+static_assert(sizeof(sgx_covis_ba_report) == sizeof(SgxCovisBaReport), "the kernels write sgx_covis_ba_report records");
 
 enum { H_FREE = 0, H_LIVE = 1, H_HDR = 2, COVIS_JCAP = 1 << 16, COVIS_GRID = 128 };
 
@@ -527,6 +529,39 @@ extern "C" int sgx_covis_keyframe_culling_batch_dev(sgx_covis *h, int Q, const i
     return SGX_OK;
 }
 
+extern "C" int sgx_covis_ba_graph_batch_dev(sgx_covis *h, int Q, int mode, const int32_t *kf_ids_dev, int32_t *pose_id_dev, uint8_t *pose_fixed_dev, int pcap,
+                                            int32_t *point_id_dev, int32_t *point_edge_begin_dev, int ecap, int32_t *edge_pose_dev, int32_t *edge_point_dev,
+                                            int32_t *edge_kp_dev, uint8_t *edge_attr_dev, sgx_covis_ba_report *report_dev, void *stream)
+{
+    if (!h || Q < 0 || Q > h->max_q || (mode != SGX_COVIS_BA_LOCAL && mode != SGX_COVIS_BA_GLOBAL) || (mode == SGX_COVIS_BA_GLOBAL && Q != 1)) return SGX_ERR_INVALID;
+    if (Q == 0) return SGX_OK;
+    if ((mode == SGX_COVIS_BA_LOCAL && !kf_ids_dev) || !pose_id_dev || !pose_fixed_dev || !point_edge_begin_dev || !report_dev || (pcap > 0 && !point_id_dev) ||
+        (ecap > 0 && (!edge_pose_dev || !edge_point_dev || !edge_kp_dev || !edge_attr_dev))) return SGX_ERR_INVALID;
+    const int rc = covis_sync_tables(h);
+    if (rc != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    SgxCovisArgs A = covis_args(h);
+    A.Q = Q; A.q_kf = kf_ids_dev; A.ba_global = mode == SGX_COVIS_BA_GLOBAL; A.pcap = pcap; A.ecap = ecap; A.pose_id = pose_id_dev; A.pose_fixed = pose_fixed_dev;
+    A.point_id = point_id_dev; A.point_begin = point_edge_begin_dev; A.edge_pose = edge_pose_dev; A.edge_point = edge_point_dev; A.edge_kp = edge_kp_dev;
+    A.edge_attr = edge_attr_dev; A.ba_report = (SgxCovisBaReport *)report_dev;
+    const unsigned G = (unsigned)std::max(1, std::min(h->nslots, (int)COVIS_GRID));
+    SGX_LAUNCH(k_covis_ba_begin, dim3((unsigned)Q), dim3(256), s, A);
+    if (A.ba_global) {
+        SGX_LAUNCH(k_covis_ba_all_count, dim3((unsigned)std::max(1, std::min((h->max_points + 255) / 256, 4 * (int)COVIS_GRID))), dim3(256), s, A);
+        SGX_LAUNCH(k_covis_ba_all_points, dim3(1), dim3(256), s, A);
+    } else {
+        SGX_CHECK_HIP(hipMemsetAsync(h->d_stamp, 0x7f, (size_t)Q * h->max_points * 4, s));
+        SGX_LAUNCH(k_covis_lm_stamp, dim3(G, (unsigned)Q), dim3(256), s, A);
+        SGX_LAUNCH(k_covis_ba_count, dim3(G, (unsigned)Q), dim3(256), s, A);
+    }
+    SGX_LAUNCH(k_covis_ba_poses, dim3((unsigned)Q), dim3(256), s, A);
+    if (!A.ba_global) SGX_LAUNCH(k_covis_ba_points, dim3(G, (unsigned)Q), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_ba_scan, dim3((unsigned)Q), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_ba_edges, dim3((unsigned)std::max(1, std::min(std::max(pcap, 0) / 4 + 1, 8 * (int)COVIS_GRID)), (unsigned)Q), dim3(256), s, A);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
 // ---- one query from host memory through the batch entries: staged in device buffers of the call, run on the legacy stream, read back
 template <class T> static int covis_stage(SgxDevMem &m, T **d, const T *src, size_t n, size_t cap)
 {
@@ -600,4 +635,34 @@ extern "C" int sgx_covis_keyframe_culling(sgx_covis *h, int32_t kf_id, int max_c
     }
     *n_cand = nc;
     return SGX_OK;
+}
+
+extern "C" int sgx_covis_ba_graph(sgx_covis *h, int mode, int32_t kf_id, int32_t *pose_id, uint8_t *pose_fixed, int pcap, int32_t *point_id, int32_t *point_edge_begin,
+                                  int ecap, int32_t *edge_pose, int32_t *edge_point, int32_t *edge_kp, uint8_t *edge_attr, sgx_covis_ba_report *report)
+{
+    if (!h || !pose_id || !pose_fixed || !point_edge_begin || (pcap > 0 && !point_id) || (ecap > 0 && (!edge_pose || !edge_point || !edge_kp || !edge_attr))) return SGX_ERR_INVALID;
+    SgxDevMem m; int rc;
+    const size_t pc = (size_t)std::max(pcap, 0), ec = (size_t)std::max(ecap, 0);
+    int32_t *d_id = nullptr, *d_pid = nullptr, *d_pts = nullptr, *d_beg = nullptr, *d_ep = nullptr, *d_el = nullptr, *d_ek = nullptr;
+    uint8_t *d_pf = nullptr, *d_ea = nullptr; sgx_covis_ba_report *d_rep = nullptr;
+    if ((rc = covis_stage(m, &d_id, &kf_id, 1, 1)) || (rc = m.alloc(&d_pid, (size_t)h->max_kf)) || (rc = m.alloc(&d_pf, (size_t)h->max_kf)) || (rc = m.alloc(&d_pts, pc)) ||
+        (rc = m.alloc(&d_beg, pc + 1)) || (rc = m.alloc(&d_ep, ec)) || (rc = m.alloc(&d_el, ec)) || (rc = m.alloc(&d_ek, ec)) || (rc = m.alloc(&d_ea, ec)) ||
+        (rc = m.alloc(&d_rep, 1))) return rc;
+    if ((rc = sgx_covis_ba_graph_batch_dev(h, 1, mode, d_id, d_pid, d_pf, pcap, d_pts, d_beg, ecap, d_ep, d_el, d_ek, d_ea, d_rep, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    sgx_covis_ba_report R;
+    SGX_CHECK_HIP(hipMemcpy(&R, d_rep, sizeof(R), hipMemcpyDeviceToHost));
+    if (report) *report = R;
+    if (R.status == SGX_ERR_INVALID) return R.status;                              // nothing of the query was written
+    const size_t np = (size_t)std::min(R.n_points, pcap);
+    if (R.n_poses) { SGX_CHECK_HIP(hipMemcpy(pose_id, d_pid, (size_t)R.n_poses * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(pose_fixed, d_pf, (size_t)R.n_poses, hipMemcpyDeviceToHost)); }
+    if (np) SGX_CHECK_HIP(hipMemcpy(point_id, d_pts, np * 4, hipMemcpyDeviceToHost));
+    SGX_CHECK_HIP(hipMemcpy(point_edge_begin, d_beg, (np + 1) * 4, hipMemcpyDeviceToHost));
+    size_t ne = 0;                                                                 // the edges of the leading points that fit wholly
+    for (size_t i = 0; i < np && point_edge_begin[i + 1] <= ecap; i++) ne = (size_t)point_edge_begin[i + 1];
+    if (ne) {
+        SGX_CHECK_HIP(hipMemcpy(edge_pose, d_ep, ne * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(edge_point, d_el, ne * 4, hipMemcpyDeviceToHost));
+        SGX_CHECK_HIP(hipMemcpy(edge_kp, d_ek, ne * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(edge_attr, d_ea, ne, hipMemcpyDeviceToHost));
+    }
+    return R.status;                                                               // SGX_OK, or SGX_ERR_NOMEM with what fits written
 }

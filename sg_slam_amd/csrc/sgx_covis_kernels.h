@@ -1,5 +1,6 @@
 // sgx_covis_kernels.h — the covisibility graph on the device: KeyFrame::UpdateConnections (src/sg-slam/src/KeyFrame.cc:290-380), Tracking::UpdateLocalKeyFrames +
-// UpdateLocalPoints (Tracking.cc:1324-1458) and the votes of LocalMapping::KeyFrameCulling (LocalMapping.cc:632-696).
+// UpdateLocalPoints (Tracking.cc:1324-1458), the votes of LocalMapping::KeyFrameCulling (LocalMapping.cc:632-696), and the graph of the bundle adjustments: the set
+// selection and the edge loop of Optimizer::LocalBundleAdjustment (Optimizer.cc:453-504, :572-653) and the edge loop of Optimizer::BundleAdjustment (:49-150).
 //
 // The relation "keyframe k observes point p at index i" is one int32 heap the host mirrors and patches (k_covis_scatter): per point the head of a chain of 8-entry chunks,
 // its length and nObs; per keyframe slot the row mvpMapPoints[cap].  An entry is (slot << 16 | index).  The graph is device state: W[slot][slot] uint16 =
@@ -17,10 +18,19 @@ enum { SGX_COVIS_ALL = 0, SGX_COVIS_GATED = 1, SGX_COVIS_SINGLE = 2 };          
 enum { SGX_COVIS_FREE = 0, SGX_COVIS_LIVE = 1, SGX_COVIS_DEAD = 2 };                      // DEAD: erased, but another keyframe's row still lists it (isBad())
 enum { CV_ID = 0, CV_STATE, CV_N, CV_MODE, CV_SINGLE, CV_PARENT, CV_FIRST, CV_PAD, CV_FIELDS };   // the record of a slot
 enum { CQ_SLOT = 0, CQ_N, CQ_MAX, CQ_ARG, CQ_NORD, CQ_NL, CQ_VALID, CQ_PAD, CQ_FIELDS };          // per-query scalars between the kernels of one sequence
+#ifndef SGX_COVIS_ATTR_BITS                                                               // include/sgx.h names the same bits for the edge_attr row of the BA graph
+#define SGX_COVIS_ATTR_BITS
 enum { SGX_COVIS_ATTR_OCTAVE = 31, SGX_COVIS_ATTR_RIGHT = 32, SGX_COVIS_ATTR_CLOSE = 64 };
+#endif
+enum { BQ_POINTS = CQ_N, BQ_EDGES = CQ_MAX, BQ_STEREO = CQ_ARG, BQ_NP = CQ_PAD };         // the per-query scalars as the BA graph uses them
+enum { SGX_COVIS_BA_NONE = 0, SGX_COVIS_BA_FIXED = 1, SGX_COVIS_BA_LOCALKF = 2, SGX_COVIS_BA_WAVE = 64 };
 
 struct SgxCovisReport {                   // sgx_covis_report
     int status, n_counter, max_weight, max_kf, n_ordered, parent, n_stage1, n_local_kf, n_local_points, ref_tracked;
+};
+
+struct SgxCovisBaReport {                 // sgx_covis_ba_report
+    int status, n_local_kf, n_fixed_kf, n_poses, n_points, n_edges, n_mono_edges, n_stereo_edges;
 };
 
 struct SgxCovisArgs {
@@ -35,6 +45,9 @@ struct SgxCovisArgs {
     int Q; const int *q_kf; SgxCovisReport *report;
     int f_cap; int *frame_mp; const int *f_n, *min_obs; int *local_kf, *n_local_kf, *ref_kf, *ref_tracked; int mcap; int *local_points, *local_obs, *n_local_points;
     int max_cand; int *cand, *n_cand, *n_red, *n_mps, *cull;
+    // the bundle-adjustment graph
+    int ba_global, pcap, ecap; int *pose_id; unsigned char *pose_fixed; int *point_id, *point_begin, *edge_pose, *edge_point, *edge_kp; unsigned char *edge_attr;
+    SgxCovisBaReport *ba_report;
 };
 
 SGX_DEV int sgx_covis_lookup(const SgxCovisArgs &A, int id)                // slot of a live keyframe, -1 if there is none
@@ -584,4 +597,343 @@ SGX_KERNEL(256) k_covis_refs(SgxCovisArgs A, int *refs)
     const int t = (int)blockIdx.x * 256 + tid;
     if (t < A.nslots) { int c = 0; for (int k = 0; k < A.nslots; k++) c += A.W[(size_t)k * A.max_kf + t] > 0; refs[t] = c; }
     SGX_THREADS_END
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------ the bundle-adjustment graph
+// The set selection of Optimizer::LocalBundleAdjustment (Optimizer.cc:453-504) and its edge loop (:572-653), and the same edge loop over the whole map for
+// Optimizer::BundleAdjustment (:49-150).  Per query the five workspace rows hold: ws_cnt the ROLE of every slot (none / fixed camera / local keyframe), ws_ord the ordered
+// list and later the pose index of every slot, ws_lkf lLocalKeyFrames as slots (-1 where the list names an erased keyframe), ws_pcnt the points every position contributes;
+// the stamp row is UpdateLocalPoints' (k_covis_lm_stamp is launched as it is).  The scalars BQ_* are summed with integer atomics.
+//
+// Query q's validity, lLocalKeyFrames = the keyframe and then its ordered list without the isBad() entries (:458-468), and the roles.  Global mode: every live slot is local.
+SGX_KERNEL(256) k_covis_ba_begin(SgxCovisArgs A)
+{
+    const int q = (int)blockIdx.x;
+    int *w = A.ws_q + q * CQ_FIELDS, *role = A.ws_cnt + (size_t)q * A.max_kf, *ord = A.ws_ord + (size_t)q * A.max_kf, *lkf = A.ws_lkf + (size_t)q * A.max_kf;
+    const int s = A.ba_global ? -1 : sgx_covis_lookup(A, A.q_kf[q]);
+    if (A.pcap < 0 || A.ecap < 0 || (!A.ba_global && s < 0)) {          // its status, and nothing else of it is written by any kernel
+        SGX_THREADS_BEGIN(tid)
+        if (tid == 0) { SgxCovisBaReport R = {}; R.status = -1; A.ba_report[q] = R; w[CQ_VALID] = 0; }
+        SGX_THREADS_END
+        return;
+    }
+    sgx_covis_ordered_wg(A, s, A.max_kf, ord, nullptr, &w[CQ_NORD]);
+    const int n = A.ba_global ? 0 : (w[CQ_NORD] < A.max_kf ? w[CQ_NORD] : A.max_kf - 1);
+    SGX_THREADS_BEGIN(tid)
+    for (int t = tid; t < A.nslots; t += 256) role[t] = A.ba_global && A.kf[t * CV_FIELDS + CV_STATE] == SGX_COVIS_LIVE ? SGX_COVIS_BA_LOCALKF : SGX_COVIS_BA_NONE;
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    if (!A.ba_global) {
+        if (tid == 0) { lkf[0] = s; role[s] = SGX_COVIS_BA_LOCALKF; }
+        for (int r = tid; r < n; r += 256) {                              // pKFi->mnBALocalForKF is set for a bad one too (:465), which has no observation to be met through again
+            const int t = ord[r];
+            const bool live = A.kf[t * CV_FIELDS + CV_STATE] == SGX_COVIS_LIVE;
+            lkf[1 + r] = live ? t : -1;
+            if (live) role[t] = SGX_COVIS_BA_LOCALKF;
+        }
+    }
+    if (tid == 0) { w[CQ_SLOT] = s; w[CQ_VALID] = 1; w[CQ_NL] = A.ba_global ? 0 : 1 + n; w[BQ_POINTS] = 0; w[BQ_EDGES] = 0; w[BQ_STEREO] = 0; w[BQ_NP] = 0; }
+    SGX_THREADS_END
+}
+
+// Per position of lLocalKeyFrames: the points it contributes to lLocalMapPoints (those whose stamp it holds), their observations = edges, the stereo ones among them, and
+// lFixedCameras (:489-504): every observing slot without a role gets the fixed one.  A lane takes a point and walks its chain; the marks are idempotent.
+SGX_KERNEL(256) k_covis_ba_count(SgxCovisArgs A)
+{
+    SGX_LDS int s_c, s_e, s_s;
+    const int q = (int)blockIdx.y;
+    int *w = A.ws_q + q * CQ_FIELDS;
+    if (!w[CQ_VALID]) return;
+    const int nl = w[CQ_NL];
+    const int *stamp = A.stamp + (size_t)q * A.max_points;
+    int *role = A.ws_cnt + (size_t)q * A.max_kf;
+    for (int pos = (int)blockIdx.x; pos < nl; pos += (int)gridDim.x) {
+        const int k = A.ws_lkf[(size_t)q * A.max_kf + pos];
+        SGX_THREADS_BEGIN(tid)
+        if (tid == 0) { s_c = 0; s_e = 0; s_s = 0; }
+        SGX_THREADS_END
+        SGX_SYNC();
+        if (k >= 0 && A.kf[k * CV_FIELDS + CV_STATE] == SGX_COVIS_LIVE) {
+            SGX_THREADS_BEGIN(tid)
+            const int np = A.kf[k * CV_FIELDS + CV_N];
+            int c = 0, e = 0, st = 0;
+            for (int i = tid; i < np; i += 256) {
+                const int p = A.heap[A.o_mp + (size_t)k * A.cap + i];
+                if (p < 0 || stamp[p] != pos * A.cap + i) continue;
+                c++; e += A.heap[A.o_cnt + (size_t)p];
+                SGX_COVIS_FOR_OBS(A, p, t, j, if (A.attr[(size_t)t * A.cap + j] & SGX_COVIS_ATTR_RIGHT) st++;
+                                              if (role[t] == SGX_COVIS_BA_NONE) sgx_atomic_max(&role[t], (int)SGX_COVIS_BA_FIXED););
+            }
+            if (c) sgx_atomic_add(&s_c, c);
+            if (e) sgx_atomic_add(&s_e, e);
+            if (st) sgx_atomic_add(&s_s, st);
+            SGX_THREADS_END
+            SGX_SYNC();
+        }
+        SGX_THREADS_BEGIN(tid)
+        if (tid == 0) {
+            A.ws_pcnt[(size_t)q * A.max_kf + pos] = s_c;
+            if (s_e) sgx_atomic_add(&w[BQ_EDGES], s_e);
+            if (s_s) sgx_atomic_add(&w[BQ_STEREO], s_s);
+        }
+        SGX_THREADS_END
+        SGX_SYNC();
+    }
+}
+
+// Global mode: the existing points of the whole map, their observations and the stereo ones, by a grid over the point ids
+SGX_KERNEL(256) k_covis_ba_all_count(SgxCovisArgs A)
+{
+    SGX_LDS int s_c, s_e, s_s;
+    int *w = A.ws_q;
+    if (!w[CQ_VALID]) return;
+    SGX_THREADS_BEGIN(tid)
+    if (tid == 0) { s_c = 0; s_e = 0; s_s = 0; }
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    int c = 0, e = 0, st = 0;
+    for (long long p = (long long)blockIdx.x * 256 + tid; p < A.max_points; p += (long long)gridDim.x * 256) {
+        const int n = A.heap[A.o_cnt + (size_t)p];
+        if (n <= 0) continue;
+        c++; e += n;
+        SGX_COVIS_FOR_OBS(A, p, t, j, if (A.attr[(size_t)t * A.cap + j] & SGX_COVIS_ATTR_RIGHT) st++;);
+    }
+    if (c) sgx_atomic_add(&s_c, c);
+    if (e) sgx_atomic_add(&s_e, e);
+    if (st) sgx_atomic_add(&s_s, st);
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    if (tid == 0) {
+        if (s_c) sgx_atomic_add(&w[BQ_POINTS], s_c);
+        if (s_e) sgx_atomic_add(&w[BQ_EDGES], s_e);
+        if (s_s) sgx_atomic_add(&w[BQ_STEREO], s_s);
+    }
+    SGX_THREADS_END
+}
+
+// Global mode: the existing points in ascending id by one workgroup: every lane counts its stretch of the ids, lane 0 scans the 256 counts, every lane writes its stretch
+// (the first pcap); point_begin holds every written point's number of observations until k_covis_ba_scan turns it into the prefix.
+SGX_KERNEL(256) k_covis_ba_all_points(SgxCovisArgs A)
+{
+    SGX_LDS int s_part[256];
+    if (!A.ws_q[CQ_VALID]) return;
+    const long long seg = ((long long)A.max_points + 255) / 256;
+    SGX_THREADS_BEGIN(tid)
+    int c = 0;
+    for (long long p = tid * seg; p < A.max_points && p < (tid + 1) * seg; p++) c += A.heap[A.o_cnt + (size_t)p] > 0;
+    s_part[tid] = c;
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    if (tid == 0) { int o = 0; for (int i = 0; i < 256; i++) { const int c = s_part[i]; s_part[i] = o; o += c; } }
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    int o = s_part[tid];
+    for (long long p = tid * seg; p < A.max_points && p < (tid + 1) * seg; p++) {
+        const int n = A.heap[A.o_cnt + (size_t)p];
+        if (n > 0) { if (o < A.pcap) { A.point_id[o] = (int)p; A.point_begin[o] = n; } o++; }
+    }
+    SGX_THREADS_END
+}
+
+// The poses: the slots with a role in ascending keyframe id = the order of the sorted table (every lane counts its stretch, lane 0 scans, every lane writes), the pose
+// index of every slot for the edges, and the report with the true counts.
+SGX_KERNEL(256) k_covis_ba_poses(SgxCovisArgs A)
+{
+    SGX_LDS int s_part[256];
+    SGX_LDS int s_n, s_loc, s_pts;
+    const int q = (int)blockIdx.x;
+    int *w = A.ws_q + q * CQ_FIELDS;
+    if (!w[CQ_VALID]) return;
+    const int nl = w[CQ_NL];
+    const int *role = A.ws_cnt + (size_t)q * A.max_kf, *pcnt = A.ws_pcnt + (size_t)q * A.max_kf;
+    int *pidx = A.ws_ord + (size_t)q * A.max_kf, *pose_id = A.pose_id + (size_t)q * A.max_kf;
+    unsigned char *pose_fixed = A.pose_fixed + (size_t)q * A.max_kf;
+    const int seg = (A.nlive + 255) / 256;
+    SGX_THREADS_BEGIN(tid)
+    for (int t = tid; t < A.nslots; t += 256) pidx[t] = -1;
+    if (tid == 0) { s_loc = 0; s_pts = 0; }
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    int c = 0, loc = 0, pc = 0;
+    for (int j = tid * seg; j < A.nlive && j < (tid + 1) * seg; j++) { const int r = role[A.sorted_slot[j]]; if (r != SGX_COVIS_BA_NONE) { c++; loc += r == SGX_COVIS_BA_LOCALKF; } }
+    for (int j = tid; j < nl; j += 256) pc += pcnt[j];
+    s_part[tid] = c;
+    if (loc) sgx_atomic_add(&s_loc, loc);
+    if (pc) sgx_atomic_add(&s_pts, pc);
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    if (tid == 0) { int o = 0; for (int i = 0; i < 256; i++) { const int c = s_part[i]; s_part[i] = o; o += c; } s_n = o; }
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    int o = s_part[tid];
+    for (int j = tid * seg; j < A.nlive && j < (tid + 1) * seg; j++) {
+        const int sl = A.sorted_slot[j], r = role[sl], id = A.sorted_id[j];
+        if (r == SGX_COVIS_BA_NONE) continue;
+        pose_id[o] = id; pose_fixed[o] = (unsigned char)(r == SGX_COVIS_BA_FIXED ? 1 : id == 0 ? 2 : 0);      // vSE3->setFixed(pKFi->mnId==0) (:529)
+        pidx[sl] = o; o++;
+    }
+    if (tid == 0) {
+        const int n_points = A.ba_global ? w[BQ_POINTS] : s_pts, n_edges = w[BQ_EDGES];
+        w[BQ_POINTS] = n_points; w[BQ_NP] = n_points < A.pcap ? n_points : A.pcap;
+        SgxCovisBaReport R = {};
+        R.status = n_points > A.pcap || n_edges > A.ecap ? -3 : 0;          // SGX_ERR_NOMEM
+        R.n_local_kf = s_loc; R.n_fixed_kf = s_n - s_loc; R.n_poses = s_n; R.n_points = n_points; R.n_edges = n_edges;
+        R.n_stereo_edges = w[BQ_STEREO]; R.n_mono_edges = n_edges - w[BQ_STEREO];
+        A.ba_report[q] = R;
+    }
+    SGX_THREADS_END
+}
+
+// lLocalMapPoints (:472-486) in the reference's order, as k_covis_lm_emit does it: a position starts where the positions before it end, within a keyframe every lane takes
+// a stretch of indices.  point_begin holds every written point's number of observations until k_covis_ba_scan turns it into the prefix.
+SGX_KERNEL(256) k_covis_ba_points(SgxCovisArgs A)
+{
+    SGX_LDS int s_part[256];
+    SGX_LDS int s_base;
+    const int q = (int)blockIdx.y;
+    const int *w = A.ws_q + q * CQ_FIELDS;
+    if (!w[CQ_VALID]) return;
+    const int nl = w[CQ_NL];
+    const int *stamp = A.stamp + (size_t)q * A.max_points, *pcnt = A.ws_pcnt + (size_t)q * A.max_kf;
+    int *point_id = A.point_id + (size_t)q * A.pcap, *point_begin = A.point_begin + (size_t)q * ((size_t)A.pcap + 1);
+    for (int pos = (int)blockIdx.x; pos < nl; pos += (int)gridDim.x) {
+        const int k = A.ws_lkf[(size_t)q * A.max_kf + pos];
+        const bool live = k >= 0 && A.kf[k * CV_FIELDS + CV_STATE] == SGX_COVIS_LIVE;
+        const int np = live ? A.kf[k * CV_FIELDS + CV_N] : 0, seg = (np + 255) / 256;
+        SGX_THREADS_BEGIN(tid)
+        int c = 0;
+        for (int j = tid; j < pos; j += 256) c += pcnt[j];
+        s_part[tid] = c;
+        SGX_THREADS_END
+        SGX_SYNC();
+        SGX_THREADS_BEGIN(tid)
+        if (tid == 0) { int b = 0; for (int i = 0; i < 256; i++) b += s_part[i]; s_base = b; }
+        SGX_THREADS_END
+        SGX_SYNC();
+        SGX_THREADS_BEGIN(tid)
+        int c = 0;
+        for (int i = tid * seg; i < np && i < (tid + 1) * seg; i++) { const int p = A.heap[A.o_mp + (size_t)k * A.cap + i]; if (p >= 0 && stamp[p] == pos * A.cap + i) c++; }
+        s_part[tid] = c;
+        SGX_THREADS_END
+        SGX_SYNC();
+        SGX_THREADS_BEGIN(tid)
+        if (tid == 0) { int o = s_base; for (int i = 0; i < 256; i++) { const int c = s_part[i]; s_part[i] = o; o += c; } }
+        SGX_THREADS_END
+        SGX_SYNC();
+        SGX_THREADS_BEGIN(tid)
+        int o = s_part[tid];
+        for (int i = tid * seg; i < np && i < (tid + 1) * seg; i++) {
+            const int p = A.heap[A.o_mp + (size_t)k * A.cap + i];
+            if (p >= 0 && stamp[p] == pos * A.cap + i) { if (o < A.pcap) { point_id[o] = p; point_begin[o] = A.heap[A.o_cnt + (size_t)p]; } o++; }
+        }
+        SGX_THREADS_END
+        SGX_SYNC();
+    }
+}
+
+// point_edge_begin: the exclusive prefix of the written points' observation counts, and their total behind the last one
+SGX_KERNEL(256) k_covis_ba_scan(SgxCovisArgs A)
+{
+    SGX_LDS int s_part[256];
+    SGX_LDS int s_total;
+    const int q = (int)blockIdx.x;
+    const int *w = A.ws_q + q * CQ_FIELDS;
+    if (!w[CQ_VALID]) return;
+    const int np = w[BQ_NP], seg = (np + 255) / 256;
+    int *point_begin = A.point_begin + (size_t)q * ((size_t)A.pcap + 1);
+    SGX_THREADS_BEGIN(tid)
+    int c = 0;
+    for (int i = tid * seg; i < np && i < (tid + 1) * seg; i++) c += point_begin[i];
+    s_part[tid] = c;
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    if (tid == 0) { int o = 0; for (int i = 0; i < 256; i++) { const int c = s_part[i]; s_part[i] = o; o += c; } s_total = o; }
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    int o = s_part[tid];
+    for (int i = tid * seg; i < np && i < (tid + 1) * seg; i++) { const int c = point_begin[i]; point_begin[i] = o; o += c; }
+    SGX_THREADS_END
+    SGX_SYNC();
+    SGX_THREADS_BEGIN(tid)
+    if (tid == 0) point_begin[np] = s_total;
+    SGX_THREADS_END
+}
+
+// the entries first, first + stride, ... (stride a power of two) of point p's chain, at their chain positions: the observing keyframe's id and the entry itself
+SGX_DEV void sgx_covis_ba_stage(const SgxCovisArgs &A, int p, int n, int first, int stride, int *s_id, int *s_e)
+{
+    int j0 = 0, left = n, m = ((n - 1) & (SGX_COVIS_CHUNK - 1)) + 1;          // the walk of SGX_COVIS_FOR_OBS over the chunks alone: only the lane's own entries are loaded
+    for (int c = A.heap[A.o_head + (size_t)p]; left > 0 && c >= 0; c = A.heap[A.o_next + (size_t)c], m = SGX_COVIS_CHUNK) {
+        for (int j = j0 + ((first - j0) & (stride - 1)); j < j0 + m; j += stride) {
+            const int e = A.heap[A.o_ent + (size_t)c * SGX_COVIS_CHUNK + (j - j0)];
+            s_id[j] = A.kf[(e >> 16) * CV_FIELDS + CV_ID]; s_e[j] = e;
+        }
+        j0 += m; left -= m;
+    }
+}
+
+// one edge of point number i: the observation staged at s_id[k] / s_e[k] of n goes behind those of a smaller keyframe id (map<KeyFrame*, size_t> order, rule 1)
+SGX_DEV void sgx_covis_ba_edge(const SgxCovisArgs &A, int q, int i, int begin, int n, int k, const int *s_id, const int *s_e, const int *pidx)
+{
+    const int id = s_id[k], e = s_e[k], t = e >> 16, ix = e & 0xffff;
+    int rank = 0;
+    for (int m = 0; m < n; m++) rank += s_id[m] < id;
+    if (begin + rank >= A.ecap) return;
+    const size_t o = (size_t)q * A.ecap + begin + rank;
+    A.edge_pose[o] = pidx[t]; A.edge_point[o] = i; A.edge_kp[o] = ix; A.edge_attr[o] = A.attr[(size_t)t * A.cap + ix];
+}
+
+// The edges (:572-653): point i's observations in ascending keyframe id at point_begin[i] ...  A point seen by at most 64 keyframes is a wave's: the workgroup takes four
+// points at a time, lane l stages observation l of its wave's point in LDS and ranks it against the others.  A longer list (up to every keyframe) is the whole
+// workgroup's.  Only the points whose edges fit wholly are written.
+SGX_KERNEL(256) k_covis_ba_edges(SgxCovisArgs A)
+{
+    SGX_LDS int s_id[SGX_COVIS_MAX_KF];
+    SGX_LDS int s_e[SGX_COVIS_MAX_KF];
+    const int q = (int)blockIdx.y;
+    const int *w = A.ws_q + q * CQ_FIELDS;
+    if (!w[CQ_VALID]) return;
+    const int np = w[BQ_NP];
+    const int *point_id = A.point_id + (size_t)q * A.pcap, *point_begin = A.point_begin + (size_t)q * ((size_t)A.pcap + 1), *pidx = A.ws_ord + (size_t)q * A.max_kf;
+    for (int base = (int)blockIdx.x * 4; base < np; base += (int)gridDim.x * 4) {
+        SGX_THREADS_BEGIN(tid)
+        const int wv = tid >> 6, lane = tid & 63, i = base + wv;
+        if (i < np) {
+            const int p = point_id[i], n = A.heap[A.o_cnt + (size_t)p];
+            if (n <= SGX_COVIS_BA_WAVE && lane < n) sgx_covis_ba_stage(A, p, n, lane, SGX_COVIS_BA_WAVE, s_id + wv * SGX_COVIS_BA_WAVE, s_e + wv * SGX_COVIS_BA_WAVE);
+        }
+        SGX_THREADS_END
+        SGX_SYNC();
+        SGX_THREADS_BEGIN(tid)
+        const int wv = tid >> 6, lane = tid & 63, i = base + wv;
+        if (i < np) {
+            const int n = A.heap[A.o_cnt + (size_t)point_id[i]];
+            if (n <= SGX_COVIS_BA_WAVE && lane < n && point_begin[i + 1] <= A.ecap)
+                sgx_covis_ba_edge(A, q, i, point_begin[i], n, lane, s_id + wv * SGX_COVIS_BA_WAVE, s_e + wv * SGX_COVIS_BA_WAVE, pidx);
+        }
+        SGX_THREADS_END
+        SGX_SYNC();
+    }
+    for (int i = (int)blockIdx.x; i < np; i += (int)gridDim.x) {
+        const int p = point_id[i], n = A.heap[A.o_cnt + (size_t)p];
+        if (n <= SGX_COVIS_BA_WAVE || n > SGX_COVIS_MAX_KF || point_begin[i + 1] > A.ecap) continue;
+        SGX_THREADS_BEGIN(tid)
+        sgx_covis_ba_stage(A, p, n, tid, 256, s_id, s_e);
+        SGX_THREADS_END
+        SGX_SYNC();
+        SGX_THREADS_BEGIN(tid)
+        for (int k = tid; k < n; k += 256) sgx_covis_ba_edge(A, q, i, point_begin[i], n, k, s_id, s_e, pidx);
+        SGX_THREADS_END
+        SGX_SYNC();
+    }
 }

@@ -141,6 +141,18 @@ int main(int argc, char **argv)
         printf("\nculled:"); for (int32_t k : G.KeyFrameCulling(cur)) printf(" %d", k);
         printf("\nparent of %d: %d, children:", cur, G.GetParent(cur)); for (int32_t c : G.GetChilds(cur)) printf(" %d", c);
         printf("\n");
+        // the graph of LocalBundleAdjustment(cur) after the culling, every third edge erased as vToErase, and the graph again
+        for (int round = 0; round < 2; round++) {
+            const sgx::CovisibilityGraph::BaGraph g = G.ba_graph(cur);
+            printf("ba poses"); for (size_t j = 0; j < g.pose_id.size(); j++) printf(" %d/%d", g.pose_id[j], g.pose_fixed[j]);
+            printf(" points"); for (int32_t q : g.point_id) printf(" %d", q);
+            printf(" edges"); for (size_t j = 0; j < g.edge_pose.size(); j++) printf(" %d:%d:%d:%d", g.edge_pose[j], g.edge_point[j], g.edge_kp[j], g.edge_attr[j]);
+            printf("\n");
+            if (round) break;
+            std::vector<uint8_t> erase(g.edge_pose.size(), 0);
+            for (size_t j = 0; j < erase.size(); j += 3) erase[j] = 1;
+            G.apply_ba_erase(g, erase);
+        }
         return 0;
     }
     if (argc >= 11 && !strcmp(argv[1], "stereo")) {                 // the stereo Frame constructor up to ComputeStereoMatches (Frame.cc:70-99): left.raw right.raw width height nfeatures scale nlevels fx bf

@@ -551,6 +551,33 @@ public:
         }
         return erased;
     }
+    // The graph of Optimizer::LocalBundleAdjustment(keyframe mnId) (Optimizer.cc:453-504, :572-653), or with mode = SGX_COVIS_BA_GLOBAL that of
+    // Optimizer::BundleAdjustment over the whole map (:49-150; mnId is not read): the index arrays of sgx_ba_problem.  Two calls: the counts, then rows of exactly the need.
+    struct BaGraph {
+        std::vector<int32_t> pose_id, point_id, point_edge_begin, edge_pose, edge_point, edge_kp; std::vector<uint8_t> pose_fixed, edge_attr; sgx_covis_ba_report report{};
+    };
+    BaGraph ba_graph(int32_t mnId, int mode = SGX_COVIS_BA_LOCAL)
+    {
+        BaGraph g; g.pose_id.resize((size_t)maxkf_); g.pose_fixed.resize((size_t)maxkf_); g.point_edge_begin.resize(1);
+        int rc = sgx_covis_ba_graph(h_, mode, mnId, g.pose_id.data(), g.pose_fixed.data(), 0, nullptr, g.point_edge_begin.data(), 0, nullptr, nullptr, nullptr, nullptr, &g.report);
+        if (rc != SGX_OK && rc != SGX_ERR_NOMEM) check(rc, "sgx_covis_ba_graph");
+        const size_t np = (size_t)g.report.n_points, ne = (size_t)g.report.n_edges;
+        g.point_id.resize(np); g.point_edge_begin.resize(np + 1); g.edge_pose.resize(ne); g.edge_point.resize(ne); g.edge_kp.resize(ne); g.edge_attr.resize(ne);
+        if (rc != SGX_OK)
+            check(sgx_covis_ba_graph(h_, mode, mnId, g.pose_id.data(), g.pose_fixed.data(), (int)np, g.point_id.data(), g.point_edge_begin.data(), (int)ne, g.edge_pose.data(),
+                                     g.edge_point.data(), g.edge_kp.data(), g.edge_attr.data(), &g.report), "sgx_covis_ba_graph");
+        g.pose_id.resize((size_t)g.report.n_poses); g.pose_fixed.resize((size_t)g.report.n_poses);
+        return g;
+    }
+    // vToErase (Optimizer.cc:711-757) into the relation: the flagged monocular edges in edge order, then the flagged stereo ones, each EraseMapPointMatch +
+    // EraseObservation with its SetBadFlag at nObs <= 2.  erase: the flags sgx_local_bundle_adjustment returned for the problem flattened from g.
+    void apply_ba_erase(const BaGraph &g, const std::vector<uint8_t> &erase)
+    {
+        if (erase.size() != g.edge_pose.size()) check(SGX_ERR_INVALID, "apply_ba_erase");
+        for (int stereo = 0; stereo < 2; stereo++)
+            for (size_t j = 0; j < erase.size(); j++)
+                if (erase[j] && ((g.edge_attr[j] & SGX_COVIS_ATTR_RIGHT) != 0) == (stereo != 0)) EraseMapPointMatch(g.pose_id[(size_t)g.edge_pose[j]], g.edge_kp[j]);
+    }
     sgx_covis *handle() const { return h_; }
 private:
     template <class F> std::vector<std::pair<int32_t, int32_t>> pairs(F fn, int32_t mnId, const char *what)

@@ -49,6 +49,27 @@ class Optimizer:
         return erase, dict(iterations=(st.iterations_first, st.iterations_second), chi2=(st.chi2_first, st.chi2_second), free_poses=st.free_poses)
 
     @staticmethod
+    def flatten_ba_problem(graph, keyframes, points, inv_level_sigma2):
+        """The dict LocalBundleAdjustment / BundleAdjustment take, from a graph of CovisibilityGraph.local_ba_graph / global_ba_graph (status 0) and the caller's arrays:
+        keyframes[id] = dict(Tcw [4,4], uv [n,2] = mvKeysUn[i].pt, uright [n] = mvuRight), points [P,3] = GetWorldPos() by point id, inv_level_sigma2 = mvInvLevelSigma2.
+        edge_obs = (u, v, uR) with uR = -1 for a monocular edge (Optimizer.cc:594), edge_info = mvInvLevelSigma2[octave] (:604, :632).  A numpy gather: the solver takes
+        host pointers."""
+        assert graph['status'] == 0, 'a graph that did not fit its rows'
+        ids = [int(k) for k in graph['pose_id']]; ne = len(graph['edge_pose'])
+        poses = np.stack([np.asarray(keyframes[k]['Tcw'], 'f4').reshape(4, 4) for k in ids]) if ids else np.zeros((0, 4, 4), 'f4')
+        pts = np.ascontiguousarray(np.asarray(points, 'f4').reshape(-1, 3)[graph['point_id']])
+        ep = np.ascontiguousarray(graph['edge_pose'], 'i4'); kp = np.asarray(graph['edge_kp']); attr = np.asarray(graph['edge_attr'])
+        obs = np.zeros((ne, 3), 'f4')
+        for j, k in enumerate(ids):
+            m = ep == j
+            if not m.any(): continue
+            obs[m, :2] = np.asarray(keyframes[k]['uv'], 'f4').reshape(-1, 2)[kp[m]]; obs[m, 2] = np.asarray(keyframes[k]['uright'], 'f4').reshape(-1)[kp[m]]
+        obs[(attr & 32) == 0, 2] = -1.0
+        info = np.ascontiguousarray(np.asarray(inv_level_sigma2, 'f4')[attr & 31])
+        return dict(poses=poses, pose_fixed=np.ascontiguousarray(graph['pose_fixed'], np.uint8), points=pts, edge_pose=ep,
+                    edge_point=np.ascontiguousarray(graph['edge_point'], 'i4'), edge_obs=obs, edge_info=info)
+
+    @staticmethod
     def BundleAdjustment(problem, cam, nIterations=5, stop_flag=None, nLoopKF=0, bRobust=True, lib=None):
         """Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust) on the flattened graph (pose_fixed != 0 exactly for the keyframe
         with mnId == 0).  nLoopKF == 0: problem['poses'] / ['points'] are updated in place (SetPose / SetWorldPos); otherwise the results are returned under
