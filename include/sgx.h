@@ -865,6 +865,78 @@ int sgx_covis_ba_graph_batch_dev(sgx_covis *h, int Q, int mode, const int32_t *k
 int sgx_covis_ba_graph(sgx_covis *h, int mode, int32_t kf_id, int32_t *pose_id, uint8_t *pose_fixed, int pcap, int32_t *point_id, int32_t *point_edge_begin,
                        int ecap, int32_t *edge_pose, int32_t *edge_point, int32_t *edge_kp, uint8_t *edge_attr, sgx_covis_ba_report *report);
 
+/* Loop closing from the relation: the map bookkeeping of LoopClosing::CorrectLoop (src/sg-slam/src/LoopClosing.cc:432-573) and the vertex and edge loops of
+ * Optimizer::OptimizeEssentialGraph (Optimizer.cc:797-983) as index arrays.  Integers only, nothing read back inside a sequence, no result depends on which wave
+ * finishes first, two runs byte-identical.  The Sim3 arithmetic on these indices is sgx_loop_propagate_sim3 / sgx_eg_flatten / sgx_eg_recover.
+ * State: mspLoopEdges.
+ *   add_loop_edge(a, b): b into a's set and a into b's (CorrectLoop :572-573 calls both); a set, so the same edge again (either way round) changes nothing.  Host
+ *     pointers, synchronous, the two changed words are uploaded.  Capacity max_keyframes pairs: beyond it SGX_ERR_NOMEM with the handle unchanged.  An unknown or erased
+ *     id, or a == b: SGX_ERR_INVALID.  get_loop_edges: the partners in ascending id (rule 1; capacity max_keyframes).  sgx_covis_clear drops the edges.
+ *   The device memory of the edges and of the three sequences below is not part of sgx_covis_create's: it is allocated by the first of these calls, once,
+ *     4 x max_keyframes x (max_keyframes + 29) + 32 bytes; sgx_covis_loop_info reports it (0 before) and the number of edges.  sgx_covis_info is unchanged.
+ *  10. erase_keyframe of a keyframe that has a loop edge is refused with SGX_ERR_INVALID and changes nothing: AddLoopEdge sets mbNotErase and SetBadFlag only records
+ *      mbToBeErased (KeyFrame.cc:419-424, :454-464).  That gate stays the caller's control flow.
+ *  11. a dead list entry (rule 4: an erased keyframe a list or a row still names) is not a group member, not a loop connection and not an edge end: it has no vertex
+ *      (Optimizer.cc:812 skips it; the reference would dereference a null vertex).
+ * loop_begin(cur): CorrectLoop :432-436 and the marks of :472-516, one launch sequence:
+ *   UpdateConnections(cur); the group mvpCurrentConnectedKFs = GetVectorCovisibleKeyFrames() of cur in list order without dead entries, then cur: group_id_dev (capacity
+ *   max_keyframes) and group_vertex_dev = each member's index among the live keyframes in ascending id (the pose row of SGX_COVIS_BA_GLOBAL, the vertex row below);
+ *   UpdateConnections of every member in ascending id (the :515 call inside the walk of CorrectedSim3, a map<KeyFrame*, ...>: rule 1); the existing points of the group:
+ *   point_id_dev = first occurrence over the members in ascending id, then keypoint index order, point_ref_dev = mnCorrectedReference as an index into the group row: the
+ *   member of smallest id that holds the point (what the mnCorrectedByKF test of :488 amounts to), also when it stands later in the list.  The first pcap points are
+ *   written; more than pcap is SGX_ERR_NOMEM in the report, whose n_group and n_points are the true counts.  cur unknown or erased, pcap < 0, a missing array:
+ *   SGX_ERR_INVALID for the call, nothing enqueued.
+ * loop_connections(cur, group row): CorrectLoop :546-564, after the caller's fusion (replace_point / set_observations).  For each member in LIST order: prev = its
+ *   ordered list as its mode defines it now (an earlier member's UpdateConnections may have rebuilt it through AddConnection); UpdateConnections of the member;
+ *   LoopConnections[member] = the keys of its weight row, minus prev, minus the group, minus dead keys (rule 11: also those of an old row an empty KFcounter left in
+ *   place).  Output: CSR over the members in ascending id (the map's order) with the targets of each in ascending id (the set's order): lc_begin_dev (n_group + 1, always
+ *   whole) and lc_j_dev (keyframe ids, capacity lcap).  More than lcap: SGX_ERR_NOMEM in the report (n_connections the true count), and only the rows that fit wholly
+ *   (lc_begin[r + 1] <= lcap) are written.  The group row is an input: an id that is no live keyframe, an id twice, or a last entry other than cur is SGX_ERR_INVALID in
+ *   the report with nothing written and the handle unchanged.  n_group outside [1, live keyframes], lcap < 0, a missing array: SGX_ERR_INVALID for the call.
+ * essential_graph(cur, loop, group row, CSR): a query, the handle is not changed.
+ *   vertices: vertex_id_dev = all live keyframes in ascending id, vertex_fixed_dev = 1 for loop, vertex_group_dev = the index into the group row or -1 (rows of
+ *     max_keyframes).  A vertex of the group starts from its corrected Sim3, any other from its pose.
+ *   edges in the reference's insertion order, e_i = vertex 0 (the keyframe whose loop it is), e_j = vertex 1, as vertex indices, e_kind:
+ *     0 loop connections (:852-880): CSR order; an entry is kept if (i == cur && j == loop) || i->GetWeight(j) >= 100, the weight read from i's OWN row (rows are not
+ *       symmetric: UpdateConnections writes only gated entries into the neighbour).  Only kept edges enter sInsertedEdges.  Both operands of the measurement are vScw.
+ *     then per vertex in ascending id (for kinds 1-3 an operand of the measurement is NonCorrectedSim3 for a group vertex, vScw otherwise):
+ *     1 the spanning-tree edge to the parent, also when the pair is in sInsertedEdges;
+ *     2 the keyframe's loop edges of smaller id, in ascending id;
+ *     3 GetCovisiblesByWeight(100) in list order, as written (KeyFrame.cc:185-200): upper_bound finds the first list entry below 100; if there is none (an empty list, or
+ *       every entry >= 100) the result is EMPTY, so a gated list whose entries all reach 100 contributes no covisibility edge while the same row in mode "all" with one
+ *       weak entry contributes all the strong ones (the list is state).  Dropped: the parent, a child, a loop edge, a dead entry, an entry of larger-or-equal id, a pair
+ *       in sInsertedEdges.
+ *   The first ecap edges are written; more is SGX_ERR_NOMEM in the report, which holds the true n_vertices, n_edges and the count per kind.
+ *   lc_j_dev has capacity lcap.  SGX_ERR_INVALID in the report, nothing else written: a group row refused as above; lc_begin not starting at 0, descending or beyond lcap;
+ *   a target that is no live keyframe; a row whose targets are not strictly ascending.  cur or loop unknown or erased, ecap < 0, a missing array: SGX_ERR_INVALID for
+ *   the call. */
+typedef struct sgx_covis_loop_report {
+    int32_t status;                         /* SGX_OK, SGX_ERR_INVALID, SGX_ERR_NOMEM */
+    int32_t n_group, n_points;              /* loop_begin: the true counts */
+    int32_t n_connections;                  /* loop_connections: the true count; essential_graph: lc_begin[n_group] */
+    int32_t n_vertices, n_edges;            /* essential_graph: the true counts */
+    int32_t n_kind[4];                      /* essential_graph: edges per kind */
+} sgx_covis_loop_report;
+int sgx_covis_add_loop_edge(sgx_covis *h, int32_t kf_a, int32_t kf_b);
+int sgx_covis_get_loop_edges(const sgx_covis *h, int32_t kf_id, int32_t *kf_ids, int32_t *n);
+int sgx_covis_loop_info(const sgx_covis *h, int64_t *loop_bytes, int32_t *n_loop_edges);
+/* device pointers, asynchronous on `stream`; a handle serves one call at a time */
+int sgx_covis_loop_begin_dev(sgx_covis *h, int32_t cur, int32_t *group_id_dev, int32_t *group_vertex_dev, int pcap, int32_t *point_id_dev, int32_t *point_ref_dev,
+                             sgx_covis_loop_report *report_dev, void *stream);
+int sgx_covis_loop_connections_dev(sgx_covis *h, int32_t cur, int n_group, const int32_t *group_id_dev, int lcap, int32_t *lc_begin_dev, int32_t *lc_j_dev,
+                                   sgx_covis_loop_report *report_dev, void *stream);
+int sgx_covis_essential_graph_dev(sgx_covis *h, int32_t cur, int32_t loop, int n_group, const int32_t *group_id_dev, int lcap, const int32_t *lc_begin_dev,
+                                  const int32_t *lc_j_dev, int32_t *vertex_id_dev, uint8_t *vertex_fixed_dev, int32_t *vertex_group_dev, int ecap, int32_t *e_i_dev,
+                                  int32_t *e_j_dev, uint8_t *e_kind_dev, sgx_covis_loop_report *report_dev, void *stream);
+/* the same from host memory, synchronous; the return value is the report's status.  Written: the first n_group entries of the group rows (capacity max_keyframes) and
+ * the first min(n_points, pcap) points; lc_begin whole and the rows of lc_j that fit; the first n_vertices of the vertex rows (capacity max_keyframes) and the first
+ * min(n_edges, ecap) edges.  essential_graph takes lcap = lc_begin[n_group]. */
+int sgx_covis_loop_begin(sgx_covis *h, int32_t cur, int32_t *group_id, int32_t *group_vertex, int pcap, int32_t *point_id, int32_t *point_ref, sgx_covis_loop_report *report);
+int sgx_covis_loop_connections(sgx_covis *h, int32_t cur, int n_group, const int32_t *group_id, int lcap, int32_t *lc_begin, int32_t *lc_j, sgx_covis_loop_report *report);
+int sgx_covis_essential_graph(sgx_covis *h, int32_t cur, int32_t loop, int n_group, const int32_t *group_id, const int32_t *lc_begin, const int32_t *lc_j,
+                              int32_t *vertex_id, uint8_t *vertex_fixed, int32_t *vertex_group, int ecap, int32_t *e_i, int32_t *e_j, uint8_t *e_kind,
+                              sgx_covis_loop_report *report);
+
 /* The colour conversion at the top of Tracking::GrabImageRGBD (src/sg-slam/src/Tracking.cc:214-227): cvtColor(CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) on
  * 8-bit images, OpenCV's fixed point (R*4899 + G*9617 + B*1868 + 8192) >> 14.  blue_first = !mbRGB.  Pitches in bytes, multiples of 4; pointers 4-byte aligned. */
 int sgx_frame_gray_from_color_batch_dev(int batch, int width, int height, const uint8_t *d_src, int src_pitch, int channels, int blue_first,
@@ -981,6 +1053,32 @@ int sgx_optimize_essential_graph(int nv, const double *S_in, const uint8_t *fixe
 /* The map-point correction that follows (Optimizer.cc:1004-1041): xw_out[i] = correctedSwr.map(Srw.map(xw[i])) with r = ref[i], the point's reference keyframe (or mnCorrectedReference);
  * Srw = vScw, corrected_Swr = vCorrectedSwc (nv x 8 each).  The pose recovery [R t/s; 0 1] (:975-985) is three divisions on the host. */
 int sgx_correct_map_points(int n, const float *xw, const int32_t *ref, int nv, const double *Srw, const double *corrected_Swr, float *xw_out);
+/* The Sim3 arithmetic of loop closing between the index rows of sgx_covis_loop_begin / sgx_covis_essential_graph and the two entries above.  A Sim3 is 8 doubles
+ * (qx, qy, qz, qw, tx, ty, tz, s), a pose 12 floats, the rows of [R | t].  Double except where the reference is float; device, emulator and a scalar float64 restatement
+ * (tests/loop_ref.py) agree in every bit.  The _dev forms take device pointers and a stream and check nothing they would have to read back: vertex_group in [-1, n_group)
+ * and edge ends in [0, nv) are the caller's, as sgx_covis_essential_graph writes them; the host forms check them (SGX_ERR_INVALID) and are synchronous.
+ * sgx_loop_propagate_sim3 (LoopClosing::CorrectLoop, LoopClosing.cc:440-469, :503-512): Tcw of the group in group order, the current keyframe last, and its Scw.
+ *   noncorrected[g] = Sim3(Riw, tiw, 1); corrected[g] = Sim3(Ric, tic, 1) * Scw with Tic = Tiw * Twc, a float cv::Mat product on cv::gemm's small-matrix path (float dot
+ *   product left to right, four terms, the result through double with alpha), Twc as KeyFrame::SetPose builds it (Rwc = Rcw.t(), Ow = -Rwc * tcw: alpha = -1); for the
+ *   current keyframe Scw itself; corrected_Tiw[g] = (toRotationMatrix(), t * (1 / s)) cast to float, what :503-512 hands to SetPose.
+ *   CorrectLoop's point correction (:491-497) is sgx_correct_map_points with ref = point_ref, Srw = noncorrected, corrected_Swr = the inverses of corrected
+ *   (sgx_eg_recover of corrected gives them).
+ * sgx_eg_flatten (Optimizer.cc:818-832, :857-867, :889-972): S_in[v] = corrected[vertex_group[v]] for a vertex of the group, Sim3(Rcw, tcw, 1) of Tcw[v] otherwise (Tcw:
+ *   nv poses in vertex order; a group vertex's is not read); e_meas[k] = Sjw * Swi, both operands S_in for e_kind 0, noncorrected for a group vertex of kinds 1-3.
+ *   The outputs with vertex_fixed, e_i and e_j are what sgx_optimize_essential_graph takes.
+ * sgx_eg_recover (:991-1010): Tcw[v] = (toRotationMatrix(), t * (1 / s)) of S_out[v] cast to float, corrected_Swc[v] = S_out[v].inverse(); the point correction of
+ *   :1013-1041 is sgx_correct_map_points with Srw = S_in and corrected_Swr = corrected_Swc.
+ * sgx_correct_map_points_dev: sgx_correct_map_points on device pointers and a stream (ref in [0, number of Sim3 rows) is the caller's), evaluated as written like the
+ *   three above; the host-pointer form lets multiply-adds fuse and may differ from it in the last bit of a float. */
+int sgx_loop_propagate_sim3_dev(int n_group, const float *Tcw_dev, const double *Scw_dev, double *noncorrected_dev, double *corrected_dev, float *corrected_Tiw_dev, void *stream);
+int sgx_eg_flatten_dev(int nv, const int32_t *vertex_group_dev, const float *Tcw_dev, int n_group, const double *corrected_dev, const double *noncorrected_dev, int ne,
+                       const int32_t *e_i_dev, const int32_t *e_j_dev, const uint8_t *e_kind_dev, double *S_in_dev, double *e_meas_dev, void *stream);
+int sgx_eg_recover_dev(int nv, const double *S_out_dev, float *Tcw_dev, double *corrected_Swc_dev, void *stream);
+int sgx_correct_map_points_dev(int n, const float *xw_dev, const int32_t *ref_dev, const double *Srw_dev, const double *corrected_Swr_dev, float *xw_out_dev, void *stream);
+int sgx_loop_propagate_sim3(int n_group, const float *Tcw, const double *Scw, double *noncorrected, double *corrected, float *corrected_Tiw);
+int sgx_eg_flatten(int nv, const int32_t *vertex_group, const float *Tcw, int n_group, const double *corrected, const double *noncorrected, int ne, const int32_t *e_i,
+                   const int32_t *e_j, const uint8_t *e_kind, double *S_in, double *e_meas);
+int sgx_eg_recover(int nv, const double *S_out, float *Tcw, double *corrected_Swc);
 
 /* ---- 2-D detector + dynamic-feature mask --------------------------------------------------------
  * Replaces ORB_SLAM2::Detector2D (src/sg-slam/include/Detector2D.h:45-67, src/sg-slam/src/Detector2D.cc:16-89): the ncnn

@@ -133,6 +133,7 @@ COVIS_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_counter', 'max_w
                                                    'ref_tracked')])   # sgx_covis_report, 40 B
 COVIS_BA_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_local_kf', 'n_fixed_kf', 'n_poses', 'n_points', 'n_edges', 'n_mono_edges',
                                                       'n_stereo_edges')])   # sgx_covis_ba_report, 32 B
+COVIS_LOOP_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_group', 'n_points', 'n_connections', 'n_vertices', 'n_edges')] + [('n_kind', 'i4', (4,))])   # sgx_covis_loop_report, 40 B
 
 
 class OrbConfig(C.Structure):
@@ -176,7 +177,9 @@ SYMBOLS = [
     'sgx_covis_set_points_bad', 'sgx_covis_replace_point', 'sgx_covis_erase_keyframe', 'sgx_covis_get_weights', 'sgx_covis_get_ordered', 'sgx_covis_best_covisibles',
     'sgx_covis_get_tree', 'sgx_covis_get_observations', 'sgx_covis_get_keyframe_points', 'sgx_covis_update_connections_batch_dev', 'sgx_covis_local_map_batch_dev',
     'sgx_covis_keyframe_culling_batch_dev', 'sgx_covis_update_connections', 'sgx_covis_local_map', 'sgx_covis_keyframe_culling', 'sgx_covis_ba_graph_batch_dev',
-    'sgx_covis_ba_graph',
+    'sgx_covis_ba_graph', 'sgx_covis_add_loop_edge', 'sgx_covis_get_loop_edges', 'sgx_covis_loop_info', 'sgx_covis_loop_begin_dev', 'sgx_covis_loop_connections_dev',
+    'sgx_covis_essential_graph_dev', 'sgx_covis_loop_begin', 'sgx_covis_loop_connections', 'sgx_covis_essential_graph',
+    'sgx_loop_propagate_sim3_dev', 'sgx_eg_flatten_dev', 'sgx_eg_recover_dev', 'sgx_correct_map_points_dev', 'sgx_loop_propagate_sim3', 'sgx_eg_flatten', 'sgx_eg_recover',
     'sgx_octomap_create', 'sgx_octomap_destroy', 'sgx_octomap_reset', 'sgx_octomap_insert_batch_dev', 'sgx_octomap_insert', 'sgx_octomap_bounds', 'sgx_octomap_cells_dev',
     'sgx_octomap_cells', 'sgx_octomap_search_dev', 'sgx_octomap_grid_header', 'sgx_octomap_project_dev', 'sgx_octomap_project', 'sgx_octomap_sensor_to_world',
     'sgx_globalmap_create', 'sgx_globalmap_destroy', 'sgx_globalmap_reset', 'sgx_globalmap_append_batch_dev', 'sgx_globalmap_append', 'sgx_globalmap_consolidate_dev',
@@ -385,6 +388,22 @@ class SgxLib:
         d.sgx_covis_keyframe_culling.argtypes = [vp, C.c_int32, C.c_int, vp, vp, vp, vp, vp]
         d.sgx_covis_ba_graph_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 6
         d.sgx_covis_ba_graph.argtypes = [vp, C.c_int, C.c_int32, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 5
+        d.sgx_covis_add_loop_edge.argtypes = [vp, C.c_int32, C.c_int32]
+        d.sgx_covis_get_loop_edges.argtypes = [vp, C.c_int32, vp, vp]
+        d.sgx_covis_loop_info.argtypes = [vp, vp, vp]
+        d.sgx_covis_loop_begin_dev.argtypes = [vp, C.c_int32, vp, vp, C.c_int, vp, vp, vp, vp]
+        d.sgx_covis_loop_connections_dev.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+        d.sgx_covis_essential_graph_dev.argtypes = [vp, C.c_int32, C.c_int32, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+        d.sgx_covis_loop_begin.argtypes = [vp, C.c_int32, vp, vp, C.c_int, vp, vp, vp]
+        d.sgx_covis_loop_connections.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int, vp, vp, vp]
+        d.sgx_covis_essential_graph.argtypes = [vp, C.c_int32, C.c_int32, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+        d.sgx_loop_propagate_sim3_dev.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp]
+        d.sgx_eg_flatten_dev.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+        d.sgx_eg_recover_dev.argtypes = [C.c_int, vp, vp, vp, vp]
+        d.sgx_correct_map_points_dev.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp]
+        d.sgx_loop_propagate_sim3.argtypes = [C.c_int, vp, vp, vp, vp, vp]
+        d.sgx_eg_flatten.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+        d.sgx_eg_recover.argtypes = [C.c_int, vp, vp, vp]
         d.sgx_octomap_create.argtypes = [C.POINTER(OctomapParams), C.c_int, C.c_int, C.POINTER(vp)]
         d.sgx_octomap_destroy.argtypes = [vp]; d.sgx_octomap_destroy.restype = None
         d.sgx_octomap_reset.argtypes = [vp]

@@ -4,10 +4,11 @@ The relation "keyframe k observes map point p at keypoint index i" lives on the 
 lists, the spanning tree, every point's observations and nObs).  Mutations take host arrays and are synchronous; the three walks — KeyFrame::UpdateConnections
 (KeyFrame.cc:290-380), Tracking::UpdateLocalMap (Tracking.cc:1314-1458) and the votes of LocalMapping::KeyFrameCulling (LocalMapping.cc:632-696) — are batched launch
 sequences on a stream, and so is the graph of Optimizer::LocalBundleAdjustment / BundleAdjustment (Optimizer.cc:453-504, :572-653, :49-150): local_ba_graph,
-global_ba_graph, ba_graph_batch, with apply_ba_erase for the vToErase loop (:745-757).  Keyframes are named by the caller's mnId, points by dense handles in [0, max_points)."""
+global_ba_graph, ba_graph_batch, with apply_ba_erase for the vToErase loop (:745-757), and the map bookkeeping of LoopClosing::CorrectLoop (LoopClosing.cc:432-573)
+with the vertices and edges of Optimizer::OptimizeEssentialGraph (Optimizer.cc:797-983): add_loop_edge, loop_begin, loop_connections, essential_graph.  Keyframes are named by the caller's mnId, points by dense handles in [0, max_points)."""
 import ctypes as C
 import numpy as np
-from .capi import _vp, COVIS_REPORT_DTYPE, COVIS_BA_REPORT_DTYPE
+from .capi import _vp, COVIS_REPORT_DTYPE, COVIS_BA_REPORT_DTYPE, COVIS_LOOP_REPORT_DTYPE
 
 
 def _i4(v):
@@ -236,6 +237,132 @@ class CovisibilityGraph:
             self.set_observations(kf, [int(graph['edge_kp'][j])], [-1])
             done.append((kf, int(graph['point_id'][graph['edge_point'][j]])))
         return done
+
+    # ---- loop closing: mspLoopEdges, CorrectLoop's group / LoopConnections and the graph of OptimizeEssentialGraph
+    def add_loop_edge(self, kf_a, kf_b):
+        """KeyFrame::AddLoopEdge both ways (LoopClosing.cc:572-573); a set: the same edge again changes nothing"""
+        self.lib.check(self.lib.dll.sgx_covis_add_loop_edge(self.h, int(kf_a), int(kf_b)), 'sgx_covis_add_loop_edge')
+
+    def loop_edges(self, kf_id):
+        """mspLoopEdges of the keyframe as ids ascending"""
+        a = np.zeros(self.max_keyframes, 'i4'); n = C.c_int32()
+        self.lib.check(self.lib.dll.sgx_covis_get_loop_edges(self.h, int(kf_id), _vp(a), C.byref(n)), 'sgx_covis_get_loop_edges')
+        return [int(x) for x in a[:n.value]]
+
+    def loop_info(self):
+        """(device bytes the loop calls allocated beyond create's: 0 before the first of them, loop edges)"""
+        a = C.c_int64(); n = C.c_int32()
+        self.lib.check(self.lib.dll.sgx_covis_loop_info(self.h, C.byref(a), C.byref(n)), 'sgx_covis_loop_info')
+        return a.value, n.value
+
+    def loop_begin_dev(self, cur, group_id_dev, group_vertex_dev, pcap, point_id_dev, point_ref_dev, report_dev, stream=None):
+        self._keep = (group_id_dev, group_vertex_dev, point_id_dev, point_ref_dev, report_dev)
+        self.lib.check(self.lib.dll.sgx_covis_loop_begin_dev(self.h, int(cur), _vp(group_id_dev), _vp(group_vertex_dev), int(pcap), _vp(point_id_dev), _vp(point_ref_dev),
+                                                             _vp(report_dev), self._stream(stream)), 'sgx_covis_loop_begin_dev')
+
+    def loop_begin(self, cur, pcap=None, stream=None):
+        """LoopClosing::CorrectLoop :432-436 and the marks of :472-516: UpdateConnections(cur), the group (the listed neighbours without dead entries, then cur), the
+        UpdateConnections of every member in ascending id, and the group's existing points with mnCorrectedReference.  Returns status, group_id, group_vertex, point_id,
+        point_ref (an index into the group row) trimmed to what was written, and the report (the true counts)."""
+        N = self.max_keyframes
+        pcap = int(min(self.max_points, self.info()[2]) if pcap is None else pcap); pc = max(pcap, 0)
+        d = [self._dev(x) for x in (np.full(N, -1, 'i4'), np.full(N, -1, 'i4'), np.full(max(pc, 1), -1, 'i4'), np.full(max(pc, 1), -1, 'i4'),
+                                    np.zeros(COVIS_LOOP_REPORT_DTYPE.itemsize, 'u1'))]
+        self.loop_begin_dev(cur, d[0], d[1], pcap, d[2], d[3], d[4], stream)
+        self._sync(stream)
+        gid, gv, pid, pref, rep = [self._host(x) for x in d]
+        r = rep.view(COVIS_LOOP_REPORT_DTYPE)[0].copy(); ng = int(r['n_group']); npt = min(int(r['n_points']), pc)
+        return dict(status=int(r['status']), group_id=gid[:ng].copy(), group_vertex=gv[:ng].copy(), point_id=pid[:npt].copy(), point_ref=pref[:npt].copy(), report=r)
+
+    def loop_connections_dev(self, cur, n_group, group_id_dev, lcap, lc_begin_dev, lc_j_dev, report_dev, stream=None):
+        self._keep = (group_id_dev, lc_begin_dev, lc_j_dev, report_dev)
+        self.lib.check(self.lib.dll.sgx_covis_loop_connections_dev(self.h, int(cur), int(n_group), _vp(group_id_dev), int(lcap), _vp(lc_begin_dev), _vp(lc_j_dev),
+                                                                   _vp(report_dev), self._stream(stream)), 'sgx_covis_loop_connections_dev')
+
+    def loop_connections(self, cur, group_id, lcap=None, stream=None):
+        """CorrectLoop :546-564 after the caller's fusion: per member in list order its previous list, UpdateConnections, LoopConnections = the keys of its row minus
+        the previous list minus the group.  Returns status, lc_begin (CSR over the members in ascending id; None for a refused group row), lc_j (ids ascending per row,
+        the rows that fit wholly) and the report."""
+        g = _i4(group_id); ng = len(g)
+        lcap = int(ng * self.max_keyframes if lcap is None else lcap); lc = max(lcap, 0)
+        d = [self._dev(x) for x in (g, np.full(ng + 1, -1, 'i4'), np.full(max(lc, 1), -1, 'i4'), np.zeros(COVIS_LOOP_REPORT_DTYPE.itemsize, 'u1'))]
+        self.loop_connections_dev(cur, ng, d[0], lcap, d[1], d[2], d[3], stream)
+        self._sync(stream)
+        _, beg, lj, rep = [self._host(x) for x in d]
+        r = rep.view(COVIS_LOOP_REPORT_DTYPE)[0].copy()
+        if int(r['status']) == -1: return dict(status=-1, lc_begin=None, lc_j=None, report=r, raw=(beg, lj))
+        nw = int(beg[np.searchsorted(beg, lc, side='right') - 1])
+        return dict(status=int(r['status']), lc_begin=beg.copy(), lc_j=lj[:nw].copy(), report=r, raw=(beg, lj))
+
+    def essential_graph_dev(self, cur, loop, n_group, group_id_dev, lcap, lc_begin_dev, lc_j_dev, vertex_id_dev, vertex_fixed_dev, vertex_group_dev, ecap, e_i_dev, e_j_dev,
+                            e_kind_dev, report_dev, stream=None):
+        self._keep = (group_id_dev, lc_begin_dev, lc_j_dev, vertex_id_dev, vertex_fixed_dev, vertex_group_dev, e_i_dev, e_j_dev, e_kind_dev, report_dev)
+        self.lib.check(self.lib.dll.sgx_covis_essential_graph_dev(self.h, int(cur), int(loop), int(n_group), _vp(group_id_dev), int(lcap), _vp(lc_begin_dev), _vp(lc_j_dev),
+                                                                  _vp(vertex_id_dev), _vp(vertex_fixed_dev), _vp(vertex_group_dev), int(ecap), _vp(e_i_dev), _vp(e_j_dev),
+                                                                  _vp(e_kind_dev), _vp(report_dev), self._stream(stream)), 'sgx_covis_essential_graph_dev')
+
+    def essential_graph(self, cur, loop, group_id, lc_begin, lc_j, ecap=None, stream=None):
+        """The vertices and edges of Optimizer::OptimizeEssentialGraph (Optimizer.cc:797-983) for the group row of loop_begin and the CSR of loop_connections.  Returns
+        status, vertex_id, vertex_fixed, vertex_group, e_i, e_j, e_kind (0 loop connection, 1 spanning tree, 2 loop edge, 3 covisibility) and the report."""
+        g = _i4(group_id); b = _i4(lc_begin); j = _i4(lc_j); ng = len(g); N = self.max_keyframes
+        assert len(b) == ng + 1
+        n = self.size()
+        ecap = int(len(j) + n * (n + 1) // 2 + n + self.loop_info()[1] if ecap is None else ecap); ec = max(ecap, 0)
+        d = [self._dev(x) for x in (g, b, j if len(j) else np.zeros(1, 'i4'), np.full(N, -1, 'i4'), np.full(N, 255, 'u1'), np.full(N, -9, 'i4'), np.full(max(ec, 1), -1, 'i4'),
+                                    np.full(max(ec, 1), -1, 'i4'), np.full(max(ec, 1), 255, 'u1'), np.zeros(COVIS_LOOP_REPORT_DTYPE.itemsize, 'u1'))]
+        self.essential_graph_dev(cur, loop, ng, d[0], len(j), d[1], d[2], d[3], d[4], d[5], ecap, d[6], d[7], d[8], d[9], stream)
+        self._sync(stream)
+        _, _, _, vid, vfx, vgr, ei, ej, ek, rep = [self._host(x) for x in d]
+        r = rep.view(COVIS_LOOP_REPORT_DTYPE)[0].copy(); st = int(r['status'])
+        raw = (vid, vfx, vgr, ei, ej, ek)
+        if st == -1: return dict(status=st, report=r, raw=raw)
+        nv = int(r['n_vertices']); ne = min(int(r['n_edges']), ec)
+        return dict(status=st, vertex_id=vid[:nv].copy(), vertex_fixed=vfx[:nv].copy(), vertex_group=vgr[:nv].copy(), e_i=ei[:ne].copy(), e_j=ej[:ne].copy(),
+                    e_kind=ek[:ne].copy(), report=r, raw=raw)
+
+    def correct_map_points(self, xw, ref, Srw, corrected_Swr, stream=None):
+        """P' = correctedSwr.map(Srw.map(P)) through sgx_correct_map_points_dev, the form evaluated as written (bit-equal to the scalar restatement)"""
+        x = np.ascontiguousarray(xw, 'f4').reshape(-1, 3); n = len(x)
+        if n == 0: return x.copy()
+        d = [self._dev(v) for v in (x, _i4(ref), np.ascontiguousarray(Srw, 'f8').reshape(-1, 8), np.ascontiguousarray(corrected_Swr, 'f8').reshape(-1, 8), np.zeros((n, 3), 'f4'))]
+        self._keep = d
+        self.lib.check(self.lib.dll.sgx_correct_map_points_dev(n, _vp(d[0]), _vp(d[1]), _vp(d[2]), _vp(d[3]), _vp(d[4]), self._stream(stream)), 'sgx_correct_map_points_dev')
+        self._sync(stream)
+        return np.array(self._host(d[4]), 'f4')
+
+    def correct_loop(self, cur, loop, Scw, Tcw, xw, fuse=None, fix_scale=True, point_ref_kf=None, iterations=20, stream=None):
+        """LoopClosing::CorrectLoop (LoopClosing.cc:432-573) with Optimizer::OptimizeEssentialGraph, in the reference's order: loop_begin, the Sim3 propagation and the
+        first point correction (:440-512), the caller's fusion fuse(self, begin, corrected) through replace_point / set_observations (:519-545, SearchAndFuse),
+        loop_connections, essential_graph, the flattening, the optimisation, the pose recovery and the second point correction (Optimizer.cc:1013-1041), add_loop_edge.
+        Tcw: the pose of every live keyframe by id (a dict, or an array indexed by id; 4 x 4 or 3 x 4); xw: the world positions by point id.  point_ref_kf (optional):
+        GetReferenceKeyFrame()->mnId by point id, for the points outside the group; without it the second correction covers the group's points only.
+        Returns the new poses by id (3 x 4 float32), the new points, and every intermediate row."""
+        from .optimizer import Optimizer
+        lib = self.lib
+        pose = lambda k: np.asarray(Tcw[int(k)], 'f4')[:3, :4]
+        xw = np.array(xw, 'f4').reshape(-1, 3)
+        b = self.loop_begin(cur, stream=stream)
+        assert b['status'] == 0
+        non, cor, cTiw = Optimizer.PropagateLoopSim3([pose(k) for k in b['group_id']], Scw, lib=lib)
+        cSwi = Optimizer.RecoverEssentialGraph(cor, lib=lib)[1]
+        if len(b['point_id']): xw[b['point_id']] = self.correct_map_points(xw[b['point_id']], b['point_ref'], non, cSwi, stream)
+        if fuse is not None: fuse(self, b, cor)
+        c = self.loop_connections(cur, b['group_id'], stream=stream)
+        assert c['status'] == 0
+        g = self.essential_graph(cur, loop, b['group_id'], c['lc_begin'], c['lc_j'], stream=stream)
+        assert g['status'] == 0
+        S_in, e_meas = Optimizer.FlattenEssentialGraph(g, [pose(k) for k in g['vertex_id']], cor, non, lib=lib)
+        S_out, stats = Optimizer.OptimizeEssentialGraph(S_in, g['vertex_fixed'], g['e_i'], g['e_j'], e_meas, fix_scale, iterations, lib=lib)
+        Tnew, cSwc = Optimizer.RecoverEssentialGraph(S_out, lib=lib)
+        ids = b['point_id']; ref = b['group_vertex'][b['point_ref']] if len(ids) else np.zeros(0, 'i4')
+        if point_ref_kf is not None:                                               # every existing point: mnCorrectedReference inside the group, the reference keyframe outside
+            vi = {int(k): j for j, k in enumerate(g['vertex_id'])}; mine = dict(zip([int(p) for p in ids], [int(r) for r in ref]))
+            ids = self.global_ba_graph(stream=stream)['point_id']
+            ref = np.array([mine[int(p)] if int(p) in mine else vi[int(point_ref_kf[int(p)])] for p in ids], 'i4')
+        if len(ids): xw[ids] = self.correct_map_points(xw[ids], ref, S_in, cSwc, stream)
+        if cur != loop: self.add_loop_edge(loop, cur)
+        return dict(Tcw={int(k): Tnew[j] for j, k in enumerate(g['vertex_id'])}, xw=xw, begin=b, connections=c, graph=g, noncorrected=non, corrected=cor, corrected_Tiw=cTiw,
+                    S_in=S_in, e_meas=e_meas, S_out=S_out, stats=stats, corrected_Swc=cSwc)
 
     def close(self):
         if self.h: self.lib.dll.sgx_covis_destroy(self.h); self.h = C.c_void_p()

@@ -1,8 +1,9 @@
 // sgx_covis.cpp — the covisibility graph behind the C ABI (sgx_covis_*): the relation keyframe x map point as a heap the host mirrors and patches on the device
 // (KeyFrame::AddMapPoint / EraseMapPointMatch, MapPoint::AddObservation / EraseObservation / SetBadFlag / Replace, src/sg-slam/src/MapPoint.cc:98-215), the graph
-// (weights, list modes, spanning tree) as device state, and the walks of it (UpdateConnections, UpdateLocalMap, the culling votes, the bundle-adjustment graph) as the
-// launch sequences of sgx_covis_kernels.h.
+// (weights, list modes, spanning tree, loop edges) as device state, and the walks of it (UpdateConnections, UpdateLocalMap, the culling votes, the bundle-adjustment graph,
+// loop closing's group / LoopConnections / essential graph) as the launch sequences of sgx_covis_kernels.h and sgx_covis_loop_kernels.h.
 #include "sgx_covis_kernels.h"
+#include "sgx_covis_loop_kernels.h"
 #include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #include <stdio.h>
@@ -15,6 +16,7 @@
 
 static_assert(sizeof(sgx_covis_report) == sizeof(SgxCovisReport), "the kernels write sgx_covis_report records");
 static_assert(sizeof(sgx_covis_ba_report) == sizeof(SgxCovisBaReport), "the kernels write sgx_covis_ba_report records");
+static_assert(sizeof(sgx_covis_loop_report) == sizeof(SgxCovisLoopReport), "the kernels write sgx_covis_loop_report records");
 
 enum { H_FREE = 0, H_LIVE = 1, H_HDR = 2, COVIS_JCAP = 1 << 16, COVIS_GRID = 128 };
 
@@ -36,6 +38,13 @@ struct sgx_covis {
     int *ws_q = nullptr, *ws_cnt = nullptr, *ws_ord = nullptr, *ws_ordw = nullptr, *ws_lkf = nullptr, *ws_pcnt = nullptr, *ws_top = nullptr, *ws_ntop = nullptr, *d_stamp = nullptr;
     int *s_kf = nullptr;
     int64_t device_bytes = 0, workspace_bytes = 0;
+    // loop closing: mspLoopEdges as slot pairs in insertion order (a keyframe with a loop edge is not erased, so its slot stays), and the workspace of the loop
+    // sequences, allocated by the first loop call
+    std::vector<std::pair<int, int>> loop_edges;
+    int *d_le = nullptr, *lw_s = nullptr, *lw_q = nullptr, *lw_qkf = nullptr, *lw_ord = nullptr, *lw_gslot = nullptr, *lw_grank = nullptr, *lw_rowg = nullptr, *lw_gof = nullptr,
+        *lw_vidx = nullptr, *lw_vcnt = nullptr, *lw_vbase = nullptr, *lw_flags = nullptr;
+    SgxCovisReport *lw_rep = nullptr;
+    int64_t loop_bytes = 0;
     SgxDevMem mem;
 
     int32_t &H(size_t i) { return heap[i]; }
@@ -156,6 +165,7 @@ static void covis_reset_host(sgx_covis *h)
     h->free_slots.clear();
     for (int s = h->max_kf - 1; s >= 0; s--) h->free_slots.push_back(s);
     h->by_id.clear(); h->dead_ids.clear(); h->undo.clear(); h->nslots = 0; h->tables_dirty = true;
+    h->loop_edges.clear();
 }
 
 static int covis_reset_device(sgx_covis *h)
@@ -327,6 +337,7 @@ extern "C" int sgx_covis_erase_keyframe(sgx_covis *h, int32_t kf_id)
     if (it == h->by_id.end()) return SGX_ERR_INVALID;
     if (kf_id == 0) return SGX_OK;                                                // KeyFrame.cc:458-459
     const int s = it->second, N = h->slot[(size_t)s].n;
+    for (const auto &e : h->loop_edges) if (e.first == s || e.second == s) return SGX_ERR_INVALID;      // rule 10: AddLoopEdge set mbNotErase (KeyFrame.cc:419-424, :460-464)
     for (int i = 0; i < N; i++) {
         const size_t at = h->o_mp + (size_t)s * h->cap + i;
         const int p = h->H(at);
@@ -665,4 +676,218 @@ extern "C" int sgx_covis_ba_graph(sgx_covis *h, int mode, int32_t kf_id, int32_t
         SGX_CHECK_HIP(hipMemcpy(edge_kp, d_ek, ne * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(edge_attr, d_ea, ne, hipMemcpyDeviceToHost));
     }
     return R.status;                                                               // SGX_OK, or SGX_ERR_NOMEM with what fits written
+}
+
+// ---- loop closing: mspLoopEdges, and CorrectLoop's group, LoopConnections and essential graph as launch sequences (sgx_covis_loop_kernels.h)
+// a buffer the handle does not hold yet; its size goes into loop_bytes where it is taken, so a call that fails half way is continued by the next one
+template <class T> static int covis_loop_take(sgx_covis *h, T **p, size_t n)
+{
+    if (*p) return SGX_OK;
+    const int rc = h->mem.alloc(p, n);
+    if (rc == SGX_OK) h->loop_bytes += (int64_t)(n * sizeof(T));
+    return rc;
+}
+
+static int covis_loop_ws(sgx_covis *h)
+{
+    const size_t N = (size_t)h->max_kf;
+    int rc;
+    if ((rc = covis_loop_take(h, &h->lw_s, (size_t)LS_FIELDS)) || (rc = covis_loop_take(h, &h->lw_q, N * CQ_FIELDS)) || (rc = covis_loop_take(h, &h->lw_qkf, N)) ||
+        (rc = covis_loop_take(h, &h->lw_ord, N)) || (rc = covis_loop_take(h, &h->lw_gslot, N)) || (rc = covis_loop_take(h, &h->lw_grank, N)) ||
+        (rc = covis_loop_take(h, &h->lw_rowg, N)) || (rc = covis_loop_take(h, &h->lw_gof, N)) || (rc = covis_loop_take(h, &h->lw_vidx, N)) ||
+        (rc = covis_loop_take(h, &h->lw_vcnt, N)) || (rc = covis_loop_take(h, &h->lw_vbase, N)) || (rc = covis_loop_take(h, &h->lw_flags, N * N)) ||
+        (rc = covis_loop_take(h, &h->lw_rep, N)) || (rc = covis_loop_take(h, &h->d_le, 2 * N))) return rc;
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_loop_info(const sgx_covis *h, int64_t *loop_bytes, int32_t *n_loop_edges)
+{
+    if (!h) return SGX_ERR_INVALID;
+    if (loop_bytes) *loop_bytes = h->loop_bytes;
+    if (n_loop_edges) *n_loop_edges = (int32_t)h->loop_edges.size();
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_add_loop_edge(sgx_covis *h, int32_t kf_a, int32_t kf_b)
+{
+    if (!h || kf_a == kf_b) return SGX_ERR_INVALID;
+    const int a = covis_slot_of(h, kf_a), b = covis_slot_of(h, kf_b);
+    if (a < 0 || b < 0) return SGX_ERR_INVALID;
+    for (const auto &e : h->loop_edges) if ((e.first == a && e.second == b) || (e.first == b && e.second == a)) return SGX_OK;      // a set: nothing changes
+    if ((int)h->loop_edges.size() >= h->max_kf) return SGX_ERR_NOMEM;
+    const int rc = covis_loop_ws(h);
+    if (rc != SGX_OK) return rc;
+    const int32_t pair[2] = { a, b };
+    SGX_CHECK_HIP(hipMemcpy(h->d_le + 2 * h->loop_edges.size(), pair, sizeof(pair), hipMemcpyHostToDevice));      // the changed words only
+    h->loop_edges.emplace_back(a, b);
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_get_loop_edges(const sgx_covis *h, int32_t kf_id, int32_t *kf_ids, int32_t *n)
+{
+    if (!h || !n) return SGX_ERR_INVALID;
+    const int s = covis_slot_of(h, kf_id);
+    if (s < 0) return SGX_ERR_INVALID;
+    std::vector<int32_t> v;
+    for (const auto &e : h->loop_edges) if (e.first == s || e.second == s) v.push_back(h->slot[(size_t)(e.first == s ? e.second : e.first)].id);
+    std::sort(v.begin(), v.end());
+    if (!v.empty() && !kf_ids) return SGX_ERR_INVALID;
+    for (size_t j = 0; j < v.size(); j++) kf_ids[j] = v[j];
+    *n = (int32_t)v.size();
+    return SGX_OK;
+}
+
+static SgxCovisLoopArgs covis_loop_args(sgx_covis *h)
+{
+    SgxCovisLoopArgs L{};
+    L.n_le = (int)h->loop_edges.size(); L.le = h->d_le; L.s = h->lw_s; L.qkf = h->lw_qkf; L.ord = h->lw_ord; L.gslot = h->lw_gslot; L.grank = h->lw_grank; L.rowg = h->lw_rowg;
+    L.gof = h->lw_gof; L.vidx = h->lw_vidx; L.vcnt = h->lw_vcnt; L.vbase = h->lw_vbase; L.flags = h->lw_flags;
+    return L;
+}
+
+// the argument block of the UpdateConnections queries of a loop sequence: Q queries whose ids, scalars, count rows and reports live in the loop workspace
+static SgxCovisArgs covis_loop_uc_args(sgx_covis *h, int Q)
+{
+    SgxCovisArgs A = covis_args(h);
+    A.Q = Q; A.q_kf = h->lw_qkf; A.ws_q = h->lw_q; A.ws_cnt = h->lw_flags; A.report = h->lw_rep;
+    return A;
+}
+
+extern "C" int sgx_covis_loop_begin_dev(sgx_covis *h, int32_t cur, int32_t *group_id_dev, int32_t *group_vertex_dev, int pcap, int32_t *point_id_dev, int32_t *point_ref_dev,
+                                        sgx_covis_loop_report *report_dev, void *stream)
+{
+    if (!h || covis_slot_of(h, cur) < 0 || !group_id_dev || !group_vertex_dev || pcap < 0 || (pcap > 0 && (!point_id_dev || !point_ref_dev)) || !report_dev) return SGX_ERR_INVALID;
+    int rc;
+    if ((rc = covis_loop_ws(h)) != SGX_OK || (rc = covis_sync_tables(h)) != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    const int nlive = (int)h->by_id.size();
+    SgxCovisArgs A = covis_args(h);
+    SgxCovisLoopArgs L = covis_loop_args(h);
+    L.cur = cur; L.pcap = pcap; L.group_id = group_id_dev; L.group_vertex = group_vertex_dev; L.point_id = point_id_dev; L.point_ref = point_ref_dev;
+    L.report = (SgxCovisLoopReport *)report_dev;
+    const unsigned G = (unsigned)std::max(1, std::min(h->nslots, (int)COVIS_GRID));
+    SgxCovisArgs U1 = covis_loop_uc_args(h, 1), Un = covis_loop_uc_args(h, nlive);
+    SGX_LAUNCH(k_covis_loop_fill, dim3(1), dim3(256), s, h->lw_qkf, 1, (int)cur, -1);
+    SGX_LAUNCH(k_covis_count, dim3(1), dim3(256), s, U1);                          // mpCurrentKF->UpdateConnections() (:433)
+    SGX_LAUNCH(k_covis_apply, dim3(1), dim3(256), s, U1);
+    SGX_LAUNCH(k_covis_loop_group, dim3(1), dim3(256), s, A, L);
+    SGX_LAUNCH(k_covis_count, dim3((unsigned)nlive), dim3(256), s, Un);            // pKFi->UpdateConnections() of :515 in the order of CorrectedSim3; the queries
+    SGX_LAUNCH(k_covis_apply, dim3(1), dim3(256), s, Un);                          // behind the group name no keyframe
+    SGX_CHECK_HIP(hipMemsetAsync(h->d_stamp, 0x7f, (size_t)h->max_points * 4, s));
+    SGX_LAUNCH(k_covis_lm_stamp, dim3(G, 1), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_lm_count, dim3(G, 1), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_loop_points, dim3(G), dim3(256), s, A, L);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_loop_connections_dev(sgx_covis *h, int32_t cur, int n_group, const int32_t *group_id_dev, int lcap, int32_t *lc_begin_dev, int32_t *lc_j_dev,
+                                              sgx_covis_loop_report *report_dev, void *stream)
+{
+    if (!h || covis_slot_of(h, cur) < 0 || n_group < 1 || n_group > (int)h->by_id.size() || !group_id_dev || lcap < 0 || !lc_begin_dev || (lcap > 0 && !lc_j_dev) || !report_dev)
+        return SGX_ERR_INVALID;
+    int rc;
+    if ((rc = covis_loop_ws(h)) != SGX_OK || (rc = covis_sync_tables(h)) != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    SgxCovisArgs A = covis_args(h), U = covis_loop_uc_args(h, n_group);
+    SgxCovisLoopArgs L = covis_loop_args(h);
+    L.cur = cur; L.n_group = n_group; L.group_id = (int32_t *)group_id_dev; L.lcap = lcap; L.lc_begin = lc_begin_dev; L.lc_j = lc_j_dev; L.report = (SgxCovisLoopReport *)report_dev;
+    SGX_LAUNCH(k_covis_lc_begin, dim3(1), dim3(256), s, A, L);
+    SGX_LAUNCH(k_covis_count, dim3((unsigned)n_group), dim3(256), s, U);
+    SGX_LAUNCH(k_covis_lc_apply, dim3(1), dim3(256), s, U, L);
+    SGX_LAUNCH(k_covis_lc_emit, dim3((unsigned)std::min(n_group, (int)COVIS_GRID)), dim3(256), s, A, L);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_essential_graph_dev(sgx_covis *h, int32_t cur, int32_t loop, int n_group, const int32_t *group_id_dev, int lcap, const int32_t *lc_begin_dev,
+                                             const int32_t *lc_j_dev, int32_t *vertex_id_dev, uint8_t *vertex_fixed_dev, int32_t *vertex_group_dev, int ecap, int32_t *e_i_dev,
+                                             int32_t *e_j_dev, uint8_t *e_kind_dev, sgx_covis_loop_report *report_dev, void *stream)
+{
+    if (!h || covis_slot_of(h, cur) < 0 || covis_slot_of(h, loop) < 0 || n_group < 1 || n_group > (int)h->by_id.size() || !group_id_dev || lcap < 0 || !lc_begin_dev ||
+        (lcap > 0 && !lc_j_dev) || !vertex_id_dev || !vertex_fixed_dev || !vertex_group_dev || ecap < 0 || (ecap > 0 && (!e_i_dev || !e_j_dev || !e_kind_dev)) || !report_dev)
+        return SGX_ERR_INVALID;
+    int rc;
+    if ((rc = covis_loop_ws(h)) != SGX_OK || (rc = covis_sync_tables(h)) != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    SgxCovisArgs A = covis_args(h);
+    SgxCovisLoopArgs L = covis_loop_args(h);
+    L.cur = cur; L.loop = loop; L.n_group = n_group; L.group_id = (int32_t *)group_id_dev; L.lcap = lcap; L.lc_begin = (int32_t *)lc_begin_dev; L.lc_j = (int32_t *)lc_j_dev;
+    L.vertex_id = vertex_id_dev; L.vertex_fixed = vertex_fixed_dev; L.vertex_group = vertex_group_dev; L.ecap = ecap; L.e_i = e_i_dev; L.e_j = e_j_dev; L.e_kind = e_kind_dev;
+    L.report = (SgxCovisLoopReport *)report_dev;
+    const unsigned G = (unsigned)std::max(1, std::min((int)h->by_id.size(), (int)COVIS_GRID));
+    SGX_LAUNCH(k_covis_eg_begin, dim3(1), dim3(256), s, A, L);
+    SGX_LAUNCH(k_covis_eg_vertex<0>, dim3(G), dim3(256), s, A, L);
+    SGX_LAUNCH(k_covis_eg_scan, dim3(1), dim3(256), s, A, L);
+    SGX_LAUNCH(k_covis_eg_vertex<1>, dim3(G), dim3(256), s, A, L);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+// one call from host memory: staged, run on the legacy stream, read back; the return value is the report's status
+extern "C" int sgx_covis_loop_begin(sgx_covis *h, int32_t cur, int32_t *group_id, int32_t *group_vertex, int pcap, int32_t *point_id, int32_t *point_ref, sgx_covis_loop_report *report)
+{
+    if (!h || !group_id || !group_vertex || pcap < 0 || (pcap > 0 && (!point_id || !point_ref))) return SGX_ERR_INVALID;
+    SgxDevMem m; int rc;
+    int32_t *d_g = nullptr, *d_v = nullptr, *d_p = nullptr, *d_r = nullptr; sgx_covis_loop_report *d_rep = nullptr;
+    if ((rc = m.alloc(&d_g, (size_t)h->max_kf)) || (rc = m.alloc(&d_v, (size_t)h->max_kf)) || (rc = m.alloc(&d_p, (size_t)pcap)) || (rc = m.alloc(&d_r, (size_t)pcap)) ||
+        (rc = m.alloc(&d_rep, 1))) return rc;
+    if ((rc = sgx_covis_loop_begin_dev(h, cur, d_g, d_v, pcap, d_p, d_r, d_rep, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    sgx_covis_loop_report R;
+    SGX_CHECK_HIP(hipMemcpy(&R, d_rep, sizeof(R), hipMemcpyDeviceToHost));
+    if (report) *report = R;
+    SGX_CHECK_HIP(hipMemcpy(group_id, d_g, (size_t)R.n_group * 4, hipMemcpyDeviceToHost));
+    SGX_CHECK_HIP(hipMemcpy(group_vertex, d_v, (size_t)R.n_group * 4, hipMemcpyDeviceToHost));
+    const size_t np = (size_t)std::min(R.n_points, pcap);
+    if (np) { SGX_CHECK_HIP(hipMemcpy(point_id, d_p, np * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(point_ref, d_r, np * 4, hipMemcpyDeviceToHost)); }
+    return R.status;                                                               // SGX_OK, or SGX_ERR_NOMEM with the first pcap points written
+}
+
+extern "C" int sgx_covis_loop_connections(sgx_covis *h, int32_t cur, int n_group, const int32_t *group_id, int lcap, int32_t *lc_begin, int32_t *lc_j, sgx_covis_loop_report *report)
+{
+    if (!h || n_group < 1 || n_group > h->max_kf || !group_id || lcap < 0 || !lc_begin || (lcap > 0 && !lc_j)) return SGX_ERR_INVALID;
+    SgxDevMem m; int rc;
+    int32_t *d_g = nullptr, *d_b = nullptr, *d_j = nullptr; sgx_covis_loop_report *d_rep = nullptr;
+    if ((rc = covis_stage(m, &d_g, group_id, (size_t)n_group, (size_t)n_group)) || (rc = m.alloc(&d_b, (size_t)n_group + 1)) || (rc = m.alloc(&d_j, (size_t)lcap)) ||
+        (rc = m.alloc(&d_rep, 1))) return rc;
+    if ((rc = sgx_covis_loop_connections_dev(h, cur, n_group, d_g, lcap, d_b, d_j, d_rep, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    sgx_covis_loop_report R;
+    SGX_CHECK_HIP(hipMemcpy(&R, d_rep, sizeof(R), hipMemcpyDeviceToHost));
+    if (report) *report = R;
+    if (R.status == SGX_ERR_INVALID) return R.status;                              // nothing of the call was written, and the handle is unchanged
+    SGX_CHECK_HIP(hipMemcpy(lc_begin, d_b, ((size_t)n_group + 1) * 4, hipMemcpyDeviceToHost));
+    size_t nw = 0;                                                                 // the rows that fit wholly
+    for (int r = 0; r < n_group && lc_begin[r + 1] <= lcap; r++) nw = (size_t)lc_begin[r + 1];
+    if (nw) SGX_CHECK_HIP(hipMemcpy(lc_j, d_j, nw * 4, hipMemcpyDeviceToHost));
+    return R.status;
+}
+
+extern "C" int sgx_covis_essential_graph(sgx_covis *h, int32_t cur, int32_t loop, int n_group, const int32_t *group_id, const int32_t *lc_begin, const int32_t *lc_j,
+                                         int32_t *vertex_id, uint8_t *vertex_fixed, int32_t *vertex_group, int ecap, int32_t *e_i, int32_t *e_j, uint8_t *e_kind,
+                                         sgx_covis_loop_report *report)
+{
+    if (!h || n_group < 1 || n_group > h->max_kf || !group_id || !lc_begin || lc_begin[n_group] < 0 || (lc_begin[n_group] > 0 && !lc_j) || !vertex_id || !vertex_fixed ||
+        !vertex_group || ecap < 0 || (ecap > 0 && (!e_i || !e_j || !e_kind))) return SGX_ERR_INVALID;
+    SgxDevMem m; int rc;
+    const int lcap = lc_begin[n_group];
+    int32_t *d_g = nullptr, *d_b = nullptr, *d_j = nullptr, *d_vi = nullptr, *d_vg = nullptr, *d_ei = nullptr, *d_ej = nullptr; uint8_t *d_vf = nullptr, *d_ek = nullptr;
+    sgx_covis_loop_report *d_rep = nullptr;
+    if ((rc = covis_stage(m, &d_g, group_id, (size_t)n_group, (size_t)n_group)) || (rc = covis_stage(m, &d_b, lc_begin, (size_t)n_group + 1, (size_t)n_group + 1)) ||
+        (rc = covis_stage(m, &d_j, lc_j, (size_t)lcap, (size_t)lcap)) || (rc = m.alloc(&d_vi, (size_t)h->max_kf)) || (rc = m.alloc(&d_vf, (size_t)h->max_kf)) ||
+        (rc = m.alloc(&d_vg, (size_t)h->max_kf)) || (rc = m.alloc(&d_ei, (size_t)ecap)) || (rc = m.alloc(&d_ej, (size_t)ecap)) || (rc = m.alloc(&d_ek, (size_t)ecap)) ||
+        (rc = m.alloc(&d_rep, 1))) return rc;
+    if ((rc = sgx_covis_essential_graph_dev(h, cur, loop, n_group, d_g, lcap, d_b, d_j, d_vi, d_vf, d_vg, ecap, d_ei, d_ej, d_ek, d_rep, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    sgx_covis_loop_report R;
+    SGX_CHECK_HIP(hipMemcpy(&R, d_rep, sizeof(R), hipMemcpyDeviceToHost));
+    if (report) *report = R;
+    if (R.status == SGX_ERR_INVALID) return R.status;                              // nothing of the call was written
+    const size_t nv = (size_t)R.n_vertices, ne = (size_t)std::min(R.n_edges, ecap);
+    if (nv) { SGX_CHECK_HIP(hipMemcpy(vertex_id, d_vi, nv * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(vertex_fixed, d_vf, nv, hipMemcpyDeviceToHost));
+              SGX_CHECK_HIP(hipMemcpy(vertex_group, d_vg, nv * 4, hipMemcpyDeviceToHost)); }
+    if (ne) { SGX_CHECK_HIP(hipMemcpy(e_i, d_ei, ne * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(e_j, d_ej, ne * 4, hipMemcpyDeviceToHost));
+              SGX_CHECK_HIP(hipMemcpy(e_kind, d_ek, ne, hipMemcpyDeviceToHost)); }
+    return R.status;                                                               // SGX_OK, or SGX_ERR_NOMEM with the first ecap edges written
 }

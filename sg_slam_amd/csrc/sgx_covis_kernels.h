@@ -156,10 +156,10 @@ SGX_KERNEL(256) k_covis_count(SgxCovisArgs A)
 
 // What UpdateConnections writes (:335-379), for the queries of the batch in their order by ONE workgroup: query q's AddConnection into a neighbour and query q + 1's
 // overwrite of that neighbour's whole map touch the same words, and the later one must win.  Within a query the lanes take a slot each.
-SGX_KERNEL(256) k_covis_apply(SgxCovisArgs A)
+SGX_DEV void sgx_covis_apply_one(const SgxCovisArgs &A, int q)
 {
     SGX_LDS int s_nord, s_front;
-    for (int q = 0; q < A.Q; q++) {
+    {
         const int *w = A.ws_q + q * CQ_FIELDS;
         const int s = w[CQ_SLOT], n = w[CQ_N], nmax = w[CQ_MAX];
         const int *cnt = A.ws_cnt + (size_t)q * A.max_kf;
@@ -172,7 +172,7 @@ SGX_KERNEL(256) k_covis_apply(SgxCovisArgs A)
                 A.report[q] = R;
             }
             SGX_THREADS_END
-            continue;
+            return;
         }
         const bool any = nmax >= SGX_COVIS_TH;
         const int tmax = sgx_covis_lookup(A, w[CQ_ARG]);
@@ -208,6 +208,11 @@ SGX_KERNEL(256) k_covis_apply(SgxCovisArgs A)
         SGX_THREADS_END
         SGX_SYNC();
     }
+}
+
+SGX_KERNEL(256) k_covis_apply(SgxCovisArgs A)
+{
+    for (int q = 0; q < A.Q; q++) sgx_covis_apply_one(A, q);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------ ordered lists, culling

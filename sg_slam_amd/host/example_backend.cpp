@@ -141,6 +141,15 @@ int main(int argc, char **argv)
         printf("\nculled:"); for (int32_t k : G.KeyFrameCulling(cur)) printf(" %d", k);
         printf("\nparent of %d: %d, children:", cur, G.GetParent(cur)); for (int32_t c : G.GetChilds(cur)) printf(" %d", c);
         printf("\n");
+        // the essential graph of a loop between cur and its parent with no new connection yet (a query: the handle does not change): the spanning tree and the
+        // covisibility edges of weight 100 and more
+        {
+            const int32_t loop = G.GetParent(cur) >= 0 ? G.GetParent(cur) : cur;
+            const sgx::CovisibilityGraph::EssentialGraph e = G.essential_graph(cur, loop, { cur }, { 0, 0 }, {});
+            printf("eg vertices %d fixed", (int)e.vertex_id.size()); for (size_t j = 0; j < e.vertex_id.size(); j++) if (e.vertex_fixed[j]) printf(" %d", e.vertex_id[j]);
+            printf(" edges"); for (size_t j = 0; j < e.e_i.size(); j++) printf(" %d:%d:%d", e.vertex_id[(size_t)e.e_i[j]], e.vertex_id[(size_t)e.e_j[j]], e.e_kind[j]);
+            printf("\n");
+        }
         // the graph of LocalBundleAdjustment(cur) after the culling, every third edge erased as vToErase, and the graph again
         for (int round = 0; round < 2; round++) {
             const sgx::CovisibilityGraph::BaGraph g = G.ba_graph(cur);
@@ -153,6 +162,28 @@ int main(int argc, char **argv)
             for (size_t j = 0; j < erase.size(); j += 3) erase[j] = 1;
             G.apply_ba_erase(g, erase);
         }
+        return 0;
+    }
+    if (argc >= 2 && !strcmp(argv[1], "loop")) {                    // LoopClosing::CorrectLoop on a map of three keyframes: 1 shares 16 points with 2 and 14 with 3; the loop is 1 - 3
+        sgx::CovisibilityGraph G(8, 32, 64, 256, 2, false, 40.0f);
+        const std::vector<int32_t> oct(32, 0); const std::vector<float> ur(32, -1.f), dp(32, 1.f);
+        for (int32_t k : { 1, 2, 3 }) G.AddKeyFrame(k, oct, ur, dp);
+        auto iota = [](int n, int from) { std::vector<int32_t> v((size_t)n); for (int i = 0; i < n; i++) v[(size_t)i] = from + i; return v; };
+        G.SetObservations(1, iota(30, 0), iota(30, 0)); G.SetObservations(2, iota(16, 0), iota(16, 0)); G.SetObservations(3, iota(14, 0), iota(14, 16));
+        std::vector<float> T(4 * 12, 0.f), xw(3 * 64);
+        for (int k = 1; k <= 3; k++) { T[12 * (size_t)k] = T[12 * (size_t)k + 5] = T[12 * (size_t)k + 10] = 1.f; T[12 * (size_t)k + 3] = -0.5f * k; T[12 * (size_t)k + 11] = 0.1f * k; }
+        for (int i = 0; i < 64; i++) { xw[3 * (size_t)i] = 0.1f * i; xw[3 * (size_t)i + 1] = 1.f - 0.05f * i; xw[3 * (size_t)i + 2] = 4.f; }
+        const sgx::Optimizer::Sim3 Scw{{0, 0, 0, 1, -0.45, 0.02, 0.1, 1}};
+        const sgx::Optimizer::LoopResult r = sgx::Optimizer::CorrectLoop(G, 1, 3, Scw, [&](int32_t id, float *o) { memcpy(o, &T[12 * (size_t)id], 48); },
+                                                                        [&](int32_t id, const float *o) { memcpy(&T[12 * (size_t)id], o, 48); }, xw,
+                                                                        [](const sgx::CovisibilityGraph::LoopGroup &, const std::vector<sgx::Optimizer::Sim3> &) {});
+        printf("group"); for (int32_t k : r.group.group_id) printf(" %d", k);
+        printf(" lc"); for (int32_t k : r.connections.lc_begin) printf(" %d", k); printf(" /"); for (int32_t k : r.connections.lc_j) printf(" %d", k);
+        printf(" edges"); for (size_t j = 0; j < r.graph.e_i.size(); j++) printf(" %d:%d:%d", r.graph.e_i[j], r.graph.e_j[j], r.graph.e_kind[j]);
+        printf(" loop edges of 1:"); for (int32_t k : G.GetLoopEdges(1)) printf(" %d", k);
+        printf("\nposes"); for (int k = 1; k <= 3; k++) for (int i = 0; i < 12; i++) printf(" %.9g", T[12 * (size_t)k + i]);
+        printf("\npoints"); for (int i = 0; i < 3 * 30; i++) printf(" %.9g", xw[(size_t)i]);
+        printf("\n");
         return 0;
     }
     if (argc >= 11 && !strcmp(argv[1], "stereo")) {                 // the stereo Frame constructor up to ComputeStereoMatches (Frame.cc:70-99): left.raw right.raw width height nfeatures scale nlevels fx bf
@@ -168,6 +199,6 @@ int main(int argc, char **argv)
         return 0;
     }
     fprintf(stderr, "usage: %s ba graph.bin | det model.param model.bin frame.raw | flow cur.raw prev.raw pts.bin | sim3 pairs.bin | voc voc.txt desc.bin | s3solver pairs.bin |"
-                    " stereo left.raw right.raw width height nfeatures scale nlevels fx bf | covis map.bin\n", argv[0]);
+                    " stereo left.raw right.raw width height nfeatures scale nlevels fx bf | covis map.bin | loop\n", argv[0]);
     return 2;
 }

@@ -578,6 +578,51 @@ public:
             for (size_t j = 0; j < erase.size(); j++)
                 if (erase[j] && ((g.edge_attr[j] & SGX_COVIS_ATTR_RIGHT) != 0) == (stereo != 0)) EraseMapPointMatch(g.pose_id[(size_t)g.edge_pose[j]], g.edge_kp[j]);
     }
+    // Loop closing (LoopClosing::CorrectLoop, LoopClosing.cc:432-573, and the graph of Optimizer::OptimizeEssentialGraph, Optimizer.cc:797-983): mspLoopEdges, the group
+    // with the point marks, LoopConnections after the caller's fusion, and the vertices and edges of the essential graph.  Two calls where a need is not known.
+    void AddLoopEdge(int32_t a, int32_t b) { check(sgx_covis_add_loop_edge(h_, a, b), "sgx_covis_add_loop_edge"); }
+    std::vector<int32_t> GetLoopEdges(int32_t mnId)
+    {
+        std::vector<int32_t> v((size_t)maxkf_); int32_t n = 0;
+        check(sgx_covis_get_loop_edges(h_, mnId, v.data(), &n), "sgx_covis_get_loop_edges"); v.resize((size_t)n);
+        return v;
+    }
+    struct LoopGroup { std::vector<int32_t> group_id, group_vertex, point_id, point_ref; sgx_covis_loop_report report{}; };
+    LoopGroup loop_begin(int32_t cur)
+    {
+        LoopGroup g; g.group_id.resize((size_t)maxkf_); g.group_vertex.resize((size_t)maxkf_);
+        int rc = sgx_covis_loop_begin(h_, cur, g.group_id.data(), g.group_vertex.data(), 0, nullptr, nullptr, &g.report);
+        if (rc != SGX_OK && rc != SGX_ERR_NOMEM) check(rc, "sgx_covis_loop_begin");
+        const size_t np = (size_t)g.report.n_points;
+        g.point_id.resize(np); g.point_ref.resize(np);
+        if (rc != SGX_OK) check(sgx_covis_loop_begin(h_, cur, g.group_id.data(), g.group_vertex.data(), (int)np, g.point_id.data(), g.point_ref.data(), &g.report), "sgx_covis_loop_begin");
+        g.group_id.resize((size_t)g.report.n_group); g.group_vertex.resize((size_t)g.report.n_group);
+        return g;
+    }
+    struct LoopConnections { std::vector<int32_t> lc_begin, lc_j; sgx_covis_loop_report report{}; };
+    LoopConnections loop_connections(int32_t cur, const std::vector<int32_t> &group_id)      // one call: a second one would find the lists the first one left
+    {
+        LoopConnections c; c.lc_begin.resize(group_id.size() + 1); c.lc_j.resize(group_id.size() * (size_t)maxkf_);
+        check(sgx_covis_loop_connections(h_, cur, (int)group_id.size(), group_id.data(), (int)c.lc_j.size(), c.lc_begin.data(), c.lc_j.data(), &c.report), "sgx_covis_loop_connections");
+        c.lc_j.resize((size_t)c.report.n_connections);
+        return c;
+    }
+    struct EssentialGraph { std::vector<int32_t> vertex_id, vertex_group, e_i, e_j; std::vector<uint8_t> vertex_fixed, e_kind; sgx_covis_loop_report report{}; };
+    EssentialGraph essential_graph(int32_t cur, int32_t loop, const std::vector<int32_t> &group_id, const std::vector<int32_t> &lc_begin, const std::vector<int32_t> &lc_j)
+    {
+        EssentialGraph g; g.vertex_id.resize((size_t)maxkf_); g.vertex_group.resize((size_t)maxkf_); g.vertex_fixed.resize((size_t)maxkf_);
+        if (lc_begin.size() != group_id.size() + 1 || (size_t)lc_begin.back() != lc_j.size()) check(SGX_ERR_INVALID, "essential_graph");
+        int rc = sgx_covis_essential_graph(h_, cur, loop, (int)group_id.size(), group_id.data(), lc_begin.data(), lc_j.data(), g.vertex_id.data(), g.vertex_fixed.data(),
+                                           g.vertex_group.data(), 0, nullptr, nullptr, nullptr, &g.report);
+        if (rc != SGX_OK && rc != SGX_ERR_NOMEM) check(rc, "sgx_covis_essential_graph");
+        const size_t ne = (size_t)g.report.n_edges;
+        g.e_i.resize(ne); g.e_j.resize(ne); g.e_kind.resize(ne);
+        if (rc != SGX_OK)
+            check(sgx_covis_essential_graph(h_, cur, loop, (int)group_id.size(), group_id.data(), lc_begin.data(), lc_j.data(), g.vertex_id.data(), g.vertex_fixed.data(),
+                                            g.vertex_group.data(), (int)ne, g.e_i.data(), g.e_j.data(), g.e_kind.data(), &g.report), "sgx_covis_essential_graph");
+        g.vertex_id.resize((size_t)g.report.n_vertices); g.vertex_group.resize((size_t)g.report.n_vertices); g.vertex_fixed.resize((size_t)g.report.n_vertices);
+        return g;
+    }
     sgx_covis *handle() const { return h_; }
 private:
     template <class F> std::vector<std::pair<int32_t, int32_t>> pairs(F fn, int32_t mnId, const char *what)
@@ -681,6 +726,81 @@ public:
         check(sgx_optimize_essential_graph((int)g.vScw.size(), g.vScw.empty() ? nullptr : g.vScw[0].v, g.fixed.data(), (int)g.e_i.size(), g.e_i.data(), g.e_j.data(),
                                            g.e_meas.empty() ? nullptr : g.e_meas[0].v, bFixScale ? 1 : 0, iterations, out[0].v, stats), "sgx_optimize_essential_graph");
         out.resize(g.vScw.size()); g.vScw = out;
+    }
+    // The Sim3 glue of loop closing (include/sgx.h).  A pose is 12 floats, the rows of [R | t].
+    // LoopClosing::CorrectLoop :440-469, :503-512: the poses of the group in group order (the current keyframe last) and its Scw
+    struct LoopSim3 { std::vector<Sim3> NonCorrectedSim3, CorrectedSim3; std::vector<float> correctedTiw; };
+    static LoopSim3 PropagateLoopSim3(const std::vector<float> &Tcw_group, const Sim3 &Scw)
+    {
+        const size_t n = Tcw_group.size() / 12; LoopSim3 r; r.NonCorrectedSim3.resize(n ? n : 1); r.CorrectedSim3.resize(n ? n : 1); r.correctedTiw.resize(12 * (n ? n : 1));
+        check(sgx_loop_propagate_sim3((int)n, Tcw_group.data(), Scw.v, r.NonCorrectedSim3[0].v, r.CorrectedSim3[0].v, r.correctedTiw.data()), "sgx_loop_propagate_sim3");
+        return r;
+    }
+    // Optimizer.cc:818-832, :857-867, :889-972: vScw and the measurements for the graph of CovisibilityGraph::essential_graph; Tcw_vertices: the poses in vertex order
+    static PoseGraph FlattenEssentialGraph(const CovisibilityGraph::EssentialGraph &e, const std::vector<float> &Tcw_vertices, const LoopSim3 &l)
+    {
+        PoseGraph g; const size_t nv = e.vertex_id.size(), ne = e.e_i.size();
+        if (Tcw_vertices.size() != 12 * nv) check(SGX_ERR_INVALID, "FlattenEssentialGraph");
+        g.vScw.resize(nv ? nv : 1); g.e_meas.resize(ne ? ne : 1); g.fixed = e.vertex_fixed; g.e_i = e.e_i; g.e_j = e.e_j;
+        check(sgx_eg_flatten((int)nv, e.vertex_group.data(), Tcw_vertices.data(), (int)l.CorrectedSim3.size(), l.CorrectedSim3[0].v, l.NonCorrectedSim3[0].v, (int)ne, e.e_i.data(),
+                             e.e_j.data(), e.e_kind.data(), g.vScw[0].v, g.e_meas[0].v), "sgx_eg_flatten");
+        g.vScw.resize(nv); g.e_meas.resize(ne);
+        return g;
+    }
+    // Optimizer.cc:991-1010: the poses and vCorrectedSwc of the optimised vertices
+    static void RecoverEssentialGraph(const std::vector<Sim3> &S, std::vector<float> &Tcw, std::vector<Sim3> &vCorrectedSwc)
+    {
+        const size_t n = S.size(); Tcw.assign(12 * (n ? n : 1), 0.f); vCorrectedSwc.resize(n ? n : 1);
+        check(sgx_eg_recover((int)n, n ? S[0].v : nullptr, Tcw.data(), vCorrectedSwc[0].v), "sgx_eg_recover");
+        Tcw.resize(12 * n); vCorrectedSwc.resize(n);
+    }
+    static void CorrectMapPoints(std::vector<float> &xw, const std::vector<int32_t> &ref, const std::vector<Sim3> &Srw, const std::vector<Sim3> &correctedSwr)
+    {
+        std::vector<float> out(xw.size() ? xw.size() : 3);
+        check(sgx_correct_map_points((int)ref.size(), xw.data(), ref.data(), (int)Srw.size(), Srw.empty() ? nullptr : Srw[0].v, correctedSwr.empty() ? nullptr : correctedSwr[0].v, out.data()),
+              "sgx_correct_map_points");
+        out.resize(xw.size()); xw = out;
+    }
+    // LoopClosing::CorrectLoop (LoopClosing.cc:432-573) with OptimizeEssentialGraph, in the reference's order.  pose(mnId, float[12]) reads a keyframe's Tcw, set_pose
+    // writes one back; xw: the world positions by point id, corrected in place (the group's points; the points outside it by their reference keyframe are the caller's,
+    // with the S_in / vCorrectedSwc returned); fuse(group, CorrectedSim3): the caller's fusion through covis.Replace / SetObservations.
+    struct LoopResult { CovisibilityGraph::LoopGroup group; CovisibilityGraph::LoopConnections connections; CovisibilityGraph::EssentialGraph graph; LoopSim3 sim3; PoseGraph problem;
+                        std::vector<Sim3> S_in, vCorrectedSwc; double stats[3] = { 0, 0, 0 }; };
+    template <class GetPose, class SetPose, class Fuse>
+    static LoopResult CorrectLoop(CovisibilityGraph &covis, int32_t cur, int32_t loop, const Sim3 &Scw, GetPose pose, SetPose set_pose, std::vector<float> &xw, Fuse fuse, bool bFixScale = true)
+    {
+        LoopResult r; r.group = covis.loop_begin(cur);
+        const size_t ng = r.group.group_id.size();
+        std::vector<float> Tg(12 * ng);
+        for (size_t k = 0; k < ng; k++) pose(r.group.group_id[k], &Tg[12 * k]);
+        r.sim3 = PropagateLoopSim3(Tg, Scw);
+        std::vector<float> unused; std::vector<Sim3> cSwi; RecoverEssentialGraph(r.sim3.CorrectedSim3, unused, cSwi);
+        auto correct = [&](const std::vector<int32_t> &ref, const std::vector<Sim3> &a, const std::vector<Sim3> &c) {
+            std::vector<float> p(3 * r.group.point_id.size());
+            for (size_t i = 0; i < r.group.point_id.size(); i++) memcpy(&p[3 * i], &xw[3 * (size_t)r.group.point_id[i]], 12);
+            CorrectMapPoints(p, ref, a, c);
+            for (size_t i = 0; i < r.group.point_id.size(); i++) memcpy(&xw[3 * (size_t)r.group.point_id[i]], &p[3 * i], 12);
+        };
+        if (!r.group.point_id.empty()) correct(r.group.point_ref, r.sim3.NonCorrectedSim3, cSwi);
+        for (size_t k = 0; k < ng; k++) set_pose(r.group.group_id[k], &r.sim3.correctedTiw[12 * k]);
+        fuse(r.group, r.sim3.CorrectedSim3);
+        r.connections = covis.loop_connections(cur, r.group.group_id);
+        r.graph = covis.essential_graph(cur, loop, r.group.group_id, r.connections.lc_begin, r.connections.lc_j);
+        const size_t nv = r.graph.vertex_id.size();
+        std::vector<float> Tv(12 * nv);
+        for (size_t v = 0; v < nv; v++) pose(r.graph.vertex_id[v], &Tv[12 * v]);
+        r.problem = FlattenEssentialGraph(r.graph, Tv, r.sim3);
+        r.S_in = r.problem.vScw;
+        OptimizeEssentialGraph(r.problem, bFixScale, 20, r.stats);
+        std::vector<float> Tn; RecoverEssentialGraph(r.problem.vScw, Tn, r.vCorrectedSwc);
+        for (size_t v = 0; v < nv; v++) set_pose(r.graph.vertex_id[v], &Tn[12 * v]);
+        if (!r.group.point_id.empty()) {
+            std::vector<int32_t> ref(r.group.point_ref.size());
+            for (size_t i = 0; i < ref.size(); i++) ref[i] = r.group.group_vertex[(size_t)r.group.point_ref[i]];
+            correct(ref, r.S_in, r.vCorrectedSwc);
+        }
+        if (cur != loop) covis.AddLoopEdge(loop, cur);
+        return r;
     }
 };
 

@@ -123,3 +123,41 @@ class Optimizer:
         out = np.zeros_like(xw)
         lib.check(lib.dll.sgx_correct_map_points(len(xw), _vp(xw), _vp(ref), len(a), _vp(a), _vp(c), _vp(out)), 'sgx_correct_map_points')
         return out
+
+    # ---- the Sim3 glue of loop closing (see include/sgx.h): a Sim3 is (qx, qy, qz, qw, tx, ty, tz, s), a pose the rows of [R | t]
+    @staticmethod
+    def _poses(T):
+        T = np.asarray(T, 'f4')
+        return np.ascontiguousarray(T.reshape(-1, T.shape[-2], 4)[:, :3, :], 'f4')
+
+    @staticmethod
+    def PropagateLoopSim3(Tcw_group, Scw, lib=None):
+        """LoopClosing::CorrectLoop :440-469, :503-512: the poses of the group in group order (the current keyframe last) and its Scw ->
+        (NonCorrectedSim3[ng, 8], CorrectedSim3[ng, 8], the corrected poses [ng, 3, 4] float32)"""
+        lib = lib if lib is not None else load()
+        T = Optimizer._poses(Tcw_group); S = np.ascontiguousarray(Scw, 'f8').reshape(8); n = len(T)
+        non = np.zeros((n, 8)); cor = np.zeros((n, 8)); out = np.zeros((n, 3, 4), 'f4')
+        lib.check(lib.dll.sgx_loop_propagate_sim3(n, _vp(T), _vp(S), _vp(non), _vp(cor), _vp(out)), 'sgx_loop_propagate_sim3')
+        return non, cor, out
+
+    @staticmethod
+    def FlattenEssentialGraph(graph, Tcw_vertices, corrected, noncorrected, lib=None):
+        """Optimizer.cc:818-832, :857-867, :889-972 for a graph of CovisibilityGraph.essential_graph and the poses in vertex order (a group vertex's is not read):
+        (S_in[nv, 8], e_meas[ne, 8]), what OptimizeEssentialGraph takes with graph['vertex_fixed'], graph['e_i'], graph['e_j']"""
+        lib = lib if lib is not None else load()
+        vg = np.ascontiguousarray(graph['vertex_group'], 'i4'); T = Optimizer._poses(Tcw_vertices); nv = len(vg)
+        assert len(T) == nv
+        cor = np.ascontiguousarray(corrected, 'f8').reshape(-1, 8); non = np.ascontiguousarray(noncorrected, 'f8').reshape(-1, 8)
+        ei = np.ascontiguousarray(graph['e_i'], 'i4'); ej = np.ascontiguousarray(graph['e_j'], 'i4'); ek = np.ascontiguousarray(graph['e_kind'], 'u1')
+        S = np.zeros((nv, 8)); m = np.zeros((len(ei), 8))
+        lib.check(lib.dll.sgx_eg_flatten(nv, _vp(vg), _vp(T), len(cor), _vp(cor), _vp(non), len(ei), _vp(ei), _vp(ej), _vp(ek), _vp(S), _vp(m)), 'sgx_eg_flatten')
+        return S, m
+
+    @staticmethod
+    def RecoverEssentialGraph(S_out, lib=None):
+        """Optimizer.cc:991-1010: (Tcw[nv, 3, 4] float32, vCorrectedSwc[nv, 8])"""
+        lib = lib if lib is not None else load()
+        S = np.ascontiguousarray(S_out, 'f8').reshape(-1, 8); n = len(S)
+        T = np.zeros((n, 3, 4), 'f4'); inv = np.zeros((n, 8))
+        lib.check(lib.dll.sgx_eg_recover(n, _vp(S), _vp(T), _vp(inv)), 'sgx_eg_recover')
+        return T, inv
