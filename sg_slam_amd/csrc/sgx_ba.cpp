@@ -24,6 +24,8 @@
 #include <chrono>
 #include <mutex>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "sgx_ba_plan.h"
 #include "sgx_lm.h"
@@ -33,7 +35,7 @@ namespace {
 // call.  With it a grow-only pinned staging buffer of the packed host->device inputs: no 17 MB zero-fill + pageable copy per call at 2 000 keyframes.
 // layout(f) runs the list of arrays f twice: the first pass sizes (no pointers handed out), the second assigns and packs the inputs, which then go up with one copy.
 struct Arena {
-    char *base = nullptr, *stage = nullptr; size_t cap = 0, stage_cap = 0, off = 0, in_bytes = 0; int device = -1; bool sizing = false;
+    char *base = nullptr, *stage = nullptr; size_t cap = 0, stage_cap = 0, off = 0, in_bytes = 0; int device = -1; bool sizing = false, taking_input = false;      // taking_input: take() on behalf of input()
     int reserve(size_t bytes) {
 #ifndef SGX_EMU
         int cur = 0;
@@ -63,22 +65,39 @@ struct Arena {
 #endif
         stage_cap = want; return SGX_OK;
     }
-    template <class T> void take(T **p, size_t n) { off = (off + 255) & ~(size_t)255; if (!sizing) *p = (T *)(base + off); off += (n ? n : 1) * sizeof(T); }
+    template <class T> void take(T **p, size_t n)
+    {
+        off = (off + 255) & ~(size_t)255; if (!sizing) *p = (T *)(base + off);
+#ifdef SGX_DEBUG_TAPS
+        if (!sizing && !taking_input && std::is_floating_point<T>::value) scratch_fp.push_back({ off, (n ? n : 1) * sizeof(T) });
+#endif
+        off += (n ? n : 1) * sizeof(T);
+    }
     // one allocation handed out as adjacent parts: *p0 is the whole, *p1 starts n0 elements in, *p2 n1 further
     template <class T> void take_parts(T **p0, size_t n0, T **p1, size_t n1, T **p2 = nullptr, size_t n2 = 0) { take(p0, n0 + n1 + n2); if (!sizing) { *p1 = *p0 + n0; if (p2) *p2 = *p1 + n1; } }
     // a host->device input (they come first): taken like any array and packed into the staging buffer from src (nullptr: zeros); the alignment gaps between them are never read
     template <class T> void input(T **p, const T *src, size_t n) {
-        take(p, n); in_bytes = off;
+        taking_input = true; take(p, n); taking_input = false; in_bytes = off;
         if (!sizing && n) { char *dst = stage + ((const char *)*p - base); if (src) memcpy(dst, src, n * sizeof(T)); else memset(dst, 0, n * sizeof(T)); }
     }
     template <class F> int layout(F &&arrays) {
         sizing = true; off = in_bytes = 0; arrays(*this);
         int rc = reserve(off); if (rc != SGX_OK) return rc;
         if ((rc = stage_reserve(in_bytes)) != SGX_OK) return rc;
-        sizing = false; off = in_bytes = 0; arrays(*this);
+        sizing = false; off = in_bytes = 0;
+#ifdef SGX_DEBUG_TAPS
+        scratch_fp.clear();
+#endif
+        arrays(*this);
         SGX_CHECK_HIP(hipMemcpy(base, stage, in_bytes, hipMemcpyHostToDevice));
         return SGX_OK;
     }
+#ifdef SGX_DEBUG_TAPS
+    // (test tap, sgx_ba_debug_set_init(3)) the double / float arrays of the last layout that are no inputs, as (offset, bytes), and their fill with 0xFF bytes: every value
+    // a NaN, where the product build has whatever the previous call left.  The integer arrays keep their content: a stale index must not become an address.
+    std::vector<std::pair<size_t, size_t>> scratch_fp;
+    int poison_scratch() { for (const auto &r : scratch_fp) SGX_CHECK_HIP(hipMemsetAsync(base + r.first, 0xFF, r.second, 0)); return SGX_OK; }
+#endif
 };
 static Arena g_arena;
 static std::mutex g_arena_mutex;      // one arena per process: calls from several threads (the reference has one LocalMapping thread, plus GlobalBundleAdjustment from LoopClosing) take turns
@@ -235,7 +254,7 @@ struct BA {
         if (NP > 0) {
             const int g = (int)(((size_t)NP * NP + SGX_BA_THREADS - 1) / SGX_BA_THREADS);
             if (C.env_rstart && sw.init_mode != 1) {             // envelope solver: only the tiles it reads
-                if (sw.init_mode == 2) SGX_CHECK_HIP(hipMemsetAsync(C.S, 0xFF, sizeof(double) * (size_t)NP * NP, 0));      // (test tap) all ones = NaN everywhere first
+                if (sw.init_mode >= 2) SGX_CHECK_HIP(hipMemsetAsync(C.S, 0xFF, sizeof(double) * (size_t)NP * NP, 0));      // (test tap) all ones = NaN everywhere first
                 const int nt = (NP + SGX_NB - 1) / SGX_NB;
                 SGX_LAUNCH(k_ba_schur_init_env, dim3((unsigned)(nt + env_nrows)), dim3(SGX_BA_THREADS), (sgx_stream_t)0, nf, Hpp, lambda, C.S, C.coef, nt, C.env_rstart, C.env_rows);
             } else
@@ -408,6 +427,9 @@ static int upload(BA &B, const BaIndex &ix, const EnvPlan &plan, const sgx_ba_pr
         A.take(&B.jobs, ix.jobs_cap); A.take(&B.blk_start, ix.jobs_cap + 1); A.take(&C.Linv, (size_t)((ix.NP + SGX_NB - 1) / SGX_NB) * SGX_NB * SGX_NB);
     });
     if (rc != SGX_OK) return rc;
+#ifdef SGX_DEBUG_TAPS
+    if (B.sw.init_mode == 3) { const int prc = g_arena.poison_scratch(); if (prc != SGX_OK) return prc; }      // before the clears below and the first kernel
+#endif
     C.ok = (int *)B.trial_out;
     if (plan.empty()) { C.env_rstart = nullptr; C.env_rows = nullptr; }
     B.env_nrows = plan.nrows(); C.env_nA = plan.nA; C.env_nB = plan.nB;
@@ -449,7 +471,7 @@ static int download(BA &B, const BaIndex &ix, const sgx_ba_problem &P, int mode,
 }  // namespace
 
 SGX_TAP int sgx_ba_debug_last_plan(int32_t plan[4]) { if (!plan) return SGX_ERR_INVALID; for (int i = 0; i < 4; i++) plan[i] = g_ba_last_plan[i]; return SGX_OK; }
-SGX_TAP int sgx_ba_debug_set_init(int mode) { g_ba_init_mode = mode < 0 ? 0 : (mode > 2 ? 2 : mode); return SGX_OK; }
+SGX_TAP int sgx_ba_debug_set_init(int mode) { g_ba_init_mode = mode < 0 ? 0 : (mode > 3 ? 3 : mode); return SGX_OK; }
 SGX_TAP int sgx_ba_debug_set_jobs(int host) { g_ba_jobs_host = host ? 1 : 0; return SGX_OK; }
 SGX_TAP int sgx_ba_debug_set_solver(int mode) { g_ba_solver = mode < 0 ? -1 : (mode > 2 ? 2 : mode); return SGX_OK; }
 

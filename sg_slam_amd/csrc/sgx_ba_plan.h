@@ -7,7 +7,7 @@
 // Every switch of the bundle adjustments and of the solver they share with the essential-graph optimisation, filled once at the top of a C entry (ba_switches(), sgx_ba.cpp)
 // from the test taps of include/sgx_debug.h and the environment.  The product build has neither (sgx_rt.h): every member keeps its default there.
 struct BaSwitches {
-    int init_mode = 0;      // sgx_ba_debug_set_init: 0 = envelope solver: only its tiles are initialised, 1 = the whole matrix, 2 = the whole matrix NaN, then the tiles
+    int init_mode = 0;      // sgx_ba_debug_set_init: 0 = envelope solver: only its tiles are initialised, 1 = the whole matrix, 2 = the whole matrix NaN, then the tiles, 3 = 2 + every double / float scratch array of the arena NaN before the first kernel
     int jobs_host = 0;      // sgx_ba_debug_set_jobs: 1 = build the Schur job list on the host (the emulator's only path; A/B arm of the device builder)
     int solver = 0;         // sgx_ba_debug_set_solver, else SGX_BA_SOLVER = dense | env | auto: 0 auto, 1 dense blocked Cholesky, 2 envelope solver
     int twist = 1;          // SGX_BA_TWIST: 0 = never the two-branch ordering

@@ -107,13 +107,14 @@ def test_device_job_list_equals_host_built_gpu(gpulib_taps, oracle, case):
 
 def test_envelope_tiles_only_initialisation_gpu(gpulib_taps):
     """Round 6: with the envelope solver only the tiles of its column steps are initialised per LM trial (k_ba_schur_init_env: 16 MB instead of the 1.15 GB dense matrix at 2 000
-    keyframes).  Same bits as the full initialisation — also when the whole matrix is NaN before the tiles are written (mode 2): nothing outside the tiles is ever read."""
+    keyframes).  Same bits as the full initialisation — also when the whole matrix is NaN before the tiles are written (mode 2): nothing outside the tiles is ever read —
+    and when every double / float scratch array of the arena is NaN before the first kernel as well (mode 3; the smaller shapes and the global entry: test_ba_solver_gpu.py)."""
     from scenes import make_big_ba_problem
     lib = gpulib_taps
     prob, _, _ = make_big_ba_problem(600, 15000)
     out = {}
     try:
-        for mode in (1, 0, 2):
+        for mode in (1, 0, 2, 3):
             lib.tap('sgx_ba_debug_set_init')(mode)
             p = {k: (v.copy() if hasattr(v, 'copy') else v) for k, v in prob.items()}
             er, st = Optimizer.LocalBundleAdjustment(p, CAM, lib=lib)
@@ -123,4 +124,4 @@ def test_envelope_tiles_only_initialisation_gpu(gpulib_taps):
     finally:
         lib.tap('sgx_ba_debug_set_init')(0)
     assert np.isfinite(out[1][4]).all()
-    assert out[0] == out[1] and out[2] == out[1]
+    assert out[0] == out[1] and out[2] == out[1] and out[3] == out[1]
