@@ -125,7 +125,8 @@ int sgx_match_project_frame(
  * Local map point i: m_xw (GetWorldPos), m_normal (GetNormal), m_min_dist / m_max_dist (mfMinDistance / mfMaxDistance), m_desc,
  * m_obs (Observations()), m_skip (isBad() or mnLastFrameSeen == current frame, Tracking.cc:1288-1291); per-frame pitch mcap (<= 4096).
  * cur_mp_obs[k] = Observations() of the map point keypoint k already holds (-1 = none; NULL = no keypoint holds one).
- * Out: cur_match[k] = local map point newly assigned to keypoint k or -1, nmatches, in_view[i] = mbTrackInView (for IncreaseVisible). */
+ * Out: cur_match[k] = local map point newly assigned to keypoint k or -1, nmatches, in_view[i] = mbTrackInView (for IncreaseVisible).
+ * The batched entry writes -1 to the rows [d_cn[f], cap) of d_cur_match; the rows [d_mn[f], mcap) of d_in_view are not written and nothing is promised about them. */
 int sgx_match_project_local_batch_dev(
     int batch, int cap, const sgx_keypoint *d_ckeys, const uint8_t *d_cdesc, const float *d_curight, const int32_t *d_cn, const float *d_cTcw, const int32_t *d_cur_mp_obs,
     int mcap, const int32_t *d_mn, const float *d_m_xw, const float *d_m_normal, const float *d_m_min_dist, const float *d_m_max_dist, const uint8_t *d_m_desc,
