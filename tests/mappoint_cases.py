@@ -40,14 +40,29 @@ def check_mappoint(lib, orc, n_cases=3):
     assert mappoint.ComputeDistinctiveDescriptors(np.zeros(1, 'i4'), np.zeros((0, 32), np.uint8), lib=lib)[0].shape == (0,)
 
 
+def triangulation_branches(pairs, a, b, cam):
+    """which branch of LocalMapping.cc:311-349 every pair takes, in float64: 'svd', 'unproject1', 'unproject2' or 'none'"""
+    rays = []
+    for k, idx in ((a, pairs[:, 0]), (b, pairs[:, 1])):
+        kk = k['keys_un'][idx]; xn = np.stack([(kk['x'] - cam['cx']) / cam['fx'], (kk['y'] - cam['cy']) / cam['fy'], np.ones(len(idx))], 1)
+        rays.append(xn @ np.asarray(k['Tcw'], 'f8')[:3, :3])              # Rwc xn as rows
+    r1, r2 = rays; cosr = (r1 * r2).sum(1) / np.linalg.norm(r1, axis=1) / np.linalg.norm(r2, axis=1)
+    s1 = a['uright'][pairs[:, 0]] >= 0; s2 = b['uright'][pairs[:, 1]] >= 0; mb = cam['bf'] / cam['fx']
+    c1 = np.where(s1, np.cos(2 * np.arctan2(mb / 2, a['depth'][pairs[:, 0]].astype('f8'))), cosr + 1)
+    c2 = np.where(~s1 & s2, np.cos(2 * np.arctan2(mb / 2, b['depth'][pairs[:, 1]].astype('f8'))), cosr + 1)
+    svd = (cosr < np.minimum(c1, c2)) & (cosr > 0) & (s1 | s2 | (cosr < 0.9998)); u1 = ~svd & s1 & (c1 < c2); u2 = ~svd & ~u1 & s2 & (c2 < c1)
+    return np.where(svd, 'svd', np.where(u1, 'unproject1', np.where(u2, 'unproject2', 'none')))
+
+
 def check_triangulation_step(lib, orc, n_cases=4, exact=True):
-    """CreateNewMapPoints' per-pair body on the pairs of SearchForTriangulation between two keyframes of a synthetic stream: every branch (SVD triangulation, stereo
-    unprojection of either side, the rejections) against the oracle"""
+    """CreateNewMapPoints' per-pair body on the pairs of SearchForTriangulation between two keyframes of a synthetic stream, against the oracle.  Counted by named branch
+    (triangulation_branches), these pairs take the SVD branch and its rejections only: at most one pair in a thousand is unprojected and none of those is kept.  The
+    unprojection of either side, 'neither', and every rejection by name are in match2_gate_cases (group N)."""
     import match2_cases as mc
     from scenes import CAM
     from sg_slam_amd.matcher import ORBmatcher
     sf = orc.orb_params()['scale']; sg = orc.orb_params()['sigma2']
-    tot = 0; svd_like = 0; branches = set()
+    tot = 0; svd_like = 0; branches = set(); kept = {}
     for c in range(n_cases):
         gen, kf1, kf2 = mc.make_keyframes(orc, 800 + c, 6 + c, 12 + 2 * c, only_some_mp=False)
         F12 = mc.fundamental_12(kf1, kf2)
@@ -71,7 +86,10 @@ def check_triangulation_step(lib, orc, n_cases=4, exact=True):
                 assert np.abs(gx[both] - ex[both]).max() <= 2e-3 * max(1.0, np.abs(ex[both]).max()), (c, variant, np.abs(gx[both] - ex[both]).max())
             tot += en; branches.add((variant, en > 0, en < len(pairs)))
             if variant == 1: svd_like += en
+            br = triangulation_branches(pairs, a, b, CAM)
+            for name in np.unique(br): kept[name] = kept.get(name, 0) + int(((br == name) & eok).sum())
     assert tot > 300 and svd_like > 20 and len(branches) >= 3, (tot, svd_like, branches)
+    assert kept.get('svd', 0) > 300, kept
     assert mappoint.TriangulateNewMapPoints(np.zeros((0, 2), 'i4'), A, B, CAM, sf, sg, lib=lib)[0] == 0
 
 
