@@ -938,6 +938,98 @@ int sgx_covis_essential_graph(sgx_covis *h, int32_t cur, int32_t loop, int n_gro
                               int32_t *vertex_id, uint8_t *vertex_fixed, int32_t *vertex_group, int ecap, int32_t *e_i, int32_t *e_j, uint8_t *e_kind,
                               sgx_covis_loop_report *report);
 
+/* LoopClosing::DetectLoop's covisibility consistency (src/sg-slam/src/LoopClosing.cc:152-225) with mvConsistentGroups as device state of the handle, and
+ * KeyFrame::GetConnectedKeyFrames of a batch of keyframes.  Integers only, one launch sequence without a read-back, no result depends on which wave finishes first, two
+ * runs byte-identical.
+ * State: mvConsistentGroups, a list of (set of keyframe ids, counter) in the reference's order.  It is not part of sgx_covis_create's totals: it is allocated by
+ *   sgx_covis_consistency_reserve(max_groups), or with max_groups = SGX_COVIS_DEFAULT_GROUPS by the first consistency call that finds none; the capacity stays until
+ *   sgx_covis_clear (a second reserve with the same value does nothing, with another one it is SGX_ERR_INVALID; max_groups < 1: SGX_ERR_INVALID, > 4096:
+ *   SGX_ERR_UNSUPPORTED).  Device memory: max_groups x (9 max_keyframes + 24) + 8 max_keyframes + 32 bytes (two halves of max_groups rows of max_keyframes ids, the
+ *   candidates x groups flag bytes, the descriptors).  sgx_covis_consistency_info reports the bytes (0 before), the number of groups and the capacity (0 before);
+ *   sgx_covis_info is unchanged.  sgx_covis_clear releases the memory; sgx_covis_consistency_clear drops the groups only.
+ * consistency(candidates, th): the candidates are vpCandidateKFs as keyframe ids in their order, with their number in device memory (what sgx_kfdb_detect_batch_dev
+ *   writes for one query: no read-back sits between the two calls); th = mnCovisibilityConsistencyTh (3).  As written in the reference: a candidate's group is the
+ *   candidate and every keyframe with a count >= 1 in its weight row (GetConnectedKeyFrames, not the gated list); the previous groups are visited in stored order; a
+ *   candidate consistent with previous group iG (they share a keyframe) that is not marked yet pushes ITS OWN group with counter previous + 1 and marks iG, so a
+ *   candidate consistent with two unmarked groups pushes its group twice with the two counters, and a later candidate consistent only with marked groups pushes nothing
+ *   (and is not pushed with 0 either); the test counter >= th is made for every consistent iG, marked or not, and enters the candidate into enough_dev (capacity
+ *   max_keyframes; mvpEnoughConsistentCandidates as ids in candidate order) at most once; a candidate consistent with no group pushes (group, 0); the new list, in
+ *   candidate order then iG order, replaces the old one.  No candidate (*n_cand_dev == 0) clears the groups (:147) and returns no enough-candidate.
+ *  12. a set of KeyFrame* is a set of keyframe ids.  A dead entry of a weight row (rule 4) is no member of a candidate's group, the choice of rule 11.  A stored group
+ *      keeps the id of a keyframe erased since (get_consistent_groups shows it) but never matches through it, and not through the keyframe that reuses its slot.
+ *      Keyframe ids are never reused by the caller (mnId is not): an erased id added again later would match the stored groups that still name it.
+ *  13. a candidate id the handle does not hold (unknown or erased), the same candidate twice, or a count outside [0, max_keyframes]: SGX_ERR_INVALID in the report;
+ *      more than max_groups resulting groups: SGX_ERR_NOMEM in the report.  In either case the stored groups, enough_dev and n_enough_dev are untouched.
+ *   A missing array is SGX_ERR_INVALID for the call, nothing enqueued.
+ * get_consistent_groups: host pointers, synchronous.  *n_groups, counter (capacity max_groups), and the members as a CSR: off (capacity max_groups + 1, whole) and ids
+ *   (capacity cap) ascending within a group; SGX_ERR_NOMEM when cap is short, with the leading groups that fit wholly written.
+ * connected_batch(Q keyframes): GetConnectedKeyFrames() of each, without dead entries (rule 12), as a CSR of ascending ids: off_dev (Q + 1, always whole; off[Q] is the
+ *   need) and ids_dev (capacity cap): the conn_offsets / conn_ids layout sgx_kfdb_detect_batch_dev takes.  One sgx_covis_report per query: status and n_counter = its
+ *   number of connected keyframes.  A row is written only if it fits wholly (off[q + 1] <= cap); otherwise that query's status is SGX_ERR_NOMEM and nothing of it is
+ *   written.  An unknown or erased keyframe: SGX_ERR_INVALID as that query's status and an empty row.  Q > max_queries, cap < 0, a missing array: SGX_ERR_INVALID for the
+ *   call.  The handle is not changed and no memory beyond the workspace of sgx_covis_create is used. */
+enum { SGX_COVIS_DEFAULT_GROUPS = 64 };
+typedef struct sgx_covis_consistency_report {
+    int32_t status;                         /* SGX_OK, SGX_ERR_INVALID, SGX_ERR_NOMEM */
+    int32_t n_before, n_after;              /* mvConsistentGroups.size() going in and coming out */
+    int32_t n_consistent;                   /* candidates consistent with some previous group */
+    int32_t n_pushed_zero;                  /* groups pushed with counter 0 */
+    int32_t n_pushed_nothing;               /* candidates that pushed nothing: every group they are consistent with was taken */
+    int32_t n_enough, n_cand;               /* mvpEnoughConsistentCandidates.size(); the candidates read */
+} sgx_covis_consistency_report;
+int sgx_covis_consistency_reserve(sgx_covis *h, int max_groups);
+int sgx_covis_consistency_clear(sgx_covis *h);
+int sgx_covis_consistency_info(const sgx_covis *h, int64_t *bytes, int32_t *n_groups, int32_t *max_groups);
+int sgx_covis_get_consistent_groups(const sgx_covis *h, int32_t *n_groups, int32_t *counter, int32_t *off, int cap, int32_t *ids);
+/* device pointers, asynchronous on `stream`; a handle serves one call at a time */
+int sgx_covis_consistency_dev(sgx_covis *h, const int32_t *cand_dev, const int32_t *n_cand_dev, int th, int32_t *enough_dev, int32_t *n_enough_dev,
+                              sgx_covis_consistency_report *report_dev, void *stream);
+int sgx_covis_connected_batch_dev(sgx_covis *h, int Q, const int32_t *kf_ids_dev, int32_t *off_dev, int32_t *ids_dev, int cap, sgx_covis_report *report_dev, void *stream);
+/* the same from host memory, synchronous.  consistency: the return value is the report's status; enough (capacity n_cand) and *n_enough are written on SGX_OK only.
+ * connected_batch (Q >= 1): off whole, the rows of the queries whose status is SGX_OK; the return value is the first query status that is not SGX_OK. */
+int sgx_covis_consistency(sgx_covis *h, int n_cand, const int32_t *cand, int th, int32_t *enough, int32_t *n_enough, sgx_covis_consistency_report *report);
+int sgx_covis_connected_batch(sgx_covis *h, int Q, const int32_t *kf_ids, int32_t *off, int32_t *ids, int cap, sgx_covis_report *report);
+
+/* The map update of LoopClosing::RunGlobalBundleAdjustment (src/sg-slam/src/LoopClosing.cc:676-737) after Optimizer::GlobalBundleAdjustemnt(nLoopKF), over the spanning
+ * tree the handle keeps.  One launch sequence, no read-back, no result depends on which wave finishes first, two runs byte-identical.
+ * gba_update: the table lists every live keyframe exactly once (nk rows: kf_ids, in_gba = mnBAGlobalForKF == nLoopKF on entry, Tcw = the pose, 3 x 4 float per row as
+ *   sgx_loop_propagate_sim3 takes it, TcwGBA = mTcwGBA, read only where in_gba is set); sgx_covis_ba_graph's global pose order is a natural choice.  The BFS of :676-700
+ *   from the origins (mvpKeyFrameOrigins) over the tree: a child that is not in_gba gets mTcwGBA = (Tcw_child * Twc_parent) * mTcwGBA_parent, both factors of the first
+ *   product being the OLD poses (:683 and :689 read before :698 writes), and is marked; every visited keyframe gets TcwBef = its old pose and Tcw_out = mTcwGBA.
+ *   kf_state: bit 0 = visited, bit 1 = mnBAGlobalForKF == nLoopKF afterwards.  Tcw_out must not be Tcw.
+ *   Arithmetic: float cv::Mat arithmetic as the Sim3 propagation states it: a product entry is a float dot product summed left to right, through double with alpha;
+ *   KeyFrame::SetPose gives Twc = [Rcw.t() | -Rwc * tcw] (alpha = -1); R * x + t is one gemm (the double of the dot product plus the double of t, rounded once).  The
+ *   unit is built without multiply-add fusion.  OpenCV is not pinned; the yardstick is the restatement of tests/loopclose_ref.py, bit for bit.
+ *  14. an origin that is not in_gba: status SGX_COVIS_GBA_ORIGIN_NOT_IN_GBA and nothing is written (the reference multiplies by a stale mTcwGBA).
+ *      An origin below another origin: the reference's queue would visit that subtree twice and overwrite mTcwBefGBA with the corrected pose on the second visit;
+ *      here every keyframe is visited once, TcwBef is the pose before the call, and a keyframe's level is counted up to the FIRST origin on its way up.
+ *  15. a live keyframe no origin reaches is not visited: its pose is copied through to Tcw_out, its TcwBef row is not written, it keeps bit 1 if it was in_gba; its
+ *      points are corrected only if it was visited (the reference reads a stale mTcwBefGBA there).  The report counts these keyframes.
+ *   SGX_ERR_INVALID in the report, nothing written: nk other than the number of live keyframes, an id that is no live keyframe or stands twice, an origin that is no
+ *   live keyframe.  A missing array, n_origins or nk outside [1, max_keyframes], Tcw_out == Tcw: SGX_ERR_INVALID for the call.  Device memory: 16 max_keyframes + 32
+ *   bytes, allocated by the first call, released with the handle.
+ * correct_points (:705-736): a point in the GBA (in_gba[i]) takes xw_gba; any other takes Rwc * (Rcw_bef * Xw + tcw_bef) + twc of its reference keyframe ref[i] (a row
+ *   of the table, -1 none; the caller supplies it, as for the loop correction, and the _dev form trusts it) if that keyframe's state is 3, and stays as it was
+ *   otherwise.  Bad points are the caller's to leave out.  One lane per point, memory-bound. */
+enum { SGX_COVIS_GBA_ORIGIN_NOT_IN_GBA = 1 };
+typedef struct sgx_covis_gba_report {
+    int32_t status;                         /* SGX_OK, SGX_ERR_INVALID, SGX_COVIS_GBA_ORIGIN_NOT_IN_GBA */
+    int32_t n_visited, n_propagated;        /* keyframes the BFS visited; of these, not in the GBA */
+    int32_t n_unreached;                    /* rule 15 */
+    int32_t max_depth;                      /* the longest chain of keyframes outside the GBA below an optimised one */
+    int32_t pad[3];
+} sgx_covis_gba_report;
+int sgx_covis_gba_update_dev(sgx_covis *h, int n_origins, const int32_t *origins_dev, int nk, const int32_t *kf_ids_dev, const uint8_t *in_gba_dev, const float *Tcw_dev,
+                             const float *TcwGBA_dev, float *Tcw_out_dev, float *TcwBef_dev, uint8_t *kf_state_dev, sgx_covis_gba_report *report_dev, void *stream);
+int sgx_gba_correct_points_dev(int n, const float *xw_dev, const uint8_t *in_gba_dev, const float *xw_gba_dev, const int32_t *ref_dev, const uint8_t *kf_state_dev,
+                               const float *TcwBef_dev, const float *Tcw_out_dev, float *xw_out_dev, void *stream);
+/* the same from host memory, synchronous; the return value is the report's status, and nothing is written unless it is SGX_OK (TcwBef is in/out) */
+int sgx_covis_gba_update(sgx_covis *h, int n_origins, const int32_t *origins, int nk, const int32_t *kf_ids, const uint8_t *in_gba, const float *Tcw, const float *TcwGBA,
+                         float *Tcw_out, float *TcwBef, uint8_t *kf_state, sgx_covis_gba_report *report);
+/* the point loop from host memory through sgx_gba_correct_points_dev, synchronous; nk = the rows of the keyframe table: a ref outside [-1, nk) is SGX_ERR_INVALID */
+int sgx_gba_correct_points(int n, const float *xw, const uint8_t *in_gba, const float *xw_gba, const int32_t *ref, int nk, const uint8_t *kf_state, const float *TcwBef,
+                           const float *Tcw_out, float *xw_out);
+
 /* The colour conversion at the top of Tracking::GrabImageRGBD (src/sg-slam/src/Tracking.cc:214-227): cvtColor(CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) on
  * 8-bit images, OpenCV's fixed point (R*4899 + G*9617 + B*1868 + 8192) >> 14.  blue_first = !mbRGB.  Pitches in bytes, multiples of 4; pointers 4-byte aligned. */
 int sgx_frame_gray_from_color_batch_dev(int batch, int width, int height, const uint8_t *d_src, int src_pitch, int channels, int blue_first,

@@ -134,6 +134,9 @@ COVIS_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_counter', 'max_w
 COVIS_BA_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_local_kf', 'n_fixed_kf', 'n_poses', 'n_points', 'n_edges', 'n_mono_edges',
                                                       'n_stereo_edges')])   # sgx_covis_ba_report, 32 B
 COVIS_LOOP_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_group', 'n_points', 'n_connections', 'n_vertices', 'n_edges')] + [('n_kind', 'i4', (4,))])   # sgx_covis_loop_report, 40 B
+COVIS_CONSISTENCY_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_before', 'n_after', 'n_consistent', 'n_pushed_zero', 'n_pushed_nothing', 'n_enough',
+                                                               'n_cand')])   # sgx_covis_consistency_report, 32 B
+COVIS_GBA_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_visited', 'n_propagated', 'n_unreached', 'max_depth')] + [('pad', 'i4', (3,))])   # sgx_covis_gba_report, 32 B
 
 
 class OrbConfig(C.Structure):
@@ -179,6 +182,8 @@ SYMBOLS = [
     'sgx_covis_keyframe_culling_batch_dev', 'sgx_covis_update_connections', 'sgx_covis_local_map', 'sgx_covis_keyframe_culling', 'sgx_covis_ba_graph_batch_dev',
     'sgx_covis_ba_graph', 'sgx_covis_add_loop_edge', 'sgx_covis_get_loop_edges', 'sgx_covis_loop_info', 'sgx_covis_loop_begin_dev', 'sgx_covis_loop_connections_dev',
     'sgx_covis_essential_graph_dev', 'sgx_covis_loop_begin', 'sgx_covis_loop_connections', 'sgx_covis_essential_graph',
+    'sgx_covis_consistency_reserve', 'sgx_covis_consistency_clear', 'sgx_covis_consistency_info', 'sgx_covis_get_consistent_groups', 'sgx_covis_consistency_dev',
+    'sgx_covis_connected_batch_dev', 'sgx_covis_consistency', 'sgx_covis_connected_batch', 'sgx_covis_gba_update_dev', 'sgx_gba_correct_points_dev', 'sgx_covis_gba_update', 'sgx_gba_correct_points',
     'sgx_loop_propagate_sim3_dev', 'sgx_eg_flatten_dev', 'sgx_eg_recover_dev', 'sgx_correct_map_points_dev', 'sgx_loop_propagate_sim3', 'sgx_eg_flatten', 'sgx_eg_recover',
     'sgx_octomap_create', 'sgx_octomap_destroy', 'sgx_octomap_reset', 'sgx_octomap_insert_batch_dev', 'sgx_octomap_insert', 'sgx_octomap_bounds', 'sgx_octomap_cells_dev',
     'sgx_octomap_cells', 'sgx_octomap_search_dev', 'sgx_octomap_grid_header', 'sgx_octomap_project_dev', 'sgx_octomap_project', 'sgx_octomap_sensor_to_world',
@@ -397,6 +402,18 @@ class SgxLib:
         d.sgx_covis_loop_begin.argtypes = [vp, C.c_int32, vp, vp, C.c_int, vp, vp, vp]
         d.sgx_covis_loop_connections.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int, vp, vp, vp]
         d.sgx_covis_essential_graph.argtypes = [vp, C.c_int32, C.c_int32, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+        d.sgx_covis_consistency_reserve.argtypes = [vp, C.c_int]
+        d.sgx_covis_consistency_clear.argtypes = [vp]
+        d.sgx_covis_consistency_info.argtypes = [vp, vp, vp, vp]
+        d.sgx_covis_get_consistent_groups.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+        d.sgx_covis_consistency_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
+        d.sgx_covis_connected_batch_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+        d.sgx_covis_consistency.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp]
+        d.sgx_covis_connected_batch.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
+        d.sgx_covis_gba_update_dev.argtypes = [vp, C.c_int, vp, C.c_int] + [vp] * 9
+        d.sgx_gba_correct_points_dev.argtypes = [C.c_int] + [vp] * 9
+        d.sgx_covis_gba_update.argtypes = [vp, C.c_int, vp, C.c_int] + [vp] * 8
+        d.sgx_gba_correct_points.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
         d.sgx_loop_propagate_sim3_dev.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp]
         d.sgx_eg_flatten_dev.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         d.sgx_eg_recover_dev.argtypes = [C.c_int, vp, vp, vp, vp]

@@ -8,7 +8,7 @@ global_ba_graph, ba_graph_batch, with apply_ba_erase for the vToErase loop (:745
 with the vertices and edges of Optimizer::OptimizeEssentialGraph (Optimizer.cc:797-983): add_loop_edge, loop_begin, loop_connections, essential_graph.  Keyframes are named by the caller's mnId, points by dense handles in [0, max_points)."""
 import ctypes as C
 import numpy as np
-from .capi import _vp, COVIS_REPORT_DTYPE, COVIS_BA_REPORT_DTYPE, COVIS_LOOP_REPORT_DTYPE
+from .capi import _vp, COVIS_REPORT_DTYPE, COVIS_BA_REPORT_DTYPE, COVIS_LOOP_REPORT_DTYPE, COVIS_CONSISTENCY_REPORT_DTYPE, COVIS_GBA_REPORT_DTYPE
 
 
 def _i4(v):
@@ -363,6 +363,102 @@ class CovisibilityGraph:
         if cur != loop: self.add_loop_edge(loop, cur)
         return dict(Tcw={int(k): Tnew[j] for j, k in enumerate(g['vertex_id'])}, xw=xw, begin=b, connections=c, graph=g, noncorrected=non, corrected=cor, corrected_Tiw=cTiw,
                     S_in=S_in, e_meas=e_meas, S_out=S_out, stats=stats, corrected_Swc=cSwc)
+
+    # ---- DetectLoop: GetConnectedKeyFrames of a batch, and mvConsistentGroups as state of the handle
+    def connected_batch_dev(self, Q, kf_ids_dev, off_dev, ids_dev, cap, report_dev, stream=None):
+        self._keep = (kf_ids_dev, off_dev, ids_dev, report_dev)
+        self.lib.check(self.lib.dll.sgx_covis_connected_batch_dev(self.h, int(Q), _vp(kf_ids_dev), _vp(off_dev), _vp(ids_dev), int(cap), _vp(report_dev),
+                                                                  self._stream(stream)), 'sgx_covis_connected_batch_dev')
+
+    def connected_batch(self, kf_ids, cap=None, stream=None):
+        """GetConnectedKeyFrames() of the listed keyframes as a CSR of ascending ids (dead entries left out): the conn_offsets / conn_ids of
+        KeyFrameDatabase.DetectLoopCandidates.  Returns off (whole), ids (the leading rows that were written), status per query, n per query, and the raw id row."""
+        k = _i4(kf_ids); Q = len(k)
+        cap = int(Q * self.max_keyframes if cap is None else cap); c = max(cap, 0)
+        d = [self._dev(x) for x in (k, np.full(Q + 1, -1, 'i4'), np.full(max(c, 1), -1, 'i4'), np.zeros(Q * COVIS_REPORT_DTYPE.itemsize, 'u1'))]
+        self.connected_batch_dev(Q, d[0], d[1], d[2], cap, d[3], stream)
+        self._sync(stream)
+        _, off, ids, rep = [self._host(x) for x in d]
+        rep = rep.view(COVIS_REPORT_DTYPE)
+        rows = [ids[off[q]:off[q + 1]].copy() if int(rep[q]['status']) == 0 else None for q in range(Q)]
+        return dict(off=off.copy(), rows=rows, status=[int(r['status']) for r in rep], n=[int(r['n_counter']) for r in rep], raw=ids)
+
+    def consistency_reserve(self, max_groups):
+        self.lib.check(self.lib.dll.sgx_covis_consistency_reserve(self.h, int(max_groups)), 'sgx_covis_consistency_reserve')
+
+    def consistency_clear(self):
+        self.lib.check(self.lib.dll.sgx_covis_consistency_clear(self.h), 'sgx_covis_consistency_clear')
+
+    def consistency_info(self):
+        """(device bytes of the groups: 0 before they are reserved, groups stored, max_groups: 0 before)"""
+        a = C.c_int64(); n = C.c_int32(); g = C.c_int32()
+        self.lib.check(self.lib.dll.sgx_covis_consistency_info(self.h, C.byref(a), C.byref(n), C.byref(g)), 'sgx_covis_consistency_info')
+        return a.value, n.value, g.value
+
+    def consistent_groups(self):
+        """mvConsistentGroups as [(members as ascending ids, counter)] in stored order"""
+        G = self.consistency_info()[2]
+        n = C.c_int32(); cnt = np.zeros(max(G, 1), 'i4'); off = np.zeros(G + 1, 'i4'); ids = np.zeros(max(G * self.max_keyframes, 1), 'i4')
+        self.lib.check(self.lib.dll.sgx_covis_get_consistent_groups(self.h, C.byref(n), _vp(cnt), _vp(off), len(ids), _vp(ids)), 'sgx_covis_get_consistent_groups')
+        return [([int(x) for x in ids[off[g]:off[g + 1]]], int(cnt[g])) for g in range(n.value)]
+
+    def consistency_dev(self, cand_dev, n_cand_dev, th, enough_dev, n_enough_dev, report_dev, stream=None):
+        self._keep = (cand_dev, n_cand_dev, enough_dev, n_enough_dev, report_dev)
+        self.lib.check(self.lib.dll.sgx_covis_consistency_dev(self.h, _vp(cand_dev), _vp(n_cand_dev), int(th), _vp(enough_dev), _vp(n_enough_dev), _vp(report_dev),
+                                                              self._stream(stream)), 'sgx_covis_consistency_dev')
+
+    def consistency(self, candidates, th=3, max_groups=None, stream=None):
+        """LoopClosing::DetectLoop :152-211 for vpCandidateKFs as ids: the groups of the handle are replaced, and mvpEnoughConsistentCandidates comes back as ids.
+        max_groups: the capacity, if this is the call that reserves the groups.  Returns status, enough (None unless status is 0), the report, and the raw rows."""
+        c = _i4(candidates)
+        if max_groups is not None: self.consistency_reserve(max_groups)
+        d = [self._dev(x) for x in (c if len(c) else np.zeros(1, 'i4'), np.array([len(c)], 'i4'), np.full(self.max_keyframes, -7, 'i4'), np.full(1, -7, 'i4'),
+                                    np.zeros(COVIS_CONSISTENCY_REPORT_DTYPE.itemsize, 'u1'))]
+        self.consistency_dev(d[0], d[1], th, d[2], d[3], d[4], stream)
+        self._sync(stream)
+        _, _, en, nen, rep = [self._host(x) for x in d]
+        r = rep.view(COVIS_CONSISTENCY_REPORT_DTYPE)[0].copy(); st = int(r['status'])
+        return dict(status=st, enough=[int(x) for x in en[:int(nen[0])]] if st == 0 else None, report=r, raw=(en, nen))
+
+    # ---- RunGlobalBundleAdjustment's map update
+    GBA_ORIGIN_NOT_IN_GBA = 1
+
+    def gba_update_dev(self, n_origins, origins_dev, nk, kf_ids_dev, in_gba_dev, Tcw_dev, TcwGBA_dev, Tcw_out_dev, TcwBef_dev, kf_state_dev, report_dev, stream=None):
+        self._keep = (origins_dev, kf_ids_dev, in_gba_dev, Tcw_dev, TcwGBA_dev, Tcw_out_dev, TcwBef_dev, kf_state_dev, report_dev)
+        self.lib.check(self.lib.dll.sgx_covis_gba_update_dev(self.h, int(n_origins), _vp(origins_dev), int(nk), _vp(kf_ids_dev), _vp(in_gba_dev), _vp(Tcw_dev), _vp(TcwGBA_dev),
+                                                             _vp(Tcw_out_dev), _vp(TcwBef_dev), _vp(kf_state_dev), _vp(report_dev), self._stream(stream)), 'sgx_covis_gba_update_dev')
+
+    def correct_points_gba_dev(self, n, xw_dev, in_gba_dev, xw_gba_dev, ref_dev, kf_state_dev, TcwBef_dev, Tcw_out_dev, xw_out_dev, stream=None):
+        self._keep2 = (xw_dev, in_gba_dev, xw_gba_dev, ref_dev, kf_state_dev, TcwBef_dev, Tcw_out_dev, xw_out_dev)
+        self.lib.check(self.lib.dll.sgx_gba_correct_points_dev(int(n), _vp(xw_dev), _vp(in_gba_dev), _vp(xw_gba_dev), _vp(ref_dev), _vp(kf_state_dev), _vp(TcwBef_dev),
+                                                               _vp(Tcw_out_dev), _vp(xw_out_dev), self._stream(stream)), 'sgx_gba_correct_points_dev')
+
+    def gba_update(self, origins, kf_ids, in_gba, Tcw, TcwGBA, points=None, poison=None, stream=None):
+        """LoopClosing::RunGlobalBundleAdjustment :676-737 after global BA.  kf_ids lists every live keyframe once; in_gba = mnBAGlobalForKF == nLoopKF; Tcw / TcwGBA
+        3 x 4 (or 4 x 4) per row; origins = mvpKeyFrameOrigins as ids.  points (optional) = dict(xw, in_gba, xw_gba, ref = row of the reference keyframe or -1).
+        Returns status, Tcw_out, TcwBef, kf_state, report and with points xw_out; the outputs start from the 32-bit pattern `poison` (default 0), so what a call did not write shows."""
+        o = _i4(origins); k = _i4(kf_ids); nk = len(k)
+        g = np.ascontiguousarray(np.asarray(in_gba).reshape(-1) != 0, 'u1'); assert len(g) == nk
+        T = np.ascontiguousarray(np.asarray(Tcw, 'f4').reshape(nk, -1, 4)[:, :3, :]); Tg = np.ascontiguousarray(np.asarray(TcwGBA, 'f4').reshape(nk, -1, 4)[:, :3, :])
+        fill = lambda shape: np.full(shape, 0 if poison is None else int(poison), 'u4').view('f4')      # poison: a 32-bit pattern
+        d = [self._dev(x) for x in (o, k, g, T, Tg, fill((nk, 3, 4)), fill((nk, 3, 4)), np.full(nk, 0x55, 'u1'), np.zeros(COVIS_GBA_REPORT_DTYPE.itemsize, 'u1'))]
+        self.gba_update_dev(len(o), d[0], nk, d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], stream)
+        out = {}
+        if points is not None:
+            x = np.ascontiguousarray(points['xw'], 'f4').reshape(-1, 3); n = len(x)
+            pg = np.ascontiguousarray(np.asarray(points['in_gba']).reshape(-1) != 0, 'u1'); xg = np.ascontiguousarray(points['xw_gba'], 'f4').reshape(-1, 3); ref = _i4(points['ref'])
+            assert len(pg) == len(xg) == len(ref) == n and (ref >= -1).all() and (ref < nk).all()
+            self._sync(stream)
+            if int(self._host(d[8]).view(COVIS_GBA_REPORT_DTYPE)[0]['status']) == 0 and n:
+                e = [self._dev(v) for v in (x, pg, xg, ref, fill((n, 3)))]
+                self.correct_points_gba_dev(n, e[0], e[1], e[2], e[3], d[7], d[6], d[5], e[4], stream)
+                self._sync(stream)
+                out['xw_out'] = np.array(self._host(e[4]), 'f4')
+            else: out['xw_out'] = None if n else x.copy()
+        self._sync(stream)
+        r = self._host(d[8]).view(COVIS_GBA_REPORT_DTYPE)[0].copy()
+        out.update(status=int(r['status']), Tcw_out=np.array(self._host(d[5]), 'f4'), TcwBef=np.array(self._host(d[6]), 'f4'), kf_state=np.array(self._host(d[7]), 'u1'), report=r)
+        return out
 
     def close(self):
         if self.h: self.lib.dll.sgx_covis_destroy(self.h); self.h = C.c_void_p()

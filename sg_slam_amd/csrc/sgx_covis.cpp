@@ -4,6 +4,8 @@
 // loop closing's group / LoopConnections / essential graph) as the launch sequences of sgx_covis_kernels.h and sgx_covis_loop_kernels.h.
 #include "sgx_covis_kernels.h"
 #include "sgx_covis_loop_kernels.h"
+#include "sgx_covis_detect_kernels.h"
+#include "sgx_covis_gba_kernels.h"
 #include "sgx_devmem.h"
 #include "../../include/sgx.h"
 #include <stdio.h>
@@ -17,6 +19,9 @@
 static_assert(sizeof(sgx_covis_report) == sizeof(SgxCovisReport), "the kernels write sgx_covis_report records");
 static_assert(sizeof(sgx_covis_ba_report) == sizeof(SgxCovisBaReport), "the kernels write sgx_covis_ba_report records");
 static_assert(sizeof(sgx_covis_loop_report) == sizeof(SgxCovisLoopReport), "the kernels write sgx_covis_loop_report records");
+static_assert(sizeof(sgx_covis_consistency_report) == sizeof(SgxCovisCgReport), "the kernels write sgx_covis_consistency_report records");
+static_assert(sizeof(sgx_covis_gba_report) == sizeof(SgxCovisGbaReport), "the kernels write sgx_covis_gba_report records");
+static_assert(SGX_ERR_INVALID == -1 && SGX_ERR_NOMEM == -3 && (int)SGX_COVIS_GBA_ORIGIN_NOT_IN_GBA == (int)SGX_GBA_ORIGIN_NOT_IN_GBA, "the kernels write these statuses as numbers");
 
 enum { H_FREE = 0, H_LIVE = 1, H_HDR = 2, COVIS_JCAP = 1 << 16, COVIS_GRID = 128 };
 
@@ -45,6 +50,13 @@ struct sgx_covis {
         *lw_vidx = nullptr, *lw_vcnt = nullptr, *lw_vbase = nullptr, *lw_flags = nullptr;
     SgxCovisReport *lw_rep = nullptr;
     int64_t loop_bytes = 0;
+    // DetectLoop: mvConsistentGroups (sgx_covis_detect_kernels.h), allocated by sgx_covis_consistency_reserve or the first consistency call; sgx_covis_clear releases it
+    int cg_G = 0;
+    int *cg_st = nullptr, *cg_cnt = nullptr, *cg_size = nullptr, *cg_mem = nullptr, *cg_cvalid = nullptr, *cg_nd_cand = nullptr, *cg_nd_cnt = nullptr, *cg_tmp = nullptr;
+    unsigned char *cg_flags = nullptr;
+    int64_t cg_bytes = 0;
+    // RunGlobalBundleAdjustment's map update (sgx_covis_gba_kernels.h): 16 max_keyframes + 32 bytes, allocated by the first call
+    int *gb_row_of = nullptr, *gb_orig = nullptr, *gb_level = nullptr, *gb_prow = nullptr, *gb_gs = nullptr;
     SgxDevMem mem;
 
     int32_t &H(size_t i) { return heap[i]; }
@@ -166,6 +178,10 @@ static void covis_reset_host(sgx_covis *h)
     for (int s = h->max_kf - 1; s >= 0; s--) h->free_slots.push_back(s);
     h->by_id.clear(); h->dead_ids.clear(); h->undo.clear(); h->nslots = 0; h->tables_dirty = true;
     h->loop_edges.clear();
+    void *cg[] = { h->cg_st, h->cg_cnt, h->cg_size, h->cg_mem, h->cg_cvalid, h->cg_nd_cand, h->cg_nd_cnt, h->cg_tmp, h->cg_flags };
+    for (void *q : cg) h->mem.release(q);
+    h->cg_st = h->cg_cnt = h->cg_size = h->cg_mem = h->cg_cvalid = h->cg_nd_cand = h->cg_nd_cnt = h->cg_tmp = nullptr; h->cg_flags = nullptr;
+    h->cg_G = 0; h->cg_bytes = 0;
 }
 
 static int covis_reset_device(sgx_covis *h)
@@ -890,4 +906,236 @@ extern "C" int sgx_covis_essential_graph(sgx_covis *h, int32_t cur, int32_t loop
     if (ne) { SGX_CHECK_HIP(hipMemcpy(e_i, d_ei, ne * 4, hipMemcpyDeviceToHost)); SGX_CHECK_HIP(hipMemcpy(e_j, d_ej, ne * 4, hipMemcpyDeviceToHost));
               SGX_CHECK_HIP(hipMemcpy(e_kind, d_ek, ne, hipMemcpyDeviceToHost)); }
     return R.status;                                                               // SGX_OK, or SGX_ERR_NOMEM with the first ecap edges written
+}
+
+// ---- DetectLoop's consistency groups (sgx_covis_detect_kernels.h): mvConsistentGroups as device state, allocated on demand, and GetConnectedKeyFrames as a CSR
+extern "C" int sgx_covis_consistency_reserve(sgx_covis *h, int max_groups)
+{
+    if (!h || max_groups < 1) return SGX_ERR_INVALID;
+    if (max_groups > SGX_COVIS_MAX_GROUPS) return SGX_ERR_UNSUPPORTED;
+    if (h->cg_G) return h->cg_G == max_groups ? SGX_OK : SGX_ERR_INVALID;         // the capacity is fixed by the first reservation; sgx_covis_clear drops it
+    const size_t N = (size_t)h->max_kf, G = (size_t)max_groups;
+    SgxDevMem m;                                                                  // all or nothing: the buffers move to the handle once every one is there
+    int *st = nullptr, *cnt = nullptr, *size = nullptr, *mem = nullptr, *cvalid = nullptr, *nd_cand = nullptr, *nd_cnt = nullptr, *tmp = nullptr; unsigned char *flags = nullptr;
+    int rc;
+    if ((rc = m.alloc(&st, (size_t)CG_FIELDS)) || (rc = m.alloc(&cnt, 2 * G)) || (rc = m.alloc(&size, 2 * G)) || (rc = m.alloc(&mem, 2 * G * N)) || (rc = m.alloc(&cvalid, N)) ||
+        (rc = m.alloc(&nd_cand, G)) || (rc = m.alloc(&nd_cnt, G)) || (rc = m.alloc(&tmp, N)) || (rc = m.alloc(&flags, N * G))) return rc;
+    SGX_CHECK_HIP(hipMemset(st, 0, CG_FIELDS * 4));
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    h->mem.owned.insert(h->mem.owned.end(), m.owned.begin(), m.owned.end()); m.owned.clear();
+    h->cg_st = st; h->cg_cnt = cnt; h->cg_size = size; h->cg_mem = mem; h->cg_cvalid = cvalid; h->cg_nd_cand = nd_cand; h->cg_nd_cnt = nd_cnt; h->cg_tmp = tmp; h->cg_flags = flags;
+    h->cg_G = max_groups;
+    h->cg_bytes = (int64_t)(G * (9 * N + 24) + 8 * N + 4 * CG_FIELDS);
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_consistency_clear(sgx_covis *h)
+{
+    if (!h) return SGX_ERR_INVALID;
+    if (!h->cg_G) return SGX_OK;
+    SGX_CHECK_HIP(hipMemset(h->cg_st, 0, CG_FIELDS * 4));
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    return SGX_OK;
+}
+
+// the scalars of the groups as they stand (a blocking copy: the calls enqueued before it have run)
+static int covis_cg_state(const sgx_covis *h, int32_t st[CG_FIELDS])
+{
+    for (int i = 0; i < CG_FIELDS; i++) st[i] = 0;
+    if (h->cg_G) SGX_CHECK_HIP(hipMemcpy(st, h->cg_st, CG_FIELDS * 4, hipMemcpyDeviceToHost));
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_consistency_info(const sgx_covis *h, int64_t *bytes, int32_t *n_groups, int32_t *max_groups)
+{
+    if (!h) return SGX_ERR_INVALID;
+    int32_t st[CG_FIELDS];
+    const int rc = covis_cg_state(h, st);
+    if (rc != SGX_OK) return rc;
+    if (bytes) *bytes = h->cg_bytes;
+    if (n_groups) *n_groups = st[CG_N];
+    if (max_groups) *max_groups = h->cg_G;
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_get_consistent_groups(const sgx_covis *h, int32_t *n_groups, int32_t *counter, int32_t *off, int cap, int32_t *ids)
+{
+    if (!h || !n_groups || !off || cap < 0 || (cap > 0 && !ids)) return SGX_ERR_INVALID;
+    int32_t st[CG_FIELDS];
+    int rc = covis_cg_state(h, st);
+    if (rc != SGX_OK) return rc;
+    const size_t n = (size_t)st[CG_N], G = (size_t)h->cg_G, base = (size_t)st[CG_CUR] * G;
+    if (n && !counter) return SGX_ERR_INVALID;
+    std::vector<int32_t> size(n);
+    if (n) {
+        SGX_CHECK_HIP(hipMemcpy(counter, h->cg_cnt + base, n * 4, hipMemcpyDeviceToHost));
+        SGX_CHECK_HIP(hipMemcpy(size.data(), h->cg_size + base, n * 4, hipMemcpyDeviceToHost));
+    }
+    *n_groups = (int32_t)n; off[0] = 0;
+    for (size_t g = 0; g < n; g++) off[g + 1] = off[g] + size[g];
+    rc = SGX_OK;
+    for (size_t g = 0; g < n; g++) {                                              // the rows that fit wholly
+        if (off[g + 1] > cap) { rc = SGX_ERR_NOMEM; break; }
+        if (size[g]) SGX_CHECK_HIP(hipMemcpy(ids + off[g], h->cg_mem + (base + g) * (size_t)h->max_kf, (size_t)size[g] * 4, hipMemcpyDeviceToHost));
+    }
+    return rc;
+}
+
+extern "C" int sgx_covis_consistency_dev(sgx_covis *h, const int32_t *cand_dev, const int32_t *n_cand_dev, int th, int32_t *enough_dev, int32_t *n_enough_dev,
+                                         sgx_covis_consistency_report *report_dev, void *stream)
+{
+    if (!h || !cand_dev || !n_cand_dev || !enough_dev || !n_enough_dev || !report_dev) return SGX_ERR_INVALID;
+    int rc;
+    if (!h->cg_G && (rc = sgx_covis_consistency_reserve(h, SGX_COVIS_DEFAULT_GROUPS)) != SGX_OK) return rc;
+    if ((rc = covis_sync_tables(h)) != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    SgxCovisArgs A = covis_args(h);
+    SgxCovisCgArgs D{};
+    D.G = h->cg_G; D.th = th; D.st = h->cg_st; D.cnt = h->cg_cnt; D.size = h->cg_size; D.mem = h->cg_mem; D.flags = h->cg_flags; D.cvalid = h->cg_cvalid;
+    D.nd_cand = h->cg_nd_cand; D.nd_cnt = h->cg_nd_cnt; D.tmp_enough = h->cg_tmp; D.cand = cand_dev; D.n_cand = n_cand_dev; D.enough = enough_dev; D.n_enough = n_enough_dev;
+    D.report = (SgxCovisCgReport *)report_dev;
+    const unsigned G = (unsigned)std::max(1, std::min(h->max_kf, (int)COVIS_GRID));
+    SGX_LAUNCH(k_covis_cg_match, dim3(G), dim3(256), s, A, D);
+    SGX_LAUNCH(k_covis_cg_replay, dim3(1), dim3(64), s, A, D);
+    SGX_LAUNCH(k_covis_cg_store, dim3((unsigned)std::min(h->cg_G, (int)COVIS_GRID)), dim3(256), s, A, D);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_consistency(sgx_covis *h, int n_cand, const int32_t *cand, int th, int32_t *enough, int32_t *n_enough, sgx_covis_consistency_report *report)
+{
+    if (!h || n_cand < 0 || n_cand > h->max_kf || (n_cand > 0 && (!cand || !enough)) || !n_enough) return SGX_ERR_INVALID;
+    SgxDevMem m; int rc;
+    int32_t *d_c = nullptr, *d_n = nullptr, *d_e = nullptr, *d_ne = nullptr; sgx_covis_consistency_report *d_rep = nullptr;
+    const int32_t n32 = n_cand;
+    if ((rc = covis_stage(m, &d_c, cand, (size_t)n_cand, (size_t)n_cand)) || (rc = covis_stage(m, &d_n, &n32, 1, 1)) || (rc = m.alloc(&d_e, (size_t)h->max_kf)) ||
+        (rc = m.alloc(&d_ne, 1)) || (rc = m.alloc(&d_rep, 1))) return rc;
+    if ((rc = sgx_covis_consistency_dev(h, d_c, d_n, th, d_e, d_ne, d_rep, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    sgx_covis_consistency_report R;
+    SGX_CHECK_HIP(hipMemcpy(&R, d_rep, sizeof(R), hipMemcpyDeviceToHost));
+    if (report) *report = R;
+    if (R.status != SGX_OK) return R.status;                                      // rule 13: nothing was written
+    if (R.n_enough) SGX_CHECK_HIP(hipMemcpy(enough, d_e, (size_t)R.n_enough * 4, hipMemcpyDeviceToHost));
+    *n_enough = R.n_enough;
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_connected_batch_dev(sgx_covis *h, int Q, const int32_t *kf_ids_dev, int32_t *off_dev, int32_t *ids_dev, int cap, sgx_covis_report *report_dev, void *stream)
+{
+    if (!h || Q < 0 || Q > h->max_q || cap < 0) return SGX_ERR_INVALID;
+    if (Q == 0) return SGX_OK;
+    if (!kf_ids_dev || !off_dev || (cap > 0 && !ids_dev) || !report_dev) return SGX_ERR_INVALID;
+    const int rc = covis_sync_tables(h);
+    if (rc != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    SgxCovisArgs A = covis_args(h);
+    A.Q = Q; A.q_kf = kf_ids_dev; A.report = (SgxCovisReport *)report_dev;
+    SGX_LAUNCH(k_covis_conn_count, dim3((unsigned)Q), dim3(256), s, A);
+    SGX_LAUNCH(k_covis_conn_emit, dim3((unsigned)Q), dim3(256), s, A, off_dev, ids_dev, cap);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_connected_batch(sgx_covis *h, int Q, const int32_t *kf_ids, int32_t *off, int32_t *ids, int cap, sgx_covis_report *report)
+{
+    if (!h || Q < 1 || Q > h->max_q || !kf_ids || !off || cap < 0 || (cap > 0 && !ids)) return SGX_ERR_INVALID;
+    SgxDevMem m; int rc;
+    int32_t *d_k = nullptr, *d_o = nullptr, *d_i = nullptr; sgx_covis_report *d_rep = nullptr;
+    if ((rc = covis_stage(m, &d_k, kf_ids, (size_t)Q, (size_t)Q)) || (rc = m.alloc(&d_o, (size_t)Q + 1)) || (rc = m.alloc(&d_i, (size_t)cap)) || (rc = m.alloc(&d_rep, (size_t)Q))) return rc;
+    if ((rc = sgx_covis_connected_batch_dev(h, Q, d_k, d_o, d_i, cap, d_rep, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    std::vector<sgx_covis_report> R((size_t)Q);
+    SGX_CHECK_HIP(hipMemcpy(R.data(), d_rep, R.size() * sizeof(sgx_covis_report), hipMemcpyDeviceToHost));
+    SGX_CHECK_HIP(hipMemcpy(off, d_o, ((size_t)Q + 1) * 4, hipMemcpyDeviceToHost));
+    rc = SGX_OK;
+    for (int q = 0; q < Q; q++) {
+        if (report) report[q] = R[(size_t)q];
+        if (R[(size_t)q].status != SGX_OK) { if (rc == SGX_OK) rc = R[(size_t)q].status; continue; }
+        if (off[q + 1] > off[q]) SGX_CHECK_HIP(hipMemcpy(ids + off[q], d_i + off[q], (size_t)(off[q + 1] - off[q]) * 4, hipMemcpyDeviceToHost));
+    }
+    return rc;                                                                    // SGX_OK, or the first query status that is not
+}
+
+// ---- RunGlobalBundleAdjustment's map update (sgx_covis_gba_kernels.h)
+extern "C" int sgx_covis_gba_update_dev(sgx_covis *h, int n_origins, const int32_t *origins_dev, int nk, const int32_t *kf_ids_dev, const uint8_t *in_gba_dev, const float *Tcw_dev,
+                                        const float *TcwGBA_dev, float *Tcw_out_dev, float *TcwBef_dev, uint8_t *kf_state_dev, sgx_covis_gba_report *report_dev, void *stream)
+{
+    if (!h || n_origins < 1 || n_origins > h->max_kf || !origins_dev || nk < 1 || nk > h->max_kf || !kf_ids_dev || !in_gba_dev || !Tcw_dev || !TcwGBA_dev || !Tcw_out_dev ||
+        !TcwBef_dev || !kf_state_dev || !report_dev || Tcw_out_dev == Tcw_dev) return SGX_ERR_INVALID;
+    const size_t N = (size_t)h->max_kf;
+    int rc;
+    if (!h->gb_gs) {
+        SgxDevMem m;                                                              // all or nothing
+        int *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr, *e = nullptr;
+        if ((rc = m.alloc(&a, N)) || (rc = m.alloc(&b, N)) || (rc = m.alloc(&c, N)) || (rc = m.alloc(&d, N)) || (rc = m.alloc(&e, (size_t)GS_FIELDS))) return rc;
+        h->mem.owned.insert(h->mem.owned.end(), m.owned.begin(), m.owned.end()); m.owned.clear();
+        h->gb_row_of = a; h->gb_orig = b; h->gb_level = c; h->gb_prow = d; h->gb_gs = e;
+    }
+    if ((rc = covis_sync_tables(h)) != SGX_OK) return rc;
+    const sgx_stream_t s = (sgx_stream_t)stream;
+    SgxCovisArgs A = covis_args(h);
+    SgxCovisGbaArgs B{};
+    B.n_origins = n_origins; B.nk = nk; B.origins = origins_dev; B.kf_ids = kf_ids_dev; B.in_gba = in_gba_dev; B.Tcw = Tcw_dev; B.TcwGBA = TcwGBA_dev; B.Tcw_out = Tcw_out_dev;
+    B.TcwBef = TcwBef_dev; B.kf_state = kf_state_dev; B.report = (SgxCovisGbaReport *)report_dev;
+    B.row_of = h->gb_row_of; B.orig = h->gb_orig; B.level = h->gb_level; B.prow = h->gb_prow; B.gs = h->gb_gs;
+    SGX_LAUNCH(k_covis_gba_begin, dim3(1), dim3(256), s, A, B);
+    SGX_LAUNCH(k_covis_gba_depth, dim3((unsigned)((nk + 255) / 256)), dim3(256), s, A, B);
+    SGX_LAUNCH(k_covis_gba_levels, dim3(1), dim3(256), s, A, B);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+extern "C" int sgx_gba_correct_points_dev(int n, const float *xw_dev, const uint8_t *in_gba_dev, const float *xw_gba_dev, const int32_t *ref_dev, const uint8_t *kf_state_dev,
+                                          const float *TcwBef_dev, const float *Tcw_out_dev, float *xw_out_dev, void *stream)
+{
+    if (n < 0) return SGX_ERR_INVALID;
+    if (n == 0) return SGX_OK;
+    if (!xw_dev || !in_gba_dev || !xw_gba_dev || !ref_dev || !kf_state_dev || !TcwBef_dev || !Tcw_out_dev || !xw_out_dev) return SGX_ERR_INVALID;
+    SGX_LAUNCH(k_gba_correct_points, dim3((unsigned)((n + 255) / 256)), dim3(256), (sgx_stream_t)stream, n, xw_dev, in_gba_dev, xw_gba_dev, ref_dev, kf_state_dev, TcwBef_dev,
+               Tcw_out_dev, xw_out_dev);
+    SGX_CHECK_HIP(hipGetLastError());
+    return SGX_OK;
+}
+
+extern "C" int sgx_covis_gba_update(sgx_covis *h, int n_origins, const int32_t *origins, int nk, const int32_t *kf_ids, const uint8_t *in_gba, const float *Tcw, const float *TcwGBA,
+                                    float *Tcw_out, float *TcwBef, uint8_t *kf_state, sgx_covis_gba_report *report)
+{
+    if (!h || n_origins < 1 || n_origins > h->max_kf || !origins || nk < 1 || nk > h->max_kf || !kf_ids || !in_gba || !Tcw || !TcwGBA || !Tcw_out || !TcwBef || !kf_state) return SGX_ERR_INVALID;
+    SgxDevMem m; int rc;
+    const size_t K = (size_t)nk;
+    int32_t *d_o = nullptr, *d_k = nullptr; uint8_t *d_g = nullptr, *d_s = nullptr; float *d_T = nullptr, *d_G = nullptr, *d_O = nullptr, *d_B = nullptr; sgx_covis_gba_report *d_rep = nullptr;
+    if ((rc = covis_stage(m, &d_o, origins, (size_t)n_origins, (size_t)n_origins)) || (rc = covis_stage(m, &d_k, kf_ids, K, K)) || (rc = covis_stage(m, &d_g, in_gba, K, K)) ||
+        (rc = covis_stage(m, &d_T, Tcw, 12 * K, 12 * K)) || (rc = covis_stage(m, &d_G, TcwGBA, 12 * K, 12 * K)) || (rc = m.alloc(&d_O, 12 * K)) || (rc = m.alloc(&d_B, 12 * K)) ||
+        (rc = m.alloc(&d_s, K)) || (rc = m.alloc(&d_rep, 1))) return rc;
+    SGX_CHECK_HIP(hipMemcpy(d_B, TcwBef, 12 * K * 4, hipMemcpyHostToDevice));     // a row of a keyframe that is not visited stays the caller's
+    if ((rc = sgx_covis_gba_update_dev(h, n_origins, d_o, nk, d_k, d_g, d_T, d_G, d_O, d_B, d_s, d_rep, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    sgx_covis_gba_report R;
+    SGX_CHECK_HIP(hipMemcpy(&R, d_rep, sizeof(R), hipMemcpyDeviceToHost));
+    if (report) *report = R;
+    if (R.status != SGX_OK) return R.status;                                      // nothing was written
+    SGX_CHECK_HIP(hipMemcpy(Tcw_out, d_O, 12 * K * 4, hipMemcpyDeviceToHost));
+    SGX_CHECK_HIP(hipMemcpy(TcwBef, d_B, 12 * K * 4, hipMemcpyDeviceToHost));
+    SGX_CHECK_HIP(hipMemcpy(kf_state, d_s, K, hipMemcpyDeviceToHost));
+    return SGX_OK;
+}
+
+extern "C" int sgx_gba_correct_points(int n, const float *xw, const uint8_t *in_gba, const float *xw_gba, const int32_t *ref, int nk, const uint8_t *kf_state, const float *TcwBef,
+                                      const float *Tcw_out, float *xw_out)
+{
+    if (n < 0 || nk < 0) return SGX_ERR_INVALID;
+    if (n == 0) return SGX_OK;
+    if (!xw || !in_gba || !xw_gba || !ref || !xw_out || (nk > 0 && (!kf_state || !TcwBef || !Tcw_out))) return SGX_ERR_INVALID;
+    for (int i = 0; i < n; i++) if (ref[i] < -1 || ref[i] >= nk) return SGX_ERR_INVALID;      // the host form checks the rows the device form trusts
+    SgxDevMem m; int rc;
+    const size_t P = (size_t)n, K = (size_t)nk;
+    float *d_x = nullptr, *d_g = nullptr, *d_B = nullptr, *d_O = nullptr, *d_y = nullptr; uint8_t *d_f = nullptr, *d_s = nullptr; int32_t *d_r = nullptr;
+    if ((rc = covis_stage(m, &d_x, xw, 3 * P, 3 * P)) || (rc = covis_stage(m, &d_f, in_gba, P, P)) || (rc = covis_stage(m, &d_g, xw_gba, 3 * P, 3 * P)) || (rc = covis_stage(m, &d_r, ref, P, P)) ||
+        (rc = covis_stage(m, &d_s, kf_state, K, K)) || (rc = covis_stage(m, &d_B, TcwBef, 12 * K, 12 * K)) || (rc = covis_stage(m, &d_O, Tcw_out, 12 * K, 12 * K)) ||
+        (rc = m.alloc(&d_y, 3 * P))) return rc;
+    if ((rc = sgx_gba_correct_points_dev(n, d_x, d_f, d_g, d_r, d_s, d_B, d_O, d_y, nullptr)) != SGX_OK) return rc;
+    SGX_CHECK_HIP(hipStreamSynchronize((sgx_stream_t)0));
+    SGX_CHECK_HIP(hipMemcpy(xw_out, d_y, 3 * P * 4, hipMemcpyDeviceToHost));
+    return SGX_OK;
 }

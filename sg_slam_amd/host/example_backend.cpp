@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include "sgx_host.hpp"
 
 static std::vector<uint8_t> slurp(const char *p)
@@ -183,6 +184,60 @@ int main(int argc, char **argv)
         printf(" loop edges of 1:"); for (int32_t k : G.GetLoopEdges(1)) printf(" %d", k);
         printf("\nposes"); for (int k = 1; k <= 3; k++) for (int i = 0; i < 12; i++) printf(" %.9g", T[12 * (size_t)k + i]);
         printf("\npoints"); for (int i = 0; i < 3 * 30; i++) printf(" %.9g", xw[(size_t)i]);
+        printf("\n");
+        return 0;
+    }
+    if (argc >= 4 && !strcmp(argv[1], "loopclose")) {               // the loop-closing thread on a ring: loopclose voc.txt ring.bin (tests/test_loopclose_host_cpp_gpu.py writes it)
+        sgx::ORBVocabulary voc;
+        if (!voc.loadFromTextFile(argv[2])) { fprintf(stderr, "Wrong path to vocabulary.\n"); return 1; }
+        const std::vector<uint8_t> raw = slurp(argv[3]); size_t at = 0;
+        auto geti = [&]() { int32_t v; memcpy(&v, &raw[at], 4); at += 4; return v; };
+        auto getf = [&](size_t n) { std::vector<float> v(n); if (n) memcpy(v.data(), &raw[at], 4 * n); at += 4 * n; return v; };
+        auto getv = [&](size_t n) { std::vector<int32_t> v(n); if (n) memcpy(v.data(), &raw[at], 4 * n); at += 4 * n; return v; };
+        const int nkf = geti(), nextra = geti(), cap = geti(), npts = geti(), ndup = geti(), cur = geti(), loop = geti();
+        struct KF { int32_t id, parent, i0; std::vector<float> uright, depth, uv, T; std::vector<int32_t> pts, words; };
+        std::vector<KF> kfs((size_t)(nkf + nextra));
+        for (KF &k : kfs) {
+            k.id = geti(); k.parent = geti(); k.i0 = geti(); const size_t n = (size_t)geti();
+            k.uright = getf((size_t)cap); k.depth = getf((size_t)cap); k.uv = getf(2 * (size_t)cap); k.pts = getv(n); k.T = getf(12); k.words = getv((size_t)geti());
+        }
+        std::vector<float> xw = getf(3 * (size_t)npts); const std::vector<int32_t> pref = getv((size_t)npts), dup = getv(2 * (size_t)ndup);
+        sgx::Optimizer::Sim3 Scw; memcpy(Scw.v, &raw[at], 64); at += 64;
+        const std::vector<float> camv = getf(5), inv = getf(8);
+        const sgx_camera cam{camv[0], camv[1], camv[2], camv[3], camv[4], 0.f, 640.f, 0.f, 480.f};
+        sgx::CovisibilityGraph G(64, cap, npts, 8 * npts, 8, false, 40.0f);
+        sgx::KeyFrameDatabase db(voc, 64);
+        sgx::LoopClosing L(G, db);
+        std::map<int32_t, const KF *> by_id; std::map<int32_t, std::vector<float>> T;
+        auto iota = [](size_t n, int from) { std::vector<int32_t> v(n); for (size_t i = 0; i < n; i++) v[i] = from + (int)i; return v; };
+        auto add = [&](const KF &k) {
+            G.AddKeyFrame(k.id, std::vector<int32_t>((size_t)cap, 0), k.uright, k.depth); G.SetObservations(k.id, iota(k.pts.size(), 0), k.pts);
+            if (k.parent >= 0) G.SetObservations(k.parent, iota(k.pts.size(), k.i0), k.pts);
+            G.UpdateConnections(k.id); by_id[k.id] = &k; T[k.id] = k.T;
+        };
+        auto bow = [](const KF &k) { sgx::LoopClosing::BowVector v; for (int32_t w : k.words) v.emplace_back(w, 1.0 / (double)k.words.size()); return v; };
+        printf("accepted");
+        for (int t = 0; t < nkf; t++) { add(kfs[(size_t)t]); if (L.DetectLoop(kfs[(size_t)t].id, bow(kfs[(size_t)t]))) { printf(" %d enough", kfs[(size_t)t].id); for (int32_t c : L.mvpEnoughConsistentCandidates) printf(" %d", c); } }
+        printf(" groups"); for (const auto &g : G.GetConsistentGroups()) { printf(" ["); for (int32_t k : g.first) printf(" %d", k); printf(" ]:%d", g.second); }
+        const sgx::Optimizer::LoopResult r = L.CorrectLoop(cur, loop, Scw, [&](int32_t id, float *o) { memcpy(o, T[id].data(), 48); }, [&](int32_t id, const float *o) { memcpy(T[id].data(), o, 48); }, xw,
+                                                           [&](const sgx::CovisibilityGraph::LoopGroup &, const std::vector<sgx::Optimizer::Sim3> &) { for (int i = 0; i < ndup; i++) G.Replace(dup[2 * (size_t)i], dup[2 * (size_t)i + 1]); });
+        printf("\nloop last %ld group", L.mLastLoopKFid); for (int32_t k : r.group.group_id) printf(" %d", k);
+        printf(" edges %zu loop edges of %d:", r.graph.e_i.size(), cur); for (int32_t k : G.GetLoopEdges(cur)) printf(" %d", k);
+        const auto u = L.RunGlobalBundleAdjustment((unsigned long)cur, cam, { 0 },
+            [&](int32_t id, float *o) { memcpy(o, T[id].data(), 48); },
+            [&](int32_t id, int32_t idx, float *o) { const KF &k = *by_id[id]; o[0] = k.uv[2 * (size_t)idx]; o[1] = k.uv[2 * (size_t)idx + 1]; o[2] = k.uright[(size_t)idx]; },
+            [&](int octave) { return inv[(size_t)octave]; },
+            [&](int32_t id, float *o) { memcpy(o, &xw[3 * (size_t)id], 12); },
+            [&](int32_t id) { return pref[(size_t)id]; },
+            [&]() { for (int t = nkf; t < nkf + nextra; t++) add(kfs[(size_t)t]); });
+        printf("\ngba visited %d propagated %d unreached %d depth %d state", u.update.report.n_visited, u.update.report.n_propagated, u.update.report.n_unreached, u.update.report.max_depth);
+        for (uint8_t v : u.update.kf_state) printf(" %d", v);
+        printf(" ids"); for (int32_t k : u.kf_ids) printf(" %d", k);
+        printf(" early");
+        for (int t = nkf; t < nkf + nextra; t++) { L.DetectLoop(kfs[(size_t)t].id, bow(kfs[(size_t)t])); printf(" %d", L.early ? 1 : 0); }
+        printf(" db %d", db.size());
+        printf("\nposes"); for (float v : u.update.Tcw) printf(" %.9g", v);
+        printf("\npoints"); for (size_t i = 0; i < u.point_ids.size(); i++) printf(" %d %.9g %.9g %.9g", u.point_ids[i], u.update.xw[3 * i], u.update.xw[3 * i + 1], u.update.xw[3 * i + 2]);
         printf("\n");
         return 0;
     }

@@ -12,6 +12,7 @@
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <algorithm>
 #include <vector>
 #include "../../include/sgx.h"
 
@@ -587,6 +588,53 @@ public:
         check(sgx_covis_get_loop_edges(h_, mnId, v.data(), &n), "sgx_covis_get_loop_edges"); v.resize((size_t)n);
         return v;
     }
+    // LoopClosing::DetectLoop (LoopClosing.cc:103-229) on the handle: GetConnectedKeyFrames() of a keyframe in ascending id (what DetectLoopCandidates excludes), the
+    // consistency groups mvConsistentGroups as state of the handle, and the map update of RunGlobalBundleAdjustment (:676-737).
+    std::vector<int32_t> GetConnectedKeyFrames(int32_t mnId)
+    {
+        int32_t off[2] = { 0, 0 }; sgx_covis_report rep{};
+        int rc = sgx_covis_connected_batch(h_, 1, &mnId, off, nullptr, 0, &rep);
+        if (rc != SGX_OK && rc != SGX_ERR_NOMEM) check(rc, "sgx_covis_connected_batch");
+        std::vector<int32_t> ids((size_t)off[1]);
+        if (off[1]) check(sgx_covis_connected_batch(h_, 1, &mnId, off, ids.data(), off[1], &rep), "sgx_covis_connected_batch");
+        return ids;
+    }
+    struct ConsistentGroup { std::vector<int32_t> first; int32_t second = 0; };      // ConsistentGroup = pair<set<KeyFrame*>, int>
+    void ReserveConsistentGroups(int maxGroups) { check(sgx_covis_consistency_reserve(h_, maxGroups), "sgx_covis_consistency_reserve"); }
+    void ClearConsistentGroups() { check(sgx_covis_consistency_clear(h_), "sgx_covis_consistency_clear"); }
+    // :152-211 for vpCandidateKFs; returns mvpEnoughConsistentCandidates (an empty candidate list clears the groups, :147)
+    std::vector<int32_t> CheckConsistency(const std::vector<int32_t> &vpCandidateKFs, int mnCovisibilityConsistencyTh = 3, sgx_covis_consistency_report *report = nullptr)
+    {
+        std::vector<int32_t> enough(vpCandidateKFs.size() + 1); int32_t n = 0;
+        check(sgx_covis_consistency(h_, (int)vpCandidateKFs.size(), vpCandidateKFs.data(), mnCovisibilityConsistencyTh, enough.data(), &n, report), "sgx_covis_consistency");
+        enough.resize((size_t)n);
+        return enough;
+    }
+    std::vector<ConsistentGroup> GetConsistentGroups()
+    {
+        int64_t bytes = 0; int32_t n = 0, G = 0;
+        check(sgx_covis_consistency_info(h_, &bytes, &n, &G), "sgx_covis_consistency_info");
+        std::vector<int32_t> cnt((size_t)G + 1), off((size_t)G + 1), ids((size_t)n * (size_t)maxkf_ + 1);
+        check(sgx_covis_get_consistent_groups(h_, &n, cnt.data(), off.data(), (int)ids.size(), ids.data()), "sgx_covis_get_consistent_groups");
+        std::vector<ConsistentGroup> out((size_t)n);
+        for (int g = 0; g < n; g++) { out[(size_t)g].first.assign(ids.begin() + off[(size_t)g], ids.begin() + off[(size_t)g + 1]); out[(size_t)g].second = cnt[(size_t)g]; }
+        return out;
+    }
+    // :676-737: kf_ids lists every live keyframe once; Tcw / TcwGBA 12 floats per row; point rows as sgx_gba_correct_points takes them (ref = a row or -1)
+    struct GbaUpdate { std::vector<float> Tcw, TcwBef, xw; std::vector<uint8_t> kf_state; sgx_covis_gba_report report{}; };
+    GbaUpdate GlobalBundleAdjustmentUpdate(const std::vector<int32_t> &origins, const std::vector<int32_t> &kf_ids, const std::vector<uint8_t> &in_gba, const std::vector<float> &Tcw,
+                                           const std::vector<float> &TcwGBA, const std::vector<float> &xw, const std::vector<uint8_t> &point_in_gba, const std::vector<float> &xw_gba,
+                                           const std::vector<int32_t> &point_ref)
+    {
+        GbaUpdate u; const size_t nk = kf_ids.size(), np = point_ref.size();
+        if (in_gba.size() != nk || Tcw.size() != 12 * nk || TcwGBA.size() != 12 * nk || xw.size() != 3 * np || xw_gba.size() != 3 * np || point_in_gba.size() != np) check(SGX_ERR_INVALID, "GlobalBundleAdjustmentUpdate");
+        u.Tcw.assign(12 * nk, 0.f); u.TcwBef.assign(12 * nk, 0.f); u.kf_state.assign(nk, 0); u.xw = xw;
+        check(sgx_covis_gba_update(h_, (int)origins.size(), origins.data(), (int)nk, kf_ids.data(), in_gba.data(), Tcw.data(), TcwGBA.data(), u.Tcw.data(), u.TcwBef.data(),
+                                   u.kf_state.data(), &u.report), "sgx_covis_gba_update");
+        if (np) check(sgx_gba_correct_points((int)np, xw.data(), point_in_gba.data(), xw_gba.data(), point_ref.data(), (int)nk, u.kf_state.data(), u.TcwBef.data(), u.Tcw.data(),
+                                             u.xw.data()), "sgx_gba_correct_points");      // :705-736 through sgx_gba_correct_points_dev
+        return u;
+    }
     struct LoopGroup { std::vector<int32_t> group_id, group_vertex, point_id, point_ref; sgx_covis_loop_report report{}; };
     LoopGroup loop_begin(int32_t cur)
     {
@@ -802,6 +850,86 @@ public:
         if (cur != loop) covis.AddLoopEdge(loop, cur);
         return r;
     }
+};
+
+// ORB_SLAM2::LoopClosing (LoopClosing.h, src/sg-slam/src/LoopClosing.cc) over the covisibility graph, the keyframe database and the optimiser: DetectLoop (:103-229),
+// CorrectLoop (:402-585) and RunGlobalBundleAdjustment (:645-749).  ComputeSim3's orchestration (:231-400), SetNotErase / SetErase and InformNewBigChange stay the caller's.
+class LoopClosing {
+public:
+    typedef ORBVocabulary::BowVector BowVector;
+    LoopClosing(CovisibilityGraph &covis, KeyFrameDatabase &db, bool bFixScale = true, int nCovisibilityConsistencyTh = 3)
+        : covis_(covis), db_(db), mbFixScale(bFixScale), mnCovisibilityConsistencyTh(nCovisibilityConsistencyTh) {}
+    long mLastLoopKFid = 0;
+    std::vector<int32_t> mvpEnoughConsistentCandidates, vpCandidateKFs;
+    bool early = false; float minScore = 1.0f;                                   // what the last DetectLoop saw
+    // bool DetectLoop() for mpCurrentKF = mnId with its mBowVec; the keyframe enters the database on every exit (:116, :146, :215)
+    bool DetectLoop(int32_t mnId, const BowVector &mBowVec)
+    {
+        struct Add { KeyFrameDatabase &db; int32_t id; const BowVector &v; ~Add() { db.add(id, v); } } add{db_, mnId, mBowVec};
+        mvpEnoughConsistentCandidates.clear(); vpCandidateKFs.clear();
+        early = mnId < mLastLoopKFid + 10;                                       // :114
+        if (early) return false;
+        std::vector<int32_t> listed;
+        for (const auto &e : covis_.GetOrderedConnectedKeyFrames(mnId)) listed.push_back(e.first);      // GetVectorCovisibleKeyFrames()
+        minScore = db_.MinScore(mBowVec, listed);                                // :126-138
+        vpCandidateKFs = db_.DetectLoopCandidates(mBowVec, covis_.GetConnectedKeyFrames(mnId), minScore);      // :141
+        mvpEnoughConsistentCandidates = covis_.CheckConsistency(vpCandidateKFs, mnCovisibilityConsistencyTh);    // :144-211; no candidate clears the groups
+        return !mvpEnoughConsistentCandidates.empty();
+    }
+    // void CorrectLoop() through Optimizer::CorrectLoop; mLastLoopKFid = mpCurrentKF->mnId (:584)
+    template <class GetPose, class SetPose, class Fuse>
+    Optimizer::LoopResult CorrectLoop(int32_t cur, int32_t loop, const Optimizer::Sim3 &Scw, GetPose pose, SetPose set_pose, std::vector<float> &xw, Fuse fuse)
+    {
+        Optimizer::LoopResult r = Optimizer::CorrectLoop(covis_, cur, loop, Scw, pose, set_pose, xw, fuse, mbFixScale);
+        mLastLoopKFid = cur;
+        return r;
+    }
+    // void RunGlobalBundleAdjustment(unsigned long nLoopKF): the global graph of the handle, gathered by the caller's callbacks, Optimizer::BundleAdjustment with the
+    // results kept apart (mTcwGBA / mPosGBA), then the map update (:676-737) for the map as it stands after while_running() (what LocalMapping did meanwhile).
+    //   pose(mnId, float[12]) = Tcw now; observation(mnId, idx, float[3]) = (u, v, uR); invSigma2(octave); point(id, float[3]) = GetWorldPos() now;
+    //   reference(id) = GetReferenceKeyFrame()->mnId or -1.  Returns the update; ids / points name its rows.
+    struct GbaResult { CovisibilityGraph::GbaUpdate update; std::vector<int32_t> kf_ids, point_ids; sgx_ba_stats stats{}; };
+    template <class GetPose, class GetObs, class InvSigma2, class GetPoint, class GetRef, class Meanwhile>
+    GbaResult RunGlobalBundleAdjustment(unsigned long nLoopKF, const sgx_camera &cam, const std::vector<int32_t> &origins, GetPose pose, GetObs observation, InvSigma2 invSigma2,
+                                        GetPoint point, GetRef reference, Meanwhile while_running, int nIterations = 10)
+    {
+        (void)nLoopKF;
+        const CovisibilityGraph::BaGraph g = covis_.ba_graph(0, SGX_COVIS_BA_GLOBAL);
+        Optimizer::LocalGraph P; const size_t nkf = g.pose_id.size(), npt = g.point_id.size(), ne = g.edge_pose.size();
+        P.poses.assign(16 * nkf, 0.f); P.pose_fixed = g.pose_fixed; P.points.resize(3 * npt); P.edge_pose = g.edge_pose; P.edge_point = g.edge_point; P.edge_obs.resize(3 * ne); P.edge_info.resize(ne);
+        for (size_t k = 0; k < nkf; k++) { pose(g.pose_id[k], &P.poses[16 * k]); P.poses[16 * k + 15] = 1.f; }
+        for (size_t i = 0; i < npt; i++) point(g.point_id[i], &P.points[3 * i]);
+        for (size_t e = 0; e < ne; e++) {
+            observation(g.pose_id[(size_t)g.edge_pose[e]], g.edge_kp[e], &P.edge_obs[3 * e]);
+            if (!(g.edge_attr[e] & SGX_COVIS_ATTR_RIGHT)) P.edge_obs[3 * e + 2] = -1.f;      // Optimizer.cc:594
+            P.edge_info[e] = invSigma2(g.edge_attr[e] & SGX_COVIS_ATTR_OCTAVE);
+        }
+        const Optimizer::LocalGraph before = P;
+        GbaResult R;
+        Optimizer::BundleAdjustment(P, cam, nIterations, nullptr, false, &R.stats);      // GlobalBundleAdjustemnt(mpMap, 10, &mbStopGBA, nLoopKF, false)
+        while_running();
+        const CovisibilityGraph::BaGraph now = covis_.ba_graph(0, SGX_COVIS_BA_GLOBAL);
+        R.kf_ids = now.pose_id; R.point_ids = now.point_id;
+        const size_t nk = R.kf_ids.size(), np = R.point_ids.size();
+        std::vector<uint8_t> in_gba(nk, 0), pin(np, 0); std::vector<float> T(12 * nk), TG(12 * nk, 0.f), X(3 * np), XG(3 * np, 0.f); std::vector<int32_t> ref(np, -1);
+        for (size_t r = 0, j = 0; r < nk; r++) {                                 // both rows ascend in id
+            while (j < nkf && g.pose_id[j] < R.kf_ids[r]) j++;
+            if (j < nkf && g.pose_id[j] == R.kf_ids[r]) { in_gba[r] = 1; memcpy(&T[12 * r], &before.poses[16 * j], 48); memcpy(&TG[12 * r], &P.poses[16 * j], 48); }
+            else pose(R.kf_ids[r], &T[12 * r]);
+        }
+        for (size_t i = 0, j = 0; i < np; i++) {
+            while (j < npt && g.point_id[j] < R.point_ids[i]) j++;
+            if (j < npt && g.point_id[j] == R.point_ids[i]) { pin[i] = 1; memcpy(&X[3 * i], &before.points[3 * j], 12); memcpy(&XG[3 * i], &P.points[3 * j], 12); }
+            else point(R.point_ids[i], &X[3 * i]);
+            const int32_t k = reference(R.point_ids[i]);
+            const auto it = std::lower_bound(R.kf_ids.begin(), R.kf_ids.end(), k);
+            ref[i] = (k >= 0 && it != R.kf_ids.end() && *it == k) ? (int32_t)(it - R.kf_ids.begin()) : -1;
+        }
+        R.update = covis_.GlobalBundleAdjustmentUpdate(origins, R.kf_ids, in_gba, T, TG, X, pin, XG, ref);
+        return R;
+    }
+private:
+    CovisibilityGraph &covis_; KeyFrameDatabase &db_; bool mbFixScale; int mnCovisibilityConsistencyTh;
 };
 
 // ORB_SLAM2::Detector2D (Detector2D.h:45-67): same public result members as the reference (read by Frame.cc:482-500)

@@ -91,6 +91,36 @@ class Optimizer:
         return dict(iterations=st.iterations_first, chi2=st.chi2_first, free_poses=st.free_poses)
 
     @staticmethod
+    def ApplyGlobalBundleAdjustment(problem, graph, covis, origins, point_ref, Tcw=None, xw=None, stream=None):
+        """The map update of LoopClosing::RunGlobalBundleAdjustment (LoopClosing.cc:676-737) from what BundleAdjustment(nLoopKF != 0) left in `problem` ('poses_gba',
+        'points_gba') for the keyframes and points of `graph` (global_ba_graph when the solver started).  The map of `covis` as it stands now may hold more: Tcw (by
+        keyframe id) and xw (by point id) give their poses and positions.  origins = mvpKeyFrameOrigins as ids; point_ref = GetReferenceKeyFrame()->mnId by point id
+        (a dict or an array; missing or -1: none).  Returns Tcw {id: 3 x 4}, xw {point id: position}, kf_state {id: bits}, and the rows of covis.gba_update."""
+        assert 'poses_gba' in problem, 'BundleAdjustment was not run with nLoopKF != 0'
+        now = covis.global_ba_graph(stream=stream)
+        assert now['status'] == 0
+        ids = [int(k) for k in now['pose_id']]; pids = [int(p) for p in now['point_id']]
+        in_kf = {int(k): j for j, k in enumerate(graph['pose_id'])}; in_pt = {int(p): j for j, p in enumerate(graph['point_id'])}
+        T = np.zeros((len(ids), 3, 4), 'f4'); G = np.zeros((len(ids), 3, 4), 'f4'); g = np.zeros(len(ids), 'u1')
+        for r, k in enumerate(ids):
+            if k in in_kf:
+                j = in_kf[k]; g[r] = 1; T[r] = np.asarray(problem['poses'], 'f4').reshape(-1, 4, 4)[j, :3]; G[r] = np.asarray(problem['poses_gba'], 'f4').reshape(-1, 4, 4)[j, :3]
+            else: T[r] = np.asarray(Tcw[k], 'f4').reshape(-1, 4)[:3]
+        row = {k: r for r, k in enumerate(ids)}
+        X = np.zeros((len(pids), 3), 'f4'); XG = np.zeros((len(pids), 3), 'f4'); pg = np.zeros(len(pids), 'u1'); ref = np.full(len(pids), -1, 'i4')
+        for i, p in enumerate(pids):
+            if p in in_pt: pg[i] = 1; X[i] = problem['points'][in_pt[p]]; XG[i] = problem['points_gba'][in_pt[p]]
+            else: X[i] = np.asarray(xw[p], 'f4')
+            k = -1 if point_ref is None else (point_ref.get(p, -1) if isinstance(point_ref, dict) else int(point_ref[p]))
+            ref[i] = row.get(int(k), -1)
+        out = covis.gba_update(origins, ids, g, T, G, points=dict(xw=X, in_gba=pg, xw_gba=XG, ref=ref), stream=stream)
+        if out['status'] == 0:
+            out['Tcw'] = {k: out['Tcw_out'][r] for r, k in enumerate(ids)}; out['xw'] = {p: out['xw_out'][i] for i, p in enumerate(pids)}
+            out['kf_state_by_id'] = {k: int(out['kf_state'][r]) for r, k in enumerate(ids)}
+        out['kf_ids'] = ids; out['point_ids'] = pids; out['in_gba'] = g; out['Tcw_in'] = T; out['TcwGBA'] = G; out['points_in'] = dict(xw=X, in_gba=pg, xw_gba=XG, ref=ref)
+        return out
+
+    @staticmethod
     def OptimizeSim3(p1c, p2c, obs1, obs2, info1, info2, K1, K2, S12, th2=10.0, bFixScale=False, lib=None):
         """Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (Optimizer.cc:1046-1257) on the flattened correspondences (see include/sgx.h):
         returns (nIn, S12[8] = (qx, qy, qz, qw, tx, ty, tz, s), inlier[n], iterations[2])."""
