@@ -1030,6 +1030,74 @@ int sgx_covis_gba_update(sgx_covis *h, int n_origins, const int32_t *origins, in
 int sgx_gba_correct_points(int n, const float *xw, const uint8_t *in_gba, const float *xw_gba, const int32_t *ref, int nk, const uint8_t *kf_state, const float *TcwBef,
                            const float *Tcw_out, float *xw_out);
 
+/* ---- Keyframe store and LocalMapping::CreateNewMapPoints (src/sg-slam/src/LocalMapping.cc:207-452, :536-553) ------------------------------------------------------------
+ * sgx_kfstore holds what LocalMapping reads of a keyframe on the device: mvKeysUn, mvKeys, the descriptors, mvuRight, mvDepth, the pose and the features grouped by
+ * vocabulary node in FeatureVector order (ascending node, ascending feature index inside a node, feat_node < 0 left out).  One sensor and one ORB pyramid for all
+ * keyframes.  The relation keyframe x map point stays in sgx_covis: the queries below take mvpMapPoints rows (point ids, -1 none: sgx_covis_get_keyframe_points).
+ * sgx_kfstore_create: at most 4096 keyframes of at most cap <= 8192 keypoints (SGX_ERR_UNSUPPORTED beyond); nlevels in [2, 12] (ratioFactor reads level 1).  Device
+ *   memory: max_keyframes x (cap x 108 + 64) bytes, allocated at create; the batched call adds a workspace of 26 x cap bytes per query of the largest batch seen
+ *   (sgx_kfstore_info reports the total and, of it, the workspace).
+ * Mutations: host pointers, synchronous, none while a batch of this handle is in flight.  Error conventions as rule 6 of the covisibility section: a refused mutation
+ *   leaves the handle unchanged.  add uploads this keyframe only; keys may be NULL (= keys_un; UnprojectStereo reads mvKeys); Tcw is 3 x 4 row-major (12 floats read).
+ *   SGX_ERR_INVALID: a negative or known id, n outside [0, cap], an octave of keys_un outside [0, nlevels), a missing array; SGX_ERR_NOMEM: a full store.
+ *   set_pose / erase of an unknown id: SGX_ERR_INVALID.  erase gives the slot back; clear drops every keyframe.
+ * A failed create clears *out and returns the status that occurred: SGX_ERR_NOMEM for a refused allocation, SGX_ERR_DEVICE for a failed copy.
+ *
+ * sgx_create_new_map_points_batch_dev: every pointer is device memory, asynchronous on `stream`, one launch for the Q queries, nothing read back, two runs byte-identical,
+ *   a batch of Q equal to Q single calls.  A handle serves one call at a time.  Query q: the current keyframe cur_ids_dev[q]; its neighbours nb_ids_dev[nb_offsets_dev[q] ..
+ *   nb_offsets_dev[q + 1]) in the order of GetBestCovisibilityKeyFrames(nn); first_new_id_dev[q]; median_depth_dev (optional, one entry per neighbour, aligned with
+ *   nb_ids_dev): NULL selects the stereo / RGB-D gate baseline < mb (:249-253), given it selects the monocular gate baseline / median < 0.01 (:254-261).
+ *   mp_rows_dev (in/out, pitch cap): query q owns rows q + nb_offsets_dev[q] (the current keyframe) .. q + nb_offsets_dev[q + 1] (its neighbours, in order).
+ *   Per neighbour, in order: the camera centres, the baseline and its gate; ComputeF12; the epipole (ORBmatcher.cc:666-674); the join of the two stored node lists;
+ *   SearchForTriangulation(cur, kf2, F12, pairs, false) without the orientation check (ORBmatcher(0.6, false)), has_mp = row[i] >= 0; the per-pair body :286-431; the
+ *   commit :433-447 in ascending idx1: the k-th accepted pair of the QUERY writes first_new_id + k into both rows and appends its record, and the next neighbour's search
+ *   sees the updated row of the current keyframe.
+ *   Outputs, rows of pitch cap per query, the first n_new_dev[q] entries written: new_kf2 / new_idx1 / new_idx2, new_x3d (x3), and the two MapPoint post-steps the
+ *   reference runs at once (:442-444) over the point's two observations in ascending keyframe id (rule 1): new_desc (x32 bytes, ComputeDistinctiveDescriptors; 4-byte
+ *   aligned) and new_normal (x3) / new_min_dist / new_max_dist (UpdateNormalAndDepth, mpRefKF = the current keyframe, level = kp1.octave).  At most n_cur <= cap points can
+ *   be created, because every accepted pair fills a free keypoint of the current keyframe: the rows cannot overflow and there is no capacity status.
+ *   report_dev: one record per neighbour (aligned with nb_ids_dev), always written whole; fields that were not computed are 0.  pair_idx1_dev / pair_idx2_dev / pair_ok_dev
+ *   (each optional, one row of pitch cap per neighbour): vMatchedIndices and which pairs survived, the first n_pairs entries written.
+ *   Arithmetic: Ow1 / Ow2 of the report are GetCameraCenter(), Ow = -Rwc * tcw with Rwc stored (float products left to right, alpha = -1 last); they serve the baseline,
+ *   the epipole and UpdateNormalAndDepth.  The per-pair body forms its centres as sgx_triangulate_new_map_points does (-Rcw.t() * tcw as one product, double
+ *   accumulation), so that it equals that entry bit for bit.  cv::norm accumulates in double.  F12 = K1.t().inv() * t12x * R12 * K2.inv(): products with a transposed
+ *   operand (R1w * R2w.t(), -R1w * R2w.t()) accumulate in double, the others are float products left to right; A * B + C is one gemm; inv() is OpenCV's closed 3 x 3 form
+ *   with determinant and cofactors in double, and inv() * M is the inverse times M.
+ *   Statuses of a neighbour: SGX_NEWPOINTS_PROCESSED, SGX_NEWPOINTS_SKIPPED (the gate), SGX_ERR_INVALID (the neighbour or the current keyframe is not in the store, or
+ *   they are the same keyframe): that neighbour contributes nothing and the others are unaffected.  Q == 0: SGX_OK, nothing enqueued.  Q < 0 or a missing array:
+ *   SGX_ERR_INVALID for the call, nothing enqueued.
+ * sgx_create_new_map_points: one query from host memory, synchronous, a batch of one through the entry above; mp_rows holds n_nb + 1 rows of cap, report n_nb records,
+ *   the new_* arrays cap entries, the pair arrays n_nb rows of cap. */
+#define SGX_NEWPOINTS_PROCESSED 0
+#define SGX_NEWPOINTS_SKIPPED 1
+typedef struct sgx_kfstore sgx_kfstore;
+typedef struct sgx_newpoints_report {
+    int32_t status;                         /* SGX_NEWPOINTS_PROCESSED, SGX_NEWPOINTS_SKIPPED, SGX_ERR_INVALID */
+    int32_t kf2;                            /* the neighbour's id as given */
+    int32_t n_pairs, n_new;                 /* vMatchedIndices.size() and the points created with this neighbour */
+    float baseline;
+    float F12[9];                           /* row-major */
+    float Ow1[3], Ow2[3];                   /* GetCameraCenter() of the current keyframe and of the neighbour */
+} sgx_newpoints_report;
+int sgx_kfstore_create(int max_keyframes, int cap, const sgx_camera *cam, const float *scale_factors, const float *level_sigma2, int nlevels, sgx_kfstore **out);
+void sgx_kfstore_destroy(sgx_kfstore *h);
+int sgx_kfstore_size(const sgx_kfstore *h);                                                                    /* keyframes held */
+int sgx_kfstore_info(const sgx_kfstore *h, int64_t *device_bytes, int64_t *workspace_bytes);
+int sgx_kfstore_clear(sgx_kfstore *h);
+int sgx_kfstore_add(sgx_kfstore *h, int32_t kf_id, int n, const sgx_keypoint *keys_un, const sgx_keypoint *keys, const uint8_t *desc, const float *uright,
+                    const float *depth, const int32_t *feat_node, const float *Tcw);
+int sgx_kfstore_set_pose(sgx_kfstore *h, int32_t kf_id, const float *Tcw);
+int sgx_kfstore_erase(sgx_kfstore *h, int32_t kf_id);
+int sgx_create_new_map_points_batch_dev(
+    sgx_kfstore *h, int Q, const int32_t *cur_ids_dev, const int32_t *nb_offsets_dev, const int32_t *nb_ids_dev, const int32_t *first_new_id_dev, const float *median_depth_dev,
+    int32_t *mp_rows_dev, int32_t *n_new_dev, int32_t *new_kf2_dev, int32_t *new_idx1_dev, int32_t *new_idx2_dev, float *new_x3d_dev, uint8_t *new_desc_dev,
+    float *new_normal_dev, float *new_min_dist_dev, float *new_max_dist_dev, sgx_newpoints_report *report_dev,
+    int32_t *pair_idx1_dev, int32_t *pair_idx2_dev, uint8_t *pair_ok_dev, void *stream);
+int sgx_create_new_map_points(
+    sgx_kfstore *h, int32_t cur_id, int n_nb, const int32_t *nb_ids, int32_t first_new_id, const float *median_depth, int32_t *mp_rows,
+    int32_t *n_new, int32_t *new_kf2, int32_t *new_idx1, int32_t *new_idx2, float *new_x3d, uint8_t *new_desc, float *new_normal, float *new_min_dist, float *new_max_dist,
+    sgx_newpoints_report *report, int32_t *pair_idx1, int32_t *pair_idx2, uint8_t *pair_ok);
+
 /* The colour conversion at the top of Tracking::GrabImageRGBD (src/sg-slam/src/Tracking.cc:214-227): cvtColor(CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) on
  * 8-bit images, OpenCV's fixed point (R*4899 + G*9617 + B*1868 + 8192) >> 14.  blue_first = !mbRGB.  Pitches in bytes, multiples of 4; pointers 4-byte aligned. */
 int sgx_frame_gray_from_color_batch_dev(int batch, int width, int height, const uint8_t *d_src, int src_pitch, int channels, int blue_first,

@@ -136,6 +136,9 @@ COVIS_BA_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_local_kf', 'n
 COVIS_LOOP_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_group', 'n_points', 'n_connections', 'n_vertices', 'n_edges')] + [('n_kind', 'i4', (4,))])   # sgx_covis_loop_report, 40 B
 COVIS_CONSISTENCY_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_before', 'n_after', 'n_consistent', 'n_pushed_zero', 'n_pushed_nothing', 'n_enough',
                                                                'n_cand')])   # sgx_covis_consistency_report, 32 B
+NEWPOINTS_REPORT_DTYPE = np.dtype([('status', 'i4'), ('kf2', 'i4'), ('n_pairs', 'i4'), ('n_new', 'i4'), ('baseline', 'f4'), ('F12', 'f4', (9,)), ('Ow1', 'f4', (3,)),
+                                   ('Ow2', 'f4', (3,))])   # sgx_newpoints_report, 80 B
+SGX_NEWPOINTS_PROCESSED, SGX_NEWPOINTS_SKIPPED = 0, 1
 COVIS_GBA_REPORT_DTYPE = np.dtype([(k, 'i4') for k in ('status', 'n_visited', 'n_propagated', 'n_unreached', 'max_depth')] + [('pad', 'i4', (3,))])   # sgx_covis_gba_report, 32 B
 
 
@@ -189,6 +192,8 @@ SYMBOLS = [
     'sgx_octomap_cells', 'sgx_octomap_search_dev', 'sgx_octomap_grid_header', 'sgx_octomap_project_dev', 'sgx_octomap_project', 'sgx_octomap_sensor_to_world',
     'sgx_globalmap_create', 'sgx_globalmap_destroy', 'sgx_globalmap_reset', 'sgx_globalmap_append_batch_dev', 'sgx_globalmap_append', 'sgx_globalmap_consolidate_dev',
     'sgx_globalmap_consolidate', 'sgx_globalmap_size', 'sgx_globalmap_read', 'sgx_globalmap_points_dev',
+    'sgx_kfstore_create', 'sgx_kfstore_destroy', 'sgx_kfstore_size', 'sgx_kfstore_info', 'sgx_kfstore_clear', 'sgx_kfstore_add', 'sgx_kfstore_set_pose', 'sgx_kfstore_erase',
+    'sgx_create_new_map_points_batch_dev', 'sgx_create_new_map_points',
 ]
 # the test / tuning taps include/sgx_debug.h declares: exported by tests/taps/libsgx_taps.so and the emulator (-DSGX_DEBUG_TAPS) only, never by the product library
 TAP_SYMBOLS = [
@@ -444,6 +449,16 @@ class SgxLib:
         d.sgx_globalmap_size.argtypes = [vp, vp]
         d.sgx_globalmap_read.argtypes = [vp, vp, C.c_int, vp]
         d.sgx_globalmap_points_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        d.sgx_kfstore_create.argtypes = [C.c_int, C.c_int, C.POINTER(Camera), vp, vp, C.c_int, vp]
+        d.sgx_kfstore_destroy.argtypes = [vp]; d.sgx_kfstore_destroy.restype = None
+        d.sgx_kfstore_size.argtypes = [vp]
+        d.sgx_kfstore_info.argtypes = [vp, vp, vp]
+        d.sgx_kfstore_clear.argtypes = [vp]
+        d.sgx_kfstore_add.argtypes = [vp, C.c_int32, C.c_int] + [vp] * 7
+        d.sgx_kfstore_set_pose.argtypes = [vp, C.c_int32, vp]
+        d.sgx_kfstore_erase.argtypes = [vp, C.c_int32]
+        d.sgx_create_new_map_points_batch_dev.argtypes = [vp, C.c_int] + [vp] * 20
+        d.sgx_create_new_map_points.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int32] + [vp] * 15
         d.sgx_match_search_by_bow_kf.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 4 + [C.c_float, C.c_int, vp, vp]
         d.sgx_match_fuse_search.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 6 + [C.POINTER(Camera), vp, vp, C.c_int, C.c_float, C.c_float, vp, vp, vp]
         d.sgx_hamming_matrix_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
